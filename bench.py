@@ -1,6 +1,9 @@
 """Headline benchmark: SRGAN training images/s on the crowd workload (BASELINE.json configs[2]/[3]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; ``--dump-outputs DIR`` also writes what the
+last timed step computed (``dump_outputs``).  ``--full`` adds the extra legs listed below.
 
 N > 1: one rank per GPU over RCCL.  Started by ``torch.distributed.run`` (RANK / WORLD_SIZE in the environment) the
 script IS a rank; started plainly (``python bench.py --gpus 8``) it launches its N ranks itself -- as a child
@@ -15,7 +18,8 @@ that the gradient penalty is ACTIVE (at the default initialisation every gradien
 backward would multiply exact zeros); ``config.gradient_penalty_last`` is its value in the last timed step.
 Prints ONE JSON line on rank 0.
 
-Extra legs (rank 0, N = 1 only):
+Extra legs of ``--full``: ``config.host_ms_per_step`` (one more iteration, enqueue time only) and ``config.schedule_check``
+(the timed schedule against the single-stream one) on every rank; on rank 0 with N = 1 only:
 * ``roofline``: every contraction launch (the MFMA kernel family = the dominant kernels) of one extra step is
   bracketed with HIP events on its launch stream inside libsrgan_hip.so; achieved = sum(executed 2*M*N*K) /
   sum(event durations), against the fp32 MFMA peak (157.3 TF/s, MI355X_MICROARCH.md).
@@ -25,6 +29,7 @@ Extra legs (rank 0, N = 1 only):
   profiles/ and is null unless that file was measured at this image size / batch on these kernel sources.
 * ``cpu_baseline``: the CPU oracle (PyTorch-CPU fp32 restatement of the reference step, kind "port") timed on
   this box's host cores on a bounded sample (1 warm-up + 3 timed iterations at the same 512x512 shape, batch 1).
+* ``secondary``: the two mixed-precision configurations, each this script run with ``--full`` in a child process.
 """
 import argparse
 import json
@@ -101,7 +106,7 @@ def parse():
                              'RCCL on a one-GPU box)')
     parser.add_argument('--single-device', action='store_true',
                         help='testing aid: every rank uses cuda:0 (with --backend gloo on a one-GPU box)')
-    parser.add_argument('--shape-report', default=None, help='write the per-shape contraction timing table here')
+    parser.add_argument('--shape-report', default=None, help='with --full: write the per-shape contraction timing table of the roofline step here')
     parser.add_argument('--reference-schedule', action='store_true',
                         help='replay the reference forward/backward order instead of sharing forwards')
     parser.add_argument('--workload', default='crowd', choices=sorted(WORKLOADS),
@@ -125,6 +130,11 @@ def parse():
                         help='crowd headline on one GPU: do not append the two mixed-precision configurations (age-vgg-bf16, '
                              'driving-fp16) as `secondary` entries (each is this script run as a child process)')
     parser.add_argument('--secondary-steps', type=int, default=100, help='timed steps of each secondary configuration')
+    parser.add_argument('--full', action='store_true',
+                        help='after the headline, also run the extra legs: host enqueue time, schedule check, roofline and HBM '
+                             'kernel rates, CPU baseline, secondary configurations (each still subject to its --no-* option)')
+    parser.add_argument('--dump-outputs', default=None, metavar='DIR',
+                        help='write the losses and (a fixed sample of) the updated weights of the last timed step to DIR/*.npy')
     return parser.parse_args()
 
 
@@ -468,7 +478,7 @@ def secondary_line(workload, steps, warmup=5, limit_seconds=600):
     check and single-stream roofline step), reduced to the figures the headline line carries as `secondary`."""
     import subprocess
     command = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--steps', str(steps), '--warmup', str(warmup),
-               '--no-cpu-baseline', '--no-secondary']
+               '--full', '--no-cpu-baseline', '--no-secondary']
     completed = None
     try:
         completed = subprocess.run(command, capture_output=True, text=True, timeout=limit_seconds)
@@ -552,6 +562,27 @@ def cpu_baseline_child(image_size, batch=1, warmup=1, timed=3):
                       f'{warmup} warm-up + {timed} timed iterations (dnn_training_step + gan_training_step) of the '
                       f'PyTorch-CPU fp32 oracle, crowd {image_size}x{image_size}: '
                       + ' / '.join(f'{t:.2f}' for t in seconds[warmup:]) + f' s (warm-up {seconds[0]:.2f} s)'}
+
+
+DUMP_SAMPLE = 1 << 20                    # weights per network in --dump-outputs: at most 3 x 4 MiB in all
+
+
+def dump_outputs(experiment, directory):
+    """What the last timed step hands its caller, as float32 .npy files in ``directory``: each loss of the iteration
+    (``<loss name>.npy``, this rank's device scalar) and the updated weights of D, DNN and G (``<network>_weights.npy``):
+    all of a network's weights when it has at most DUMP_SAMPLE, else the same DUMP_SAMPLE positions of its flat weight
+    arena in every run (drawn with seed 0, ascending)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, loss in experiment.last_losses.items():
+        if loss is not None:
+            np.save(os.path.join(directory, f'{name}.npy'), loss.data.detach().float().reshape(1).cpu().numpy())
+    for name in ('D', 'DNN', 'G'):
+        weights = getattr(experiment, name)._srgan_arena.data.detach()
+        if weights.numel() > DUMP_SAMPLE:
+            index = np.sort(np.random.default_rng(0).choice(weights.numel(), DUMP_SAMPLE, replace=False))
+            weights = weights[torch.from_numpy(index).to(weights.device)]
+        np.save(os.path.join(directory, f'{name}_weights.npy'), weights.float().cpu().numpy())
 
 
 def ensure_library():
@@ -652,17 +683,27 @@ def main():
                 restore_weights(live, saved)
     fence()
     elapsed = time.perf_counter() - start
+    # after the timed region: the penalty really was active, and nothing diverged
+    penalty = experiment.loss_value(experiment.last_losses['gradient_penalty'], partial=True)
+    finite = all(bool(torch.isfinite(v.data).all()) for v in experiment.last_losses.values() if v is not None)
+    if gp_scale(args) != 1.0 and not penalty > 0.0:
+        raise SystemExit(f'gradient penalty inactive ({penalty}) at GP scale {gp_scale(args)}: the benchmark would time zeros')
+    if not finite:
+        raise SystemExit('non-finite losses in the last timed step')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(experiment, args.dump_outputs)
     # What the HOST needs to enqueue one iteration (eager: the Python tape and ~4000 launches; replay: input copies + one graph
     # launch): one more iteration issued into an idle device, timed until the last launch call returns -- no queue
     # back-pressure in the number, which is what matters when eight ranks share a 16-CPU quota.  Outside the timed region.
     host_seconds = float('nan')
-    if not os.environ.get('SRGAN_BENCH_NO_HOST_STEP'):      # (the PMC passes count exactly the timed steps: scratch/pmc_summarise.py)
-        enqueue_start = time.perf_counter()
-        one_step(experiment, labeled, unlabeled, args.warmup + args.steps)
-        host_seconds = time.perf_counter() - enqueue_start
-        fence()
-    for live, saved in snapshot:
-        restore_weights(live, saved)
+    if args.full:
+        if not os.environ.get('SRGAN_BENCH_NO_HOST_STEP'):  # (the PMC passes count exactly the timed steps: scratch/pmc_summarise.py)
+            enqueue_start = time.perf_counter()
+            one_step(experiment, labeled, unlabeled, args.warmup + args.steps)
+            host_seconds = time.perf_counter() - enqueue_start
+            fence()
+        for live, saved in snapshot:            # the legs below start from the post-warm-up weights
+            restore_weights(live, saved)
     del snapshot
     per_rank_ms = None
     if dp is not None:
@@ -672,15 +713,8 @@ def main():
         elapsed = dp.all_reduce_max_float(elapsed)
     global_batch = experiment.settings.batch_size
     images_per_second = global_batch * args.steps / elapsed
-    # after the timed region: the penalty really was active, and nothing diverged
-    penalty = experiment.loss_value(experiment.last_losses['gradient_penalty'], partial=True)
-    finite = all(bool(torch.isfinite(v.data).all()) for v in experiment.last_losses.values() if v is not None)
-    if gp_scale(args) != 1.0 and not penalty > 0.0:
-        raise SystemExit(f'gradient penalty inactive ({penalty}) at GP scale {gp_scale(args)}: the benchmark would time zeros')
-    if not finite:
-        raise SystemExit('non-finite losses in the last timed step')
     check = None
-    if side_streams(args) or args.step_graph:
+    if args.full and (side_streams(args) or args.step_graph):
         # ONE comparison against a fixed limit, no second chances: a difference above it is a failure of the schedule.
         check = schedule_check(experiment, labeled, unlabeled, args.warmup + args.steps)
         excess = check['max_relative_loss_difference'] / check['limit']
@@ -723,7 +757,9 @@ def main():
     result['config']['launch'] = (f'HIP graph replay ({captured.replays} replayed, {captured.eager_iterations} eager iterations)'
                                   if captured is not None else 'eager (Python tape enqueues every kernel)')
     result['config']['host_ms_per_step'] = round(1e3 * host_seconds, 3) if host_seconds == host_seconds else None
-    result['config']['schedule_check'] = check if check is not None else 'not applicable: the timed region ran on one stream, eagerly'
+    result['config']['schedule_check'] = check if check is not None else (
+        'not run: the --full option runs it' if side_streams(args) or args.step_graph else
+        'not applicable: the timed region ran on one stream, eagerly')
     if dp is not None:
         import torch.distributed as dist
         if dp.abi is not None:
@@ -744,7 +780,7 @@ def main():
         result['step_tflops_as_written_schedule'] = images_per_second * gflop / 1e3
         result['step_frac_as_written_schedule'] = result['step_tflops_as_written_schedule'] / (FP32_MFMA_PEAK_TFLOPS * world)
 
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         import ctypes
         from srgan_amd import _lib
         lib = _lib.library()
@@ -806,13 +842,13 @@ def main():
                               'achieved': rest_flops / (rest_ms * 1e-3) / 1e12 if rest_ms > 0 else 0.0,
                               'peak': FP32_MFMA_PEAK_TFLOPS},
                 'step_frac_executed': None})
-    if rank == 0 and world == 1 and not args.no_roofline and args.workload == 'crowd':
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and args.workload == 'crowd':
         result['hbm_kernels'] = hbm_kernel_rates(experiment)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'crowd':
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'crowd':
         result['cpu_baseline'] = cpu_baseline(args.image_size, batch=args.cpu_baseline_batch, timed=args.cpu_baseline_timed)
         result['cpu_baseline']['like_for_like'] = committed_cpu_baseline(args.image_size, args.batch_per_gpu,
                                                                          result['cpu_baseline'].get('cpu'))
-    if rank == 0 and world == 1 and dp is None and args.workload == 'crowd' and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and dp is None and args.workload == 'crowd' and not args.no_secondary:
         # the two BASELINE.json configurations that name a precision (configs[1] bf16, configs[4] fp16): same script, child
         # processes, after this process has finished its own GPU work
         torch.cuda.synchronize()

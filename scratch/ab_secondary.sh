@@ -5,8 +5,8 @@ out=gpurun_out/$tag; mkdir -p $out
 for w in age-vgg-bf16 driving-fp16; do
   for v in a b a b; do
     n=$(ls $out | grep -c "^${w}_$v")
-    if [ $v = a ]; then python bench.py --workload $w --steps $steps --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $out/${w}_${v}$n.json
-    else env $assignment python bench.py --workload $w --steps $steps --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $out/${w}_${v}$n.json; fi
+    if [ $v = a ]; then python bench.py --full --workload $w --steps $steps --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $out/${w}_${v}$n.json
+    else env $assignment python bench.py --full --workload $w --steps $steps --warmup 5 --no-secondary --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $out/${w}_${v}$n.json; fi
   done
 done
 python - <<PY

@@ -8,8 +8,8 @@ mkdir -p $out
 line() { grep '^{' | tail -1; }
 run() {  # <name> <cpus or all> <bench arguments...>
   name=$1; cpus=$2; shift 2
-  if [ "$cpus" = all ]; then python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary "$@" 2>/dev/null | line > $out/$name.json
-  else taskset -c $cpus python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary "$@" 2>/dev/null | line > $out/$name.json; fi
+  if [ "$cpus" = all ]; then python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary "$@" 2>/dev/null | line > $out/$name.json
+  else taskset -c $cpus python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary "$@" 2>/dev/null | line > $out/$name.json; fi
 }
 for cpus in all 0,1; do
   c=${cpus/,/_}

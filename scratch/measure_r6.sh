@@ -11,31 +11,31 @@ bash scratch/pmc_one.sh $tag age_vgg64_bf16 64 128 age-vgg-bf16
 bash scratch/pmc_one.sh $tag driving_64x192_fp16 64 128 driving-fp16
 cp profiles/pmc_traffic.json $out/
 
-# 2. bench lines.  The first is the driver's own invocation (defaults; carries `secondary` and `cpu_baseline`)
-python bench.py 2> $out/bench_default.err | line > $out/bench_default.json
-python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --shape-report $out/shape_report.txt 2> $out/bench.err | line > $out/bench.json
+# 2. bench lines, each with --full (the extra legs).  The first is the default invocation (carries `secondary` and `cpu_baseline`)
+python bench.py --full 2> $out/bench_default.err | line > $out/bench_default.json
+python bench.py --full --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --shape-report $out/shape_report.txt 2> $out/bench.err | line > $out/bench.json
 python scratch/shapes.py $out/shape_report.txt > $out/per_kernel_table.md 2>&1
-python bench.py --steps 20 --warmup 5 --single-stream --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_single_stream.json
-python bench.py --steps 20 --warmup 5 --step-graph --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_graph_four_streams.json
-SRGAN_NO_BLOCKED_F32=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_generator_on_nchw_kernels.json
-python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_100_steps.json
-python bench.py --steps 20 --warmup 5 --image-size 224 --no-secondary --shape-report $out/shape_report_224x224.txt 2>/dev/null | line > $out/bench_224x224.json
+python bench.py --full --steps 20 --warmup 5 --single-stream --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_single_stream.json
+python bench.py --full --steps 20 --warmup 5 --step-graph --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_graph_four_streams.json
+SRGAN_NO_BLOCKED_F32=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_generator_on_nchw_kernels.json
+python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_100_steps.json
+python bench.py --full --steps 20 --warmup 5 --image-size 224 --no-secondary --shape-report $out/shape_report_224x224.txt 2>/dev/null | line > $out/bench_224x224.json
 python scratch/shapes.py $out/shape_report_224x224.txt > $out/per_kernel_table_224x224.md 2>&1
-python bench.py --steps 20 --warmup 5 --image-size 224 --single-stream --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_224x224_single_stream.json
-python bench.py --steps 20 --warmup 5 --image-size 224 --step-graph --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_224x224_graph_four_streams.json
-python bench.py --workload age-vgg-bf16 --steps 100 --warmup 5 --shape-report $out/shape_report_age_vgg64_bf16.txt 2>/dev/null | line > $out/bench_age_vgg64_bf16.json
+python bench.py --full --steps 20 --warmup 5 --image-size 224 --single-stream --no-cpu-baseline --no-secondary 2>/dev/null | line > $out/bench_224x224_single_stream.json
+python bench.py --full --steps 20 --warmup 5 --image-size 224 --step-graph --no-cpu-baseline --no-roofline --no-secondary 2>/dev/null | line > $out/bench_224x224_graph_four_streams.json
+python bench.py --full --workload age-vgg-bf16 --steps 100 --warmup 5 --shape-report $out/shape_report_age_vgg64_bf16.txt 2>/dev/null | line > $out/bench_age_vgg64_bf16.json
 python scratch/shapes.py $out/shape_report_age_vgg64_bf16.txt > $out/per_kernel_table_age_vgg64_bf16.md 2>&1
-python bench.py --workload driving-fp16 --steps 100 --warmup 5 --shape-report $out/shape_report_driving_64x192_fp16.txt 2>/dev/null | line > $out/bench_driving_64x192_fp16.json
+python bench.py --full --workload driving-fp16 --steps 100 --warmup 5 --shape-report $out/shape_report_driving_64x192_fp16.txt 2>/dev/null | line > $out/bench_driving_64x192_fp16.json
 python scratch/shapes.py $out/shape_report_driving_64x192_fp16.txt > $out/per_kernel_table_driving_64x192_fp16.md 2>&1
-SRGAN_NO_STORAGE16=1 python bench.py --workload age-vgg-bf16 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $out/bench_age_vgg64_bf16_fp32_storage.json
-SRGAN_NO_STORAGE16=1 python bench.py --workload driving-fp16 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $out/bench_driving_64x192_fp16_fp32_storage.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl 2>/dev/null | line > $out/bench_forced_dp_world1.json
-SRGAN_ABI_COLLECTIVES=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl 2>/dev/null | line > $out/bench_forced_dp_world1_torch_distributed.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --grad-wire bf16 --exchange-form reduce_scatter 2>/dev/null | line > $out/bench_forced_dp_world1_bf16_reduce_scatter.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --step-graph 2>/dev/null | line > $out/bench_forced_dp_world1_graph.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --image-size 224 2>/dev/null | line > $out/bench_224x224_forced_dp_world1.json
-python bench.py --workload driving-fp16 --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --force-dp --backend nccl 2>/dev/null | line > $out/bench_driving_fp16_forced_dp_bf16_reduce_scatter.json
-python bench.py --workload age-vgg-bf16 --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --force-dp --backend nccl 2>/dev/null | line > $out/bench_age_vgg_bf16_forced_dp.json
+SRGAN_NO_STORAGE16=1 python bench.py --full --workload age-vgg-bf16 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $out/bench_age_vgg64_bf16_fp32_storage.json
+SRGAN_NO_STORAGE16=1 python bench.py --full --workload driving-fp16 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | line > $out/bench_driving_64x192_fp16_fp32_storage.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl 2>/dev/null | line > $out/bench_forced_dp_world1.json
+SRGAN_ABI_COLLECTIVES=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl 2>/dev/null | line > $out/bench_forced_dp_world1_torch_distributed.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --grad-wire bf16 --exchange-form reduce_scatter 2>/dev/null | line > $out/bench_forced_dp_world1_bf16_reduce_scatter.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --step-graph 2>/dev/null | line > $out/bench_forced_dp_world1_graph.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --force-dp --backend nccl --image-size 224 2>/dev/null | line > $out/bench_224x224_forced_dp_world1.json
+python bench.py --full --workload driving-fp16 --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --force-dp --backend nccl 2>/dev/null | line > $out/bench_driving_fp16_forced_dp_bf16_reduce_scatter.json
+python bench.py --full --workload age-vgg-bf16 --steps 100 --warmup 5 --no-cpu-baseline --no-roofline --force-dp --backend nccl 2>/dev/null | line > $out/bench_age_vgg_bf16_forced_dp.json
 
 # 3. rocprofv3 kernel statistics of ONE step (3 steps - 1 step, halved), single stream
 bash scratch/stats_one.sh $tag 512

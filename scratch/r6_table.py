@@ -6,7 +6,7 @@ import sys
 tag = sys.argv[1] if len(sys.argv) > 1 else 'r06z'
 root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out', tag)
 rows = [
-    ('bench_default', '`python bench.py` (the driver\'s invocation: defaults, carries `secondary` and `cpu_baseline`)'),
+    ('bench_default', '`python bench.py --full` (defaults with the extra legs: carries `secondary` and `cpu_baseline`)'),
     ('bench', '`--steps 20 --warmup 5` (headline schedule: four streams)'),
     ('bench_generator_on_nchw_kernels', '... `SRGAN_NO_BLOCKED_F32=1` (the generator on the NCHW kernels, as in round 5)'),
     ('bench_single_stream', '`--single-stream`'),

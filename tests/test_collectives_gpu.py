@@ -282,7 +282,18 @@ def test_gradient_exchange_forms_on_the_device(pkg, backend, world):
     workers = [context.Process(target=_exchange_worker, args=(rank, world, port, backend, queue)) for rank in range(world)]
     for worker in workers:
         worker.start()
-    outputs = sorted((queue.get(timeout=600) for _ in workers), key=lambda item: item[0])
+    import queue as queue_module
+    import time
+    deadline = time.monotonic() + 600
+    outputs = []
+    while len(outputs) < len(workers):    # (a worker that died must not hold the suite for the whole time limit)
+        try:
+            outputs.append(queue.get(timeout=5))
+        except queue_module.Empty:
+            dead = [(worker.name, worker.exitcode) for worker in workers if not worker.is_alive() and worker.exitcode != 0]
+            assert not dead or not queue.empty(), f'a rank died: {dead}'
+            assert time.monotonic() < deadline, 'the ranks are still running after ten minutes'
+    outputs.sort(key=lambda item: item[0])
     for worker in workers:
         worker.join(timeout=120)
         assert worker.exitcode == 0
@@ -308,9 +319,9 @@ def test_gradient_exchange_forms_on_the_device(pkg, backend, world):
 
 def test_bench_line_with_bf16_buckets_and_reduce_scatter_over_rccl(pkg):
     """``bench.py --force-dp --backend nccl --grad-wire bf16 --exchange-form reduce_scatter``: the whole timed loop with
-    every gradient arena exchanged as bf16 reduce-scatter + all-gather buckets through RCCL on one rank; the line carries
-    the schedule check (three compute streams under data parallelism against one)."""
-    line = _bench_line('--force-dp', '--backend', 'nccl', '--grad-wire', 'bf16', '--exchange-form', 'reduce_scatter')
+    every gradient arena exchanged as bf16 reduce-scatter + all-gather buckets through RCCL on one rank; with ``--full`` the
+    line carries the schedule check (three compute streams under data parallelism against one)."""
+    line = _bench_line('--full', '--force-dp', '--backend', 'nccl', '--grad-wire', 'bf16', '--exchange-form', 'reduce_scatter')
     config = line['config']
     assert config['gradient_wire'] == 'bf16' and config['gradient_exchange_form'] == 'reduce_scatter'
     assert 'saw 1 ranks' in config['collective_world'] and len(config['per_rank_ms_per_step']) == 1
@@ -319,7 +330,7 @@ def test_bench_line_with_bf16_buckets_and_reduce_scatter_over_rccl(pkg):
     def held(check):      # ONE comparison against the fixed limit (round 5: no repetition, no limit scaled by the schedule's own noise)
         return check['within_limit'] and check['max_relative_loss_difference'] <= check['limit']
     assert held(config['schedule_check']), config['schedule_check']
-    plain = _bench_line()
+    plain = _bench_line('--full')
     assert held(plain['config']['schedule_check']), plain['config']['schedule_check']
     a, b = plain['config']['gradient_penalty_last'], config['gradient_penalty_last']
     assert a > 0 and b > 0 and abs(a - b) <= 0.1 * abs(a), (a, b)     # (two Adam updates from bf16-rounded gradients)
