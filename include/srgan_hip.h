@@ -54,6 +54,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_SPLITK_WORKSPACE 0x2u
 #define SRGAN_FEATURE_LIVE_PROFILE 0x4u
 #define SRGAN_FEATURE_BLOCKED16 0x8u    /* ABI 1.1: the srgan_h_* entry points (16-bit storage in the blocked layout) */
+#define SRGAN_FEATURE_BATCHED_SHADOWS 0x10u /* ABI 1.1, additive: srgan_h_pack_job_matrix / _bias_rows (every shadow kind in
+                                                srgan_h_pack_batched) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -466,6 +468,14 @@ int64_t srgan_h_pack_job_conv_weights(void* jobs, int64_t first_block, const flo
                                       int32_t S, int transposed, int dtype);
 int64_t srgan_h_pack_job_k4s2_weights(void* jobs, int64_t first_block, const float* w, void* packed, int32_t A, int32_t B,
                                       int direction, int dtype, int32_t* jobs_written);
+/* The matrix shadows and the bias rows as jobs of the same launch (SRGAN_FEATURE_BATCHED_SHADOWS): srgan_h_pack_job_matrix
+ * takes the arguments of srgan_h_pack_matrix (every extent and stride below 2^31) and writes one job; srgan_h_pack_job_bias_rows
+ * writes the fp32 rows[(g * plane + p) * 8 + j] = bias[8 g + j] (0 from `channels` on; ceil(channels / 8) * plane * 8 floats) of a
+ * seed transposed convolution (a linear map onto [channels][plane]). */
+int64_t srgan_h_pack_job_matrix(void* jobs, int64_t first_block, const float* src, void* out, int64_t rows, int64_t cols,
+                                int64_t rows_real, int64_t cols_real, int64_t row_stride, int64_t col_stride, int32_t row_plane,
+                                int32_t col_plane, int dtype);
+int64_t srgan_h_pack_job_bias_rows(void* jobs, int64_t first_block, const float* bias, float* rows, int32_t channels, int32_t plane);
 int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks, void* stream);
 int srgan_h_conv4x4s2(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
                       int32_t N, int32_t C_in, int32_t rows, int32_t H, int32_t W, int dtype, void* stream);

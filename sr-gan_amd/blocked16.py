@@ -193,12 +193,26 @@ def _pool_gather(x_data, meta, s):
 
 
 # ------------------------------------------------------------------------------------------------ weight shadows
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _refuse_under_capture(what):
+    """A HIP-graph capture records launches only: an allocation would come from the graph's pool and a host-to-device copy is
+    illegal, so whatever needs one must exist before the capture (``prepare``)."""
+    if _capturing():
+        raise RuntimeError(f'blocked16: {what} during a HIP graph capture; call blocked16.prepare(arena) for every network '
+                           'of the step (and run the step once eagerly) before capturing it')
+
+
 class Shadow:
     """The 16-bit operand forms of one layer's fp32 master weights: ``forward`` (rows = outputs) and ``transposed`` (the
     data gradient's operand), re-rounded whenever the masters changed -- by ``refresh(arena)`` right behind the optimizer
-    update (same stream as the update), or lazily when the version key below moved (checkpoint load, tests)."""
+    update (same stream as the update), or lazily when the version key below moved (checkpoint load, tests).  Every buffer
+    (the ``linear_t`` bias rows included) is allocated once and then written in place, so a refresh can be captured."""
 
     def __init__(self, module, kind, code, in_blocked=0, plane=1):
+        _refuse_under_capture(f'a new {kind} weight shadow')
         self.module, self.kind, self.code, self.in_blocked, self.plane = module, kind, code, in_blocked, plane
         self.forward = self.transposed = self.down = self.up = self.bias_rows = None
         self.key = None
@@ -210,14 +224,41 @@ class Shadow:
         if self.key != self._version():
             # the lazy path (first use, checkpoint load, a test that edited the weights): other streams may launch readers of
             # this shadow right away -- they are only ordered behind whatever wrote the masters, not behind this repack
+            _refuse_under_capture(f'a {self.kind} weight shadow behind its masters')
             self.repack()
-            if not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream().synchronize()
+            torch.cuda.current_stream().synchronize()
         return self
+
+    def matrix_forms(self):
+        """The matrix shadows of a ``linear`` / ``linear_t`` layer: (buffer name, 16-byte slots, the (rows, cols, rows_real,
+        cols_real, row_stride, col_stride, row_plane, col_plane) of ``srgan_h_pack_matrix``)."""
+        weight = self.module.weight
+        if self.kind == 'linear':
+            outputs, inputs = weight.shape[0], weight.numel() // weight.shape[0]
+            blocked = self.in_blocked or (inputs + 7) // 8 * 8
+            outputs_padded = (outputs + 7) // 8 * 8
+            # forward operand A[o][f'] = W[o][map(f')]; transposed operand A[f'][o] = W[o][map(f')]
+            return (('forward', outputs * blocked // 8, (outputs, blocked, outputs, inputs, inputs, 1, 1, self.plane)),
+                    ('transposed', blocked * outputs_padded // 8, (blocked, outputs_padded, inputs, outputs, 1, inputs, self.plane, 1)))
+        # 'linear_t': conv_transpose2d weights [Cin][Cout][R][S] applied to a 1 x 1 input: a linear map Cin -> (Cout, R x S); its
+        # outputs in the blocked order of a [Cout, R, S] tensor (plane = R * S)
+        c_in, c_out = weight.shape[0], weight.shape[1]
+        plane = weight.shape[2] * weight.shape[3]
+        blocked, c_in_padded = (c_out + 7) // 8 * 8 * plane, (c_in + 7) // 8 * 8
+        return (('forward', blocked * c_in_padded // 8, (blocked, c_in_padded, c_out * plane, c_in, 1, c_out * plane, plane, 1)),
+                ('transposed', c_in * blocked // 8, (c_in, blocked, c_in, c_out * plane, c_out * plane, 1, 1, plane)))
+
+    def bias_rows_form(self):
+        """``linear_t`` with a bias: (channels, plane) of its fp32 bias rows -- bias[co] of every output row (co, pixel) in the
+        blocked order, ceil(channels / 8) * plane * 8 floats -- else None."""
+        if self.kind != 'linear_t' or self.module.bias is None:
+            return None
+        weight = self.module.weight
+        return weight.shape[1], weight.shape[2] * weight.shape[3]
 
     def repack(self):
         weight = self.module.weight
-        lib, stream, device = _lib.library(), F._stream(), weight.device
+        lib, stream = _lib.library(), F._stream()
 
         buffer = self._buffer
         if self.kind == 'conv3x3':
@@ -225,44 +266,35 @@ class Shadow:
             for name, transposed, rows, reduced in (('forward', 0, k, c), ('transposed', 1, c, k)):
                 _call('srgan_h_pack_conv_weights', weight.data_ptr(), buffer(name, lib.srgan_h_conv_weight_slots(rows, reduced, r, s)),
                       k, c, r, s, transposed, self.code, stream)
-        elif self.kind == 'linear':
-            outputs, inputs = weight.shape[0], weight.numel() // weight.shape[0]
-            blocked = self.in_blocked or (inputs + 7) // 8 * 8
-            outputs_padded = (outputs + 7) // 8 * 8
-            # forward operand A[o][f'] = W[o][map(f')]; transposed operand A[f'][o] = W[o][map(f')]
-            _call('srgan_h_pack_matrix', weight.data_ptr(), buffer('forward', outputs * blocked // 8), outputs, blocked, outputs, inputs,
-                  inputs, 1, 1, self.plane, self.code, stream)
-            _call('srgan_h_pack_matrix', weight.data_ptr(), buffer('transposed', blocked * outputs_padded // 8), blocked, outputs_padded,
-                  inputs, outputs, 1, inputs, self.plane, 1, self.code, stream)
+        elif self.kind in ('linear', 'linear_t'):
+            for name, slots, arguments in self.matrix_forms():
+                _call('srgan_h_pack_matrix', weight.data_ptr(), buffer(name, slots), *arguments, self.code, stream)
+            form = self.bias_rows_form()
+            if form is not None:                  # (a copy, no arithmetic: written in place, the buffer keeps its address)
+                channels, plane = form
+                full = channels // 8
+                self._buffer('bias_rows', (channels + 7) // 8 * plane * 2, torch.float32)
+                rows, bias = self.bias_rows.view(-1, plane, 8), self.module.bias.data
+                if full:
+                    rows[:full].copy_(bias[:full * 8].view(full, 1, 8).expand(full, plane, 8))
+                if channels % 8:
+                    rows[full].zero_()
+                    rows[full, :, :channels % 8].copy_(bias[full * 8:].view(1, -1).expand(plane, channels % 8))
         elif self.kind == 'k4s2':
             # [A][B][4][4], A = the channels on the small plane: conv2d weights [K][C], conv_transpose2d weights [Cin][Cout]
             a, b = weight.shape[0], weight.shape[1]
             for name, direction in (('down', 0), ('up', 1)):
                 _call('srgan_h_pack_k4s2_weights', weight.data_ptr(), buffer(name, lib.srgan_h_k4s2_weight_slots(a, b, direction, self.code)),
                       a, b, direction, self.code, stream)
-        elif self.kind == 'linear_t':
-            # conv_transpose2d weights [Cin][Cout][R][S] applied to a 1 x 1 input: a linear map Cin -> (Cout, R x S); its outputs
-            # in the blocked order of a [Cout, R, S] tensor (plane = R * S)
-            c_in, c_out = weight.shape[0], weight.shape[1]
-            plane = weight.shape[2] * weight.shape[3]
-            blocked, c_in_padded = (c_out + 7) // 8 * 8 * plane, (c_in + 7) // 8 * 8
-            _call('srgan_h_pack_matrix', weight.data_ptr(), buffer('forward', blocked * c_in_padded // 8), blocked, c_in_padded,
-                  c_out * plane, c_in, 1, c_out * plane, plane, 1, self.code, stream)
-            _call('srgan_h_pack_matrix', weight.data_ptr(), buffer('transposed', c_in * blocked // 8), c_in, blocked, c_in,
-                  c_out * plane, c_out * plane, 1, 1, plane, self.code, stream)
-            if self.module.bias is not None:       # bias[co] of every output row (co, pixel), in the blocked order (a copy, no arithmetic)
-                groups = (c_out + 7) // 8
-                padded = torch.zeros(groups * 8, dtype=torch.float32, device=device)
-                padded[:c_out] = self.module.bias.data
-                self.bias_rows = padded.view(groups, 1, 8).expand(groups, plane, 8).reshape(-1).contiguous()
         else:
             raise ValueError(self.kind)
         self.key = self._version()
 
-    def _buffer(self, name, slots):
+    def _buffer(self, name, slots, dtype=torch.int32):
         """The device buffer of one operand form (``slots`` 16-byte slots), allocated on first use and then kept."""
         if getattr(self, name, None) is None:
-            setattr(self, name, torch.empty(slots * 4, dtype=torch.int32, device=self.module.weight.device))
+            _refuse_under_capture(f'the first {name} buffer of a {self.kind} weight shadow')
+            setattr(self, name, torch.empty(slots * 4, dtype=dtype, device=self.module.weight.device))
         return getattr(self, name).data_ptr()
 
     def _version(self):
@@ -283,16 +315,17 @@ def shadow_of(module, kind, code, in_blocked=0, plane=1):
 
 
 class _PackPlan:
-    """The convolution shadows of one arena as ONE launch (``srgan_h_pack_batched``): a device array of jobs, built once from
-    the arguments the single-layer packers would get -- the masters live at fixed arena addresses and a shadow keeps its
-    buffers, so the table stays valid until the set of shadows changes."""
+    """Every shadow of one arena as ONE launch (``srgan_h_pack_batched``): a device array of jobs, built once from the
+    arguments the single-layer packers would get -- the masters live at fixed arena addresses and a shadow keeps its
+    buffers, so the table stays valid until the set of shadows changes (and a replayed refresh writes the same addresses)."""
 
     def __init__(self, shadows):
         import ctypes
+        _refuse_under_capture('building the batched shadow refresh')
         lib = _lib.library()
         size = lib.srgan_h_pack_job_bytes()
         self.shadows = list(shadows)
-        self.signature = tuple((id(s), s.module.weight.data_ptr()) for s in self.shadows)
+        self.signature = _signature(self.shadows)
         host = ctypes.create_string_buffer(size * 5 * max(1, len(self.shadows)))
         count = blocks = 0
         written = ctypes.c_int32()
@@ -308,7 +341,7 @@ class _PackPlan:
                                                               k, c, r, s, transposed, shadow.code)
                     _lib.check(min(taken, 0), 'srgan_h_pack_job_conv_weights')
                     count, blocks = count + 1, blocks + taken
-            else:                                           # 'k4s2'
+            elif shadow.kind == 'k4s2':
                 a, b = weight.shape[0], weight.shape[1]
                 for name, direction in (('down', 0), ('up', 1)):
                     target = shadow._buffer(name, lib.srgan_h_k4s2_weight_slots(a, b, direction, shadow.code))
@@ -316,6 +349,21 @@ class _PackPlan:
                                                               a, b, direction, shadow.code, ctypes.byref(written))
                     _lib.check(min(taken, 0), 'srgan_h_pack_job_k4s2_weights')
                     count, blocks = count + written.value, blocks + taken
+            else:                                           # 'linear', 'linear_t'
+                for name, slots, arguments in shadow.matrix_forms():
+                    target = shadow._buffer(name, slots)
+                    taken = lib.srgan_h_pack_job_matrix(ctypes.byref(host, count * size), blocks, weight.data_ptr(), target,
+                                                        *arguments, shadow.code)
+                    _lib.check(min(taken, 0), 'srgan_h_pack_job_matrix')
+                    count, blocks = count + 1, blocks + taken
+                form = shadow.bias_rows_form()
+                if form is not None:
+                    channels, plane = form
+                    target = shadow._buffer('bias_rows', (channels + 7) // 8 * plane * 2, torch.float32)
+                    taken = lib.srgan_h_pack_job_bias_rows(ctypes.byref(host, count * size), blocks, shadow.module.bias.data_ptr(),
+                                                           target, channels, plane)
+                    _lib.check(min(taken, 0), 'srgan_h_pack_job_bias_rows')
+                    count, blocks = count + 1, blocks + taken
         self.count, self.blocks = count, blocks
         self.table = None
         if count:
@@ -328,29 +376,65 @@ class _PackPlan:
             shadow.key = shadow._version()
 
 
-BATCHED_KINDS = ('conv3x3', 'k4s2')
+# the shadow kinds of the batched refresh: all of them (the matrix shadows and the seed layer's bias rows since ABI 1.1's
+# SRGAN_FEATURE_BATCHED_SHADOWS)
+BATCHED_KINDS = ('conv3x3', 'k4s2', 'linear', 'linear_t')
+
+
+def _signature(shadows):
+    return tuple((id(s), s.module.weight.data_ptr(), None if s.module.bias is None else s.module.bias.data_ptr()) for s in shadows)
+
+
+def _plan(arena):
+    """The arena's batched refresh, (re)built when its set of shadows changed."""
+    plan = getattr(arena, '_pack_plan', None)
+    if plan is None or plan.signature != _signature(arena.shadows):
+        plan = arena._pack_plan = _PackPlan(arena.shadows)
+    return plan
 
 
 def refresh(arena):
     """Re-round every shadow of the networks' weights in ``arena`` (called right behind the optimizer update, on its stream:
-    whatever orders a later reader behind the update orders it behind the shadows too).  The convolution shadows go as one
-    batched launch, the few matrix shadows (linear layers) one by one."""
+    whatever orders a later reader behind the update orders it behind the shadows too) as ONE batched launch that writes only
+    fixed addresses (``SRGAN_H_NO_BATCHED_PACK=1``: the single-layer packers, one launch per operand)."""
     shadows = getattr(arena, 'shadows', ())
     if not shadows:
         return
-    batched = [s for s in shadows if s.kind in BATCHED_KINDS]
-    plan = getattr(arena, '_pack_plan', None)
-    if batched and os.environ.get('SRGAN_H_NO_BATCHED_PACK') != '1':
-        signature = tuple((id(s), s.module.weight.data_ptr()) for s in batched)
-        if plan is None or plan.signature != signature:
-            plan = arena._pack_plan = _PackPlan(batched)
+    if os.environ.get('SRGAN_H_NO_BATCHED_PACK') == '1':
+        for shadow in shadows:
+            shadow.repack()
+        return
+    _plan(arena).run()
+
+
+def stale(arena):
+    """True when a master of ``arena`` was written behind its shadows' back (a version key moved: checkpoint load, a copy
+    into ``arena.data``, a test editing the weights).  Host-side only: no launch, no synchronisation."""
+    return any(shadow.key != shadow._version() for shadow in getattr(arena, 'shadows', ()))
+
+
+def refresh_if_stale(arena):
+    """``refresh(arena)`` on the current stream when ``stale(arena)``; returns whether it re-rounded."""
+    if not stale(arena):
+        return False
+    refresh(arena)
+    return True
+
+
+def prepare(arena):
+    """Make the shadows of ``arena`` capture-ready: every buffer (bias rows included) and the batched refresh's device job
+    table exist, and the shadows are current.  Call it for every network of a step before capturing the step: inside the
+    capture nothing may allocate or copy from the host, and the Adam -> refresh pair it records then only rewrites fixed
+    addresses.  (A shadow that the step would create for the first time still raises there: run the step eagerly first.)"""
+    _refuse_under_capture('blocked16.prepare')
+    if not getattr(arena, 'shadows', ()):
+        return
+    if os.environ.get('SRGAN_H_NO_BATCHED_PACK') == '1':
+        refresh(arena)                                  # the single-layer packers allocate what is missing
+        return
+    plan = _plan(arena)
+    if stale(arena):
         plan.run()
-    else:
-        for shadow in batched:
-            shadow.repack()
-    for shadow in shadows:
-        if shadow.kind not in BATCHED_KINDS:
-            shadow.repack()
 
 
 # ------------------------------------------------------------------------------------------------ fused layers

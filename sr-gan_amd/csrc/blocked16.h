@@ -191,11 +191,82 @@ __device__ __forceinline__ void h_pack_k4s2_weights_slot(const float* __restrict
   packed[slot] = h_pack<PREC>(v);
 }
 
+// index of element i' of a flattened BLOCKED plane tensor ([C / 8][P][8]) in the flattened NCHW order ([C][P])
+__host__ __device__ __forceinline__ int64_t h_plane_index(int64_t i, int32_t plane) {
+  if (plane <= 1) return i;
+  const int64_t slot = i >> 3;
+  return ((slot / plane) * 8 + (i & 7)) * plane + slot % plane;
+}
+
+// The matrix shadows (linear layers, blocked16_gemm.hip).  out16[r][c] (row_slots slots per row) = src[map(r, row_plane) * rs +
+// map(c, col_plane) * cs] for map(r) < rows_real, map(c) < cols_real, else 0.  One thread per slot of 8 consecutive c.
+template <int PREC>
+__device__ __forceinline__ void h_pack_matrix_slot(const float* __restrict__ src, Slot* __restrict__ out, int64_t slot,
+                                                   int32_t row_slots, int64_t rows_real, int64_t cols_real, int64_t rs, int64_t cs,
+                                                   int32_t row_plane, int32_t col_plane) {
+  const int64_t r = slot / row_slots;
+  const int64_t c0 = (slot % row_slots) * 8;
+  const int64_t rr = h_plane_index(r, row_plane);
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int64_t cc = h_plane_index(c0 + j, col_plane);
+    v[j] = (rr < rows_real && cc < cols_real) ? src[rr * rs + cc * cs] : 0.f;
+  }
+  out[slot] = h_pack8<PREC>(v);
+}
+
+// The same for rs == 1 (the TRANSPOSED shadow of a row-major matrix): one 64 x 64 tile (`tile_index`, row tiles fastest) of a
+// WHOLE workgroup through LDS, so that both the fp32 reads (along r) and the 16-byte slot stores (along c) are coalesced.  The
+// row pitch of 65 floats puts the 64 lanes of a column write (tile[c][r_load], r_load = lane) and of a row read (tile[8 s + j][r])
+// on different banks.  Every thread of the workgroup must call it (one barrier).
+template <int PREC>
+__device__ __forceinline__ void h_pack_matrix_tile(const float* __restrict__ src, Slot* __restrict__ out, float (*tile)[65],
+                                                   int tile_index, int64_t rows, int32_t row_slots, int64_t rows_real,
+                                                   int64_t cols_real, int64_t cs, int32_t row_plane, int32_t col_plane,
+                                                   int32_t tiles_r) {
+  const int tid = (int)threadIdx.x;
+  const int64_t r0 = (int64_t)(tile_index % tiles_r) * 64, c0 = (int64_t)(tile_index / tiles_r) * 64;
+  const int r_load = tid & 63;
+  const int64_t rr = h_plane_index(r0 + r_load, row_plane);
+  const bool row_ok = r0 + r_load < rows && rr < rows_real;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c_local = (tid >> 6) + 4 * i;
+    const int64_t cc = h_plane_index(c0 + c_local, col_plane);
+    tile[c_local][r_load] = (row_ok && c0 + c_local < (int64_t)row_slots * 8 && cc < cols_real) ? src[cc * cs + rr] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int slot_local = tid & 7, r_local = (tid >> 3) + 32 * i;
+    if (r0 + r_local >= rows || c0 / 8 + slot_local >= row_slots) continue;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = tile[slot_local * 8 + j][r_local];
+    out[(r0 + r_local) * row_slots + c0 / 8 + slot_local] = h_pack8<PREC>(v);
+  }
+}
+
+// The bias rows of a seed transposed convolution (a linear map onto [Cout][plane], blocked16.py "linear_t"): fp32
+// rows[(g * plane + p) * 8 + j] = bias[8 g + j] (0 from `channels` on) -- one thread = the 8 values of one (g, p); a copy.
+__device__ __forceinline__ void h_bias_rows_slot(const float* __restrict__ bias, float* __restrict__ rows, int64_t slot,
+                                                 int32_t channels, int32_t plane) {
+  const int g = (int)(slot / plane);
+  float4 v[2];
+  float* f = reinterpret_cast<float*>(v);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = g * 8 + j < channels ? bias[g * 8 + j] : 0.f;
+  reinterpret_cast<float4*>(rows + slot * 8)[0] = v[0];
+  reinterpret_cast<float4*>(rows + slot * 8)[1] = v[1];
+}
+
 // one problem of the batched launch (80 bytes, filled on the host by srgan_h_pack_job_*)
 struct HPackJob {
-  const float* w; Slot* packed;
+  const float* w; Slot* packed;     // kind 4: packed = the fp32 bias rows
   int64_t slots, first_block;       // this job's workgroups are [first_block, first_block + ceil(slots / 256))
-  int32_t kind, prec;               // kind 0: conv weights, 1: 4x4 / stride 2 weights; prec = dtype
+  int32_t kind, prec;               // kind 0: conv weights, 1: 4x4 / stride 2 weights, 2: matrix, 3: transposed matrix (one
+                                    // 64 x 64 tile per workgroup, slots = 256 x tiles), 4: bias rows; prec = dtype
   int32_t p[10];                    // the body's integer arguments, in its order
 };
 

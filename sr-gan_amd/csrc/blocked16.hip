@@ -240,10 +240,14 @@ __global__ __launch_bounds__(256) void h_pack_conv_weights_kernel(const float* _
   h_pack_conv_weights_slot<PREC>(w, packed, slot, CO, CI, R, S, base, so, si, skh, skw);
 }
 
-// Every convolution shadow of one network in ONE launch: a workgroup finds its job by bisection over the jobs' first blocks
+// Every weight shadow of one network in ONE launch: a workgroup finds its job by bisection over the jobs' first blocks
 // (wave-uniform), then runs that job's body.  A step of the driving configuration re-rounds 80 operands, of the VGG
-// configuration 52: as single launches they were 0.45 / 0.34 ms of 5 us kernels with the launch gaps on top.
+// configuration 52: as single launches they were 0.45 / 0.34 ms of 5 us kernels with the launch gaps on top.  The matrix shadows
+// (linear layers) and the seed layer's bias rows are jobs too, so a refresh writes only fixed addresses and can be captured in a
+// HIP graph.  The transposed-matrix body stages a 64 x 65 fp32 tile in LDS (16.6 KB per workgroup for every job kind: eight
+// 256-thread workgroups per CU, the wave limit, still fit in the 160 KB of a gfx950 CU).
 __global__ __launch_bounds__(256) void h_pack_batched_kernel(const HPackJob* __restrict__ jobs, int32_t count) {
+  __shared__ float tile[64][65];
   int lo = 0, hi = count - 1;
   const int64_t block = blockIdx.x;
   while (lo < hi) {
@@ -257,10 +261,19 @@ __global__ __launch_bounds__(256) void h_pack_batched_kernel(const HPackJob* __r
   if (job.kind == 0) {
     if (job.prec == 1) h_pack_conv_weights_slot<1>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
     else h_pack_conv_weights_slot<2>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
-  } else {
+  } else if (job.kind == 1) {
     if (job.prec == 0) h_pack_k4s2_weights_slot<0>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4]);
     else if (job.prec == 1) h_pack_k4s2_weights_slot<1>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4]);
     else h_pack_k4s2_weights_slot<2>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4]);
+  } else if (job.kind == 2) {
+    if (job.prec == 1) h_pack_matrix_slot<1>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+    else h_pack_matrix_slot<2>(job.w, job.packed, slot, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+  } else if (job.kind == 3) {       // the whole workgroup (slots = 256 x tiles: no thread returned above)
+    const int tile_index = (int)(block - job.first_block);
+    if (job.prec == 1) h_pack_matrix_tile<1>(job.w, job.packed, tile, tile_index, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
+    else h_pack_matrix_tile<2>(job.w, job.packed, tile, tile_index, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
+  } else {
+    h_bias_rows_slot(job.w, reinterpret_cast<float*>(job.packed), slot, q[0], q[1]);
   }
 }
 
@@ -1134,6 +1147,50 @@ int64_t srgan_h_pack_job_k4s2_weights(void* jobs, int64_t first_block, const flo
   }
   *jobs_written = count;
   return count * blocks;
+}
+
+// The matrix shadow srgan_h_pack_matrix (blocked16_gemm.hip) would write, as one job: the tile-transposing body where that
+// function launches its transposed kernel (row_stride == 1, col_stride != 1), else the one-thread-per-slot body.  The job keeps
+// its integers in 32 bits: every extent and stride must be below 2^31.
+int64_t srgan_h_pack_job_matrix(void* jobs, int64_t first_block, const float* src, void* out, int64_t rows, int64_t cols,
+                                int64_t rows_real, int64_t cols_real, int64_t row_stride, int64_t col_stride, int32_t row_plane,
+                                int32_t col_plane, int dtype) {
+  if (const int status = check_dtype(dtype)) return status;
+  const int64_t limit = (int64_t)1 << 31;
+  SRGAN_REQUIRE(jobs && first_block >= 0 && src && out && rows > 0 && cols > 0 && rows < limit && cols < limit && rows_real >= 0 &&
+                rows_real < limit && cols_real >= 0 && cols_real < limit && row_stride > 0 && row_stride < limit && col_stride > 0 &&
+                col_stride < limit && row_plane >= 0 && col_plane >= 0, SRGAN_EINVAL, "srgan_h_pack_job_matrix arguments");
+  const int64_t row_slots = (cols + 7) / 8;
+  HPackJob job;
+  memset(&job, 0, sizeof(job));
+  job.w = src; job.packed = (Slot*)out; job.first_block = first_block; job.prec = dtype;
+  if (row_stride == 1 && col_stride != 1) {
+    const int64_t tiles_r = (rows + 63) / 64, tiles = tiles_r * ((row_slots * 8 + 63) / 64);
+    SRGAN_REQUIRE(tiles < limit / 256, SRGAN_EINVAL, "srgan_h_pack_job_matrix size");
+    job.kind = 3; job.slots = tiles * 256;
+    job.p[0] = (int32_t)rows; job.p[1] = (int32_t)row_slots; job.p[2] = (int32_t)rows_real; job.p[3] = (int32_t)cols_real;
+    job.p[4] = (int32_t)col_stride; job.p[5] = row_plane; job.p[6] = col_plane; job.p[7] = (int32_t)tiles_r;
+  } else {
+    job.kind = 2; job.slots = rows * row_slots;
+    job.p[0] = (int32_t)row_slots; job.p[1] = (int32_t)rows_real; job.p[2] = (int32_t)cols_real; job.p[3] = (int32_t)row_stride;
+    job.p[4] = (int32_t)col_stride; job.p[5] = row_plane; job.p[6] = col_plane;
+  }
+  memcpy(jobs, &job, sizeof(job));
+  return (job.slots + 255) / 256;
+}
+
+// fp32 rows[ceil(channels / 8) * plane * 8]: rows[(g * plane + p) * 8 + j] = bias[8 g + j], 0 from `channels` on (the bias of every
+// output row of a seed transposed convolution in the blocked order)
+int64_t srgan_h_pack_job_bias_rows(void* jobs, int64_t first_block, const float* bias, float* rows, int32_t channels, int32_t plane) {
+  SRGAN_REQUIRE(jobs && first_block >= 0 && bias && rows && channels > 0 && plane > 0 &&
+                (int64_t)(channels + 7) / 8 * plane < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_pack_job_bias_rows arguments");
+  HPackJob job;
+  memset(&job, 0, sizeof(job));
+  job.w = bias; job.packed = (Slot*)rows; job.first_block = first_block; job.kind = 4; job.prec = 0;
+  job.slots = (int64_t)(channels + 7) / 8 * plane;
+  job.p[0] = channels; job.p[1] = plane;
+  memcpy(jobs, &job, sizeof(job));
+  return (job.slots + 255) / 256;
 }
 
 int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks, hipStream_t stream) {

@@ -14,64 +14,29 @@
 
 namespace srgan {
 
-// index of element i' of a flattened BLOCKED plane tensor ([C / 8][P][8]) in the flattened NCHW order ([C][P])
-__host__ __device__ __forceinline__ int64_t h_plane_index(int64_t i, int32_t plane) {
-  if (plane <= 1) return i;
-  const int64_t slot = i >> 3;
-  return ((slot / plane) * 8 + (i & 7)) * plane + slot % plane;
-}
-
 // out16[r][c] (pitch ld elements, ld % 8 == 0) = src[map(r, row_plane) * rs + map(c, col_plane) * cs] for map(r) < rows_real,
-// map(c) < cols_real, else 0.  One thread per slot of 8 consecutive c.
+// map(c) < cols_real, else 0.  One thread per slot of 8 consecutive c (body: h_pack_matrix_slot, blocked16.h).
 template <int PREC>
 __global__ __launch_bounds__(256) void h_pack_matrix_kernel(const float* __restrict__ src, Slot* __restrict__ out, int64_t slots,
                                                             int32_t row_slots, int64_t rows_real, int64_t cols_real, int64_t rs,
                                                             int64_t cs, int32_t row_plane, int32_t col_plane) {
   const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (slot >= slots) return;
-  const int64_t r = slot / row_slots;
-  const int64_t c0 = (slot % row_slots) * 8;
-  const int64_t rr = h_plane_index(r, row_plane);
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int64_t cc = h_plane_index(c0 + j, col_plane);
-    v[j] = (rr < rows_real && cc < cols_real) ? src[rr * rs + cc * cs] : 0.f;
-  }
-  out[slot] = h_pack8<PREC>(v);
+  h_pack_matrix_slot<PREC>(src, out, slot, row_slots, rows_real, cols_real, rs, cs, row_plane, col_plane);
 }
 
 // The same for row_stride == 1 (the TRANSPOSED shadow of a row-major matrix: consecutive output rows are consecutive source
 // addresses): a 64 x 64 tile goes through LDS, so both the fp32 reads (along r) and the 16-byte slot stores (along c) are
 // coalesced -- the one-thread-per-slot kernel read eight floats a row pitch apart and fetched every line seven times
-// (4.1 GB per step for VGG-16's two large linear layers, PMC profiles/r06f).
+// (4.1 GB per step for VGG-16's two large linear layers, PMC profiles/r06f).  Body: h_pack_matrix_tile (blocked16.h), shared with
+// the batched refresh (h_pack_batched_kernel).
 template <int PREC>
 __global__ __launch_bounds__(256) void h_pack_matrix_transposed_kernel(const float* __restrict__ src, Slot* __restrict__ out,
                                                                        int64_t rows, int32_t row_slots, int64_t rows_real,
                                                                        int64_t cols_real, int64_t cs, int32_t row_plane,
                                                                        int32_t col_plane, int32_t tiles_r) {
   __shared__ float tile[64][65];
-  const int tid = (int)threadIdx.x;
-  const int64_t r0 = (int64_t)((int)blockIdx.x % tiles_r) * 64, c0 = (int64_t)((int)blockIdx.x / tiles_r) * 64;
-  const int r_load = tid & 63;
-  const int64_t rr = h_plane_index(r0 + r_load, row_plane);
-  const bool row_ok = r0 + r_load < rows && rr < rows_real;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c_local = (tid >> 6) + 4 * i;
-    const int64_t cc = h_plane_index(c0 + c_local, col_plane);
-    tile[c_local][r_load] = (row_ok && c0 + c_local < (int64_t)row_slots * 8 && cc < cols_real) ? src[cc * cs + rr] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int slot_local = tid & 7, r_local = (tid >> 3) + 32 * i;
-    if (r0 + r_local >= rows || c0 / 8 + slot_local >= row_slots) continue;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = tile[slot_local * 8 + j][r_local];
-    out[(r0 + r_local) * row_slots + c0 / 8 + slot_local] = h_pack8<PREC>(v);
-  }
+  h_pack_matrix_tile<PREC>(src, out, tile, (int)blockIdx.x, rows, row_slots, rows_real, cols_real, cs, row_plane, col_plane, tiles_r);
 }
 
 struct HGemmParams {

@@ -1505,7 +1505,8 @@ int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
   out->dtypes = 0x1u /* fp32 */ | 0x2u /* bf16 MFMA operands */ | 0x4u /* fp16 MFMA operands */;
   out->features = 0x1u /* fused batch-norm + relu prologues / epilogues */ | 0x2u /* split-K through a workspace */ |
                   0x4u /* live event profile of the contraction launches */ |
-                  0x8u /* 16-bit blocked data path (srgan_h_*) */;
+                  0x8u /* 16-bit blocked data path (srgan_h_*) */ |
+                  0x10u /* every weight-shadow kind as a job of srgan_h_pack_batched */;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;

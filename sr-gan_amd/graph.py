@@ -18,8 +18,15 @@ The side streams of the eager schedule (``settings.overlap_dnn_step`` / ``overla
 the joins at the end of the step close it, and the instantiated graph holds the four chains as parallel branches -- they start
 together on replay instead of in the order Python reaches them.
 
+The 16-bit data path (``settings.storage_dtype``, round 7) replays too, on a single device.  Its weight shadows (blocked16.py)
+are written in place by ONE batched launch per network behind each update, so the captured Adam -> refresh pairs keep them
+current from replay to replay; ``blocked16.prepare`` makes every shadow buffer and job table exist before a capture (inside it
+nothing may allocate or copy from the host), and masters written between two replays are caught by the shadows' host-side
+version keys and re-rounded in front of the next replay.
+
 Iterations whose host-side behaviour differs run eagerly: summary steps (they read losses back), and a graph is keyed
-by everything the captured launches baked in (input shapes, whether the generator trains this step, learning rates).
+by everything the captured launches baked in (input shapes, whether the generator trains this step, learning rates, the
+storage type and the loss scale).
 Data-parallel runs (round 5): the exchanges are captured too when they are launches on streams this process owns -- the C
 ABI's RCCL entry points on the communicator's stream (``parallel.AbiCommunicator``; forked into the capture by the event
 wait in front of a collective, joined by the ``wait()`` of its work object) -- so that eight Python ranks on a 16-CPU
@@ -27,6 +34,8 @@ quota replay instead of enqueueing ~4000 launches each; every captured iteration
 applied (the generator's exchange, which the eager loop hides under the next iteration's DNN step, completes inside the
 graph).  Over gloo (host collectives) a data-parallel run stays eager.
 """
+import gc
+
 import torch
 
 from . import functional as F
@@ -104,8 +113,10 @@ class CapturedIteration:
             return self.eager(*inputs, step)
         flat = _flatten(inputs, [])
         generator_phase = step % settings.generator_training_step_period == 0
+        # (the 16-bit path bakes its storage type into every launch and the static loss scale into the scaled backward)
         key = (tuple(tuple(v.shape) for v in flat), generator_phase, F.COMPUTE_DTYPE,
-               tuple(o.param_groups[0]['lr'] for o in self.optimizers()))
+               tuple(o.param_groups[0]['lr'] for o in self.optimizers()), getattr(settings, 'storage_dtype', None),
+               float(getattr(settings, 'loss_scale', 1.0)))
         batch = inputs[2].shape[0]
         # host draws of THIS iteration, in the order the eager step makes them (srgan.py:286, :364, :301)
         # (a draw injected by a test is used once, exactly as the eager step would use it)
@@ -117,6 +128,11 @@ class CapturedIteration:
         if generator_phase:
             host['z_g'] = drawn('z_g', lambda: e.draw_generator_noise(batch))
         record = self.records.get(key)
+        if record is not None and record['shadows'] != self.shadow_counts():
+            # a weight shadow appeared since this capture (an eager summary step, a new phase): the captured refreshes do not
+            # cover it, so the graph is captured again
+            del self.records[key]
+            record = None
         if record is None:
             record = self.records[key] = self.capture(inputs, flat, host, step)
         for target, source in zip(record['inputs'], flat):
@@ -124,6 +140,9 @@ class CapturedIteration:
         for name, value in host.items():
             record['draws'][name].copy_(value, non_blocking=True)
         self.order_side_streams()
+        # Masters written since the last step (a checkpoint load, a copy into an arena, a test editing the weights): their
+        # 16-bit shadows are re-rounded here, on the replay's stream -- inside the graph they only follow the captured updates.
+        self.refresh_stale_shadows()
         # An eager iteration in between (a summary step, a warm-up) may have left an optimizer update waiting for its
         # gradient exchange (``_pending_updates``); the captured ``finish_update`` was a no-op when it was recorded, so it is
         # settled here, before the replay overwrites those gradients.
@@ -137,6 +156,18 @@ class CapturedIteration:
         for name, value in record['outputs'].items():
             setattr(e, name, _copied_out(value))
         self.replays += 1
+
+    def arenas(self):
+        e = self.experiment
+        return [network._srgan_arena for network in (e.DNN, e.D, e.G) if getattr(network, '_srgan_arena', None) is not None]
+
+    def shadow_counts(self):
+        return tuple(len(getattr(arena, 'shadows', ())) for arena in self.arenas())
+
+    def refresh_stale_shadows(self):
+        from . import blocked16
+        for arena in self.arenas():
+            blocked16.refresh_if_stale(arena)
 
     def capture(self, inputs, flat, host, step):
         e = self.experiment
@@ -158,6 +189,16 @@ class CapturedIteration:
             self.records.pop(next(iter(self.records)))
         advanced = None
         e.join_dnn_stream()                                   # nothing eager in flight on a side stream the capture forks
+        from . import blocked16
+        for arena in self.arenas():                           # shadow buffers, bias rows and pack plans exist and are current:
+            blocked16.prepare(arena)                          # the captured refreshes rewrite them in place
+        # Cyclic garbage that holds a captured graph or its pool memory (the record evicted above, an experiment dropped by its
+        # owner) must not be destroyed while a capture is under way: a graph's destructor calls the runtime, which aborts the
+        # process inside a capture.  torch.cuda.graph no longer collects before capturing (torch.compiler.config.
+        # force_cudagraph_gc), so it is done here, and the automatic collector stays off until the capture has ended.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
         try:
             with torch.cuda.graph(graph, pool=pool):
                 e.dnn_training_step(static_inputs[0], static_inputs[1], step)
@@ -167,6 +208,8 @@ class CapturedIteration:
                 e.finish_update()
             advanced = [optimizer.step_count - count for optimizer, count in zip(optimizers, before)]
         finally:
+            if collecting:
+                gc.enable()
             e.injected_draws = injected
             for optimizer, count in zip(optimizers, before):   # capturing recorded the launches, it did not run them
                 optimizer.step_count = count                   # (also when the capture raised)
@@ -174,4 +217,7 @@ class CapturedIteration:
         for name in STEP_OUTPUTS:
             value = getattr(e, name, None)
             outputs[name] = dict(value) if isinstance(value, dict) else value
-        return dict(graph=graph, inputs=static, draws=draws, advanced=advanced, outputs=outputs)
+        # (the pack plans' device job tables are read by the captured refreshes: the record keeps them alive)
+        plans = [getattr(arena, '_pack_plan', None) for arena in self.arenas()]
+        return dict(graph=graph, inputs=static, draws=draws, advanced=advanced, outputs=outputs, shadows=self.shadow_counts(),
+                    plans=plans)

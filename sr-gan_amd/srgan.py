@@ -250,10 +250,10 @@ class Experiment(ABC):
 
     def training_iteration(self, labeled_examples, labels, unlabeled_examples, step):
         """The body of the reference's loop (srgan.py:104-118): the DNN step, then the GAN step.  With
-        ``settings.step_graph`` on a single device the iteration is captured once as a HIP graph and replayed
+        ``settings.step_graph`` on a single device (fp32 or the 16-bit path; data parallel: fp32 only) the iteration is captured
+        once as a HIP graph and replayed
         (``graph.CapturedIteration``); summary steps and the first ``settings.step_graph_warmup`` iterations run eagerly."""
-        if getattr(self.settings, 'step_graph', False) and examples_on_gpu() and not getattr(self.settings, 'storage_dtype', None) \
-                and self._exchanges_are_capturable():
+        if getattr(self.settings, 'step_graph', False) and examples_on_gpu() and self._exchanges_are_capturable():
             if getattr(self, '_captured_iteration', None) is None:
                 from .graph import CapturedIteration
                 self._captured_iteration = CapturedIteration(self)
@@ -269,7 +269,8 @@ class Experiment(ABC):
         return getattr(self.settings, name, False)
 
     def _exchanges_are_capturable(self):
-        """True when this run's iterations can be captured as HIP graphs.  Single device: always.  Data parallel: only when the
+        """True when this run's iterations can be captured as HIP graphs.  Single device: always.  Data parallel: fp32 only (settings.storage_dtype
+        keeps such a run eager, with a note), and only when the
         caller OPTED IN with ``settings.step_graph_collectives = 'abi'`` -- the exchanges then run through the C ABI's RCCL entry
         points on a stream this process owns (``DataParallel.use_abi_collectives``, the default device transport; destroyed by
         ``close()``) and are captured with the iteration; collectives that go through a host-side process group
@@ -279,6 +280,12 @@ class Experiment(ABC):
         the compute side streams AND the communication stream)."""
         if not self.parallel:
             return True
+        if getattr(self.settings, 'storage_dtype', None):
+            if not getattr(self, '_graph_note', False):
+                print('[srgan_amd] step_graph with settings.storage_dtype replays on a single device only; running eagerly '
+                      'under data parallelism')
+                self._graph_note = True
+            return False
         if getattr(self.settings, 'step_graph_collectives', None) != 'abi':
             if not getattr(self, '_graph_note', False):
                 print('[srgan_amd] step_graph under data parallelism needs settings.step_graph_collectives = "abi" '
