@@ -8,6 +8,7 @@ import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
+PUBLIC_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'srgan_hip.h')
 LIBRARY = os.path.join(CSRC, 'libsrgan_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-I' + CSRC]
 
@@ -17,13 +18,15 @@ def _sources():
 
 
 def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
+    """csrc/*.h and the public header, which csrc/common.h includes into every translation unit."""
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [PUBLIC_HEADER]
 
 
 def source_id():
-    """sha256 over the names and contents of every csrc/*.hip and *.h: the identity of the kernel sources.  It is
-    compiled into the library (``srgan_build_id()``) and compared by ``_lib.library()`` when the library is loaded, so
-    a stale prebuilt .so is detected by content, not by file times (which do not survive the copy to the GPU box)."""
+    """sha256 over the names and contents of every csrc/*.hip and *.h and of include/srgan_hip.h: the identity of the
+    kernel sources.  It is compiled into the library (``srgan_build_id()``) and compared by ``_lib.library()`` when the
+    library is loaded, so a stale prebuilt .so is detected by content, not by file times (which do not survive the copy
+    to the GPU box)."""
     digest = hashlib.sha256()
     for path in sorted(_sources() + _headers()):
         digest.update(os.path.basename(path).encode())
@@ -87,6 +90,7 @@ def build(force=False, verbose=True):
     # owns the allocations and streams we are handed).
     # Linked under a temporary name and renamed into place: a rank that waits for the file never maps a half-written one.
     temporary = f'{LIBRARY}.tmp.{os.getpid()}'
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC'] + objects + ['-o', temporary])
+    # -z defs: a declared but undefined function fails the link here, not the first dlopen on another machine.
+    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs'] + objects + ['-o', temporary])
     os.replace(temporary, LIBRARY)
     return LIBRARY

@@ -272,9 +272,4 @@ struct HPackJob {
 
 const struct Slot* h_zero_slots();      // 64 bytes of zeros in device memory (blocked16.hip): the source of padding slots
 
-// Declared in gather_gemm_kernels.hip: the bench's live event bracket around a contraction launch, with explicit bytes.
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn, int split,
-                              double bytes, int precision);
-
 }  // namespace srgan

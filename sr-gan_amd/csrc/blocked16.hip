@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <string.h>
 #include "blocked16.h"
+#include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <atomic>
@@ -958,8 +959,6 @@ __global__ __launch_bounds__(256) void hwgrad3x3_finish_kernel(const float* __re
   }
 }
 
-float* partial_workspace(size_t bytes, hipStream_t stream);
-
 static int check_dtype(int dtype) {
   SRGAN_REQUIRE(dtype == 1 || dtype == 2, SRGAN_EINVAL, "blocked 16-bit tensors are bf16 (1) or fp16 (2)");
   return SRGAN_OK;
@@ -969,13 +968,6 @@ static int check_dtype_or_f32(int dtype) {        // the layout conversions and 
   return SRGAN_OK;
 }
 
-}  // namespace srgan
-
-using namespace srgan;
-
-extern "C" int64_t srgan_h_k4s2_weight_slots(int32_t A, int32_t B, int direction, int dtype);     // (blocked16_k4s2.hip)
-
-namespace srgan {
 // the job (= the single-layer kernel's arguments) of one conv-weight operand; transposed: rows = C, taps mirrored
 static void conv_weights_job(HPackJob& job, const float* w, void* packed, int32_t K, int32_t C, int32_t R, int32_t S, int transposed,
                              int dtype) {
@@ -989,50 +981,57 @@ static void conv_weights_job(HPackJob& job, const float* w, void* packed, int32_
   job.p[6] = transposed ? C * R * S : R * S;                // reduced-channel stride
   job.p[7] = transposed ? -S : S; job.p[8] = transposed ? -1 : 1;
 }
+
 }  // namespace srgan
+
+using namespace srgan;
 
 extern "C" {
 
 int srgan_h_pack(const float* x, void* out, const void* mask_ref, float slope, int32_t N, int32_t C, int64_t HW, int dtype,
-                 hipStream_t stream) {
+                 void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_or_f32(dtype)) return status;
   SRGAN_REQUIRE(x && out && N >= 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_pack arguments");
   const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
   const int64_t slots = (int64_t)N * CG * HW;
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_pack_kernel<0>, grid, dim3(256), 0, stream, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
-  else if (dtype == 1) hipLaunchKernelGGL(h_pack_kernel<1>, grid, dim3(256), 0, stream, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
-  else hipLaunchKernelGGL(h_pack_kernel<2>, grid, dim3(256), 0, stream, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
+  if (dtype == 0) hipLaunchKernelGGL(h_pack_kernel<0>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
+  else if (dtype == 1) hipLaunchKernelGGL(h_pack_kernel<1>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
+  else hipLaunchKernelGGL(h_pack_kernel<2>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
   return launch_status();
 }
 
-int srgan_h_unpack(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, hipStream_t stream) {
+int srgan_h_unpack(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_or_f32(dtype)) return status;
   SRGAN_REQUIRE(x && out && N >= 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_unpack arguments");
   const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
   const int64_t slots = (int64_t)N * CG * HW;
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_unpack_kernel<0>, grid, dim3(256), 0, stream, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
-  else if (dtype == 1) hipLaunchKernelGGL(h_unpack_kernel<1>, grid, dim3(256), 0, stream, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
-  else hipLaunchKernelGGL(h_unpack_kernel<2>, grid, dim3(256), 0, stream, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
+  if (dtype == 0) hipLaunchKernelGGL(h_unpack_kernel<0>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
+  else if (dtype == 1) hipLaunchKernelGGL(h_unpack_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
+  else hipLaunchKernelGGL(h_unpack_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
   return launch_status();
 }
 
-int srgan_h_add(const void* a, const void* b, void* out, int64_t slots, int dtype, hipStream_t stream) {
+int srgan_h_add(const void* a, const void* b, void* out, int64_t slots, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_or_f32(dtype)) return status;
   SRGAN_REQUIRE(a && b && out && slots >= 0, SRGAN_EINVAL, "srgan_h_add arguments");
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_add_kernel<0>, grid, dim3(256), 0, stream, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
-  else if (dtype == 1) hipLaunchKernelGGL(h_add_kernel<1>, grid, dim3(256), 0, stream, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
-  else hipLaunchKernelGGL(h_add_kernel<2>, grid, dim3(256), 0, stream, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
+  if (dtype == 0) hipLaunchKernelGGL(h_add_kernel<0>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
+  else if (dtype == 1) hipLaunchKernelGGL(h_add_kernel<1>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
+  else hipLaunchKernelGGL(h_add_kernel<2>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
   return launch_status();
 }
 
 // out[c] += sum over n and pixels of x[n, c, pixel]   (c < C; fp32; the bias gradient of a fused convolution / linear layer)
-int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, hipStream_t stream) {
+int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_or_f32(dtype)) return status;
   SRGAN_REQUIRE(x && out && N > 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_channel_sums arguments");
   const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
@@ -1043,23 +1042,24 @@ int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_
   while (parts > 1 && (int64_t)parts * CG > 4096) parts >>= 1;
   unsigned int* tickets = nullptr;
   static const bool two_launches = getenv("SRGAN_H_SUMS_TWO_LAUNCHES") != nullptr;
-  float* part = two_launches ? nullptr : row_finish_workspace(CG, parts, 8, g_h_sum_tickets, stream, &tickets);
+  float* part = two_launches ? nullptr : row_finish_workspace(CG, parts, 8, g_h_sum_tickets, s, &tickets);
   if (!part) {
     tickets = nullptr;
-    part = partial_workspace((size_t)CG * parts * 8 * sizeof(float), stream);
+    part = partial_workspace((size_t)CG * parts * 8 * sizeof(float), s);
   }
   SRGAN_REQUIRE(part, SRGAN_EINVAL, "srgan_h_channel_sums: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)CG, (unsigned)parts);
-  if (dtype == 0) hipLaunchKernelGGL(h_channel_sums_kernel<0>, grid, dim3(256), 0, stream, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  else if (dtype == 1) hipLaunchKernelGGL(h_channel_sums_kernel<1>, grid, dim3(256), 0, stream, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  else hipLaunchKernelGGL(h_channel_sums_kernel<2>, grid, dim3(256), 0, stream, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  if (!tickets) hipLaunchKernelGGL(h_channel_sums_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, part, out, C, parts, group);
+  if (dtype == 0) hipLaunchKernelGGL(h_channel_sums_kernel<0>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
+  else if (dtype == 1) hipLaunchKernelGGL(h_channel_sums_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
+  else hipLaunchKernelGGL(h_channel_sums_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
+  if (!tickets) hipLaunchKernelGGL(h_channel_sums_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, out, C, parts, group);
   return launch_status();
 }
 
 // mode 0: out = maxpool2x2(x); mode 2: out = `g` gathered at the arg-max of x (both [planes][H/2][W/2] slots, planes = N * groups)
 int srgan_h_maxpool2(const void* x, const void* g, void* out, int64_t planes, int32_t H, int32_t W, int mode, int dtype,
-                     hipStream_t stream) {
+                     void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype(dtype)) return status;
   SRGAN_REQUIRE(x && out && planes >= 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && (mode == 0 || (mode == 2 && g)),
                 SRGAN_EINVAL, "srgan_h_maxpool2 arguments (even planes; mode 0 or 2)");
@@ -1067,26 +1067,27 @@ int srgan_h_maxpool2(const void* x, const void* g, void* out, int64_t planes, in
   if (total == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(total, 256));
   if (dtype == 1) {
-    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<1, 0>), grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-    else hipLaunchKernelGGL((h_maxpool_kernel<1, 2>), grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<1, 0>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+    else hipLaunchKernelGGL((h_maxpool_kernel<1, 2>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
   } else {
-    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<2, 0>), grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-    else hipLaunchKernelGGL((h_maxpool_kernel<2, 2>), grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<2, 0>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+    else hipLaunchKernelGGL((h_maxpool_kernel<2, 2>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
   }
   return launch_status();
 }
 
 // gx (shape of x) = gp placed at the arg-max of x, times mask(x, slope) when `masked`
 int srgan_h_maxpool2_bwd(const void* x, const void* gp, void* gx, int64_t planes, int32_t H, int32_t W, int masked, float slope,
-                         int dtype, hipStream_t stream) {
+                         int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype(dtype)) return status;
   SRGAN_REQUIRE(x && gp && gx && planes >= 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, SRGAN_EINVAL,
                 "srgan_h_maxpool2_bwd arguments");
   const int64_t total = planes * (H / 2) * (W / 2);
   if (total == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(total, 256));
-  if (dtype == 1) hipLaunchKernelGGL(h_maxpool_bwd_kernel<1>, grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
-  else hipLaunchKernelGGL(h_maxpool_bwd_kernel<2>, grid, dim3(256), 0, stream, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
+  if (dtype == 1) hipLaunchKernelGGL(h_maxpool_bwd_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
+  else hipLaunchKernelGGL(h_maxpool_bwd_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
   return launch_status();
 }
 
@@ -1098,15 +1099,16 @@ int64_t srgan_h_conv_weight_slots(int32_t CO, int32_t CI, int32_t R, int32_t S) 
 // transposed = 0: the forward operand of conv2d weights w[K][C][R][S] (rows = K, reduced = C).
 // transposed = 1: the data-gradient operand (rows = C, reduced = K, taps mirrored).
 int srgan_h_pack_conv_weights(const float* w, void* packed, int32_t K, int32_t C, int32_t R, int32_t S, int transposed, int dtype,
-                              hipStream_t stream) {
+                              void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype(dtype)) return status;
   SRGAN_REQUIRE(w && packed && K > 0 && C > 0 && R > 0 && S > 0, SRGAN_EINVAL, "srgan_h_pack_conv_weights arguments");
   HPackJob job;
   conv_weights_job(job, w, packed, K, C, R, S, transposed, dtype);
   const dim3 grid((unsigned)((job.slots + 255) / 256));
   const int32_t* q = job.p;
-  if (dtype == 1) hipLaunchKernelGGL(h_pack_conv_weights_kernel<1>, grid, dim3(256), 0, stream, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
-  else hipLaunchKernelGGL(h_pack_conv_weights_kernel<2>, grid, dim3(256), 0, stream, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  if (dtype == 1) hipLaunchKernelGGL(h_pack_conv_weights_kernel<1>, grid, dim3(256), 0, s, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  else hipLaunchKernelGGL(h_pack_conv_weights_kernel<2>, grid, dim3(256), 0, s, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
   return launch_status();
 }
 
@@ -1193,9 +1195,10 @@ int64_t srgan_h_pack_job_bias_rows(void* jobs, int64_t first_block, const float*
   return (job.slots + 255) / 256;
 }
 
-int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks, hipStream_t stream) {
+int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   SRGAN_REQUIRE(jobs_device && count > 0 && blocks > 0 && blocks < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_pack_batched arguments");
-  hipLaunchKernelGGL(h_pack_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const HPackJob*)jobs_device, count);
+  hipLaunchKernelGGL(h_pack_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const HPackJob*)jobs_device, count);
   return launch_status();
 }
 
@@ -1203,7 +1206,8 @@ int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks,
 // epi 0: plain; 1: + bias (may be NULL), then leaky_relu(slope) (slope 0 = relu, 1 = identity); 2: times mask(ref, slope), ref
 // of the output's shape.  C_out = the channels the output tensor stores (rows of the packed weights may be fewer or more).
 int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
-                    int32_t N, int32_t C_in, int32_t C_out, int32_t rows, int32_t H, int32_t W, int dtype, hipStream_t stream) {
+                    int32_t N, int32_t C_in, int32_t C_out, int32_t rows, int32_t H, int32_t W, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype(dtype)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && C_out > 0 && rows > 0 && H > 0 && W > 0 && epi >= 0 && epi <= 2 &&
                 (epi != 2 || ref), SRGAN_EINVAL, "srgan_h_conv3x3 arguments");
@@ -1223,7 +1227,7 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
   if (split > 1) {
     int ticket_set = -1;
     const int64_t accumulators = (int64_t)(plan.bm / 32) * plan.ni * 16 * 256;
-    float* ws = split_workspace(plan.blocks, split, accumulators, 0, stream, &ticket_set);
+    float* ws = split_workspace(plan.blocks, split, accumulators, 0, s, &ticket_set);
     unsigned int* tickets = ws ? device_tickets(g_hconv3_split_tickets) : nullptr;
     if (ws && tickets) {
       p.split_ws = ws;
@@ -1246,25 +1250,26 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
   const int ring = ring_env >= 0 ? ring_env : 2;
   const Slot* zero = (ring == 2 || ring == 3) && split == 1 && plan.bm == 64
                          ? h_zero_slots() : nullptr;
-  const int slot = profile_bracket_begin(stream);
+  const int slot = profile_bracket_begin(s);
   if (zero) {
     int launched;
-    if (ring == 3) launched = dtype == 1 ? hconv3_dma_launch<1, 3>(p, plan, grid, stream, zero) : hconv3_dma_launch<2, 3>(p, plan, grid, stream, zero);
-    else launched = dtype == 1 ? hconv3_dma_launch<1, 2>(p, plan, grid, stream, zero) : hconv3_dma_launch<2, 2>(p, plan, grid, stream, zero);
+    if (ring == 3) launched = dtype == 1 ? hconv3_dma_launch<1, 3>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 3>(p, plan, grid, s, zero);
+    else launched = dtype == 1 ? hconv3_dma_launch<1, 2>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 2>(p, plan, grid, s, zero);
     if (launched != SRGAN_OK) return launched;
   }
-  else if (dtype == 1) hconv3_launch<1>(p, plan, grid, stream);
-  else hconv3_launch<2>(p, plan, grid, stream);
+  else if (dtype == 1) hconv3_launch<1>(p, plan, grid, s);
+  else hconv3_launch<2>(p, plan, grid, s);
   const int status = launch_status();
   const double pixels = (double)N * H * W;
-  profile_bracket_end_bytes(slot, stream, rows_needed, (int64_t)pixels, (int64_t)p.CGI * 8 * 9, 14, plan.bm, plan.ni * 128, split,
+  profile_bracket_end_bytes(slot, s, rows_needed, (int64_t)pixels, (int64_t)p.CGI * 8 * 9, 14, plan.bm, plan.ni * 128, split,
                             2.0 * (pixels * p.CGI * 8 + pixels * p.CGO * 8 * (epi == 2 ? 2 : 1) + (double)rows * p.CGI * 8 * 9), dtype);
   return status;
 }
 
 // gw[C_out][C_in][3][3] (fp32) += the weight gradient of a 3x3 / s1 / p1 convolution from x[N, C_in, H, W] and gy[N, C_out, H, W]
 int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, int32_t C_in, int32_t C_out, int32_t H, int32_t W,
-                          int dtype, hipStream_t stream) {
+                          int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype(dtype)) return status;
   SRGAN_REQUIRE(x && gy && gw && N > 0 && C_in > 0 && C_out > 0 && H > 0 && W > 0, SRGAN_EINVAL, "srgan_h_conv3x3_wgrad arguments");
   HWgrad3Params p;
@@ -1298,18 +1303,18 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
   if (walkers < 1) walkers = 1;
   p.walkers = walkers;
   const int threads = 128 * mb;
-  p.partial = partial_workspace((size_t)blocks * walkers * 9 * 16 * threads * sizeof(float), stream);
+  p.partial = partial_workspace((size_t)blocks * walkers * 9 * 16 * threads * sizeof(float), s);
   SRGAN_REQUIRE(p.partial, SRGAN_EINVAL, "srgan_h_conv3x3_wgrad: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)blocks, (unsigned)walkers);
-  const int slot = profile_bracket_begin(stream);
+  const int slot = profile_bracket_begin(s);
 #define HWGRAD_LAUNCH(TWv, ROWSv)                                                                                       \
   do {                                                                                                                  \
     if (mb == 4) {                                                                                                      \
-      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 4>), grid, dim3(512), 0, stream, p);         \
-      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 4>), grid, dim3(512), 0, stream, p);                    \
+      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 4>), grid, dim3(512), 0, s, p);               \
+      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 4>), grid, dim3(512), 0, s, p);                          \
     } else {                                                                                                            \
-      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 2>), grid, dim3(256), 0, stream, p);         \
-      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 2>), grid, dim3(256), 0, stream, p);                    \
+      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 2>), grid, dim3(256), 0, s, p);               \
+      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 2>), grid, dim3(256), 0, s, p);                          \
     }                                                                                                                   \
   } while (0)
   if (tw == 32) HWGRAD_LAUNCH(32, 2);
@@ -1318,11 +1323,11 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
   else HWGRAD_LAUNCH(4, 4);
 #undef HWGRAD_LAUNCH
   const int64_t elements = (int64_t)C_out * C_in * 9;
-  hipLaunchKernelGGL(hwgrad3x3_finish_kernel, dim3((unsigned)(blocks * 32 * mb)), dim3(256), 0, stream, p.partial, gw,
+  hipLaunchKernelGGL(hwgrad3x3_finish_kernel, dim3((unsigned)(blocks * 32 * mb)), dim3(256), 0, s, p.partial, gw,
                      C_out, C_in, p.tiles_ci, walkers, 32 * mb);
   const int status = launch_status();
   const double pixels = (double)N * H * W;
-  profile_bracket_end_bytes(slot, stream, C_out, (int64_t)C_in * 9, (int64_t)pixels, 15, 32 * mb, 64, walkers,
+  profile_bracket_end_bytes(slot, s, C_out, (int64_t)C_in * 9, (int64_t)pixels, 15, 32 * mb, 64, walkers,
                             2.0 * pixels * (p.CGX + p.CGY) * 8 + 8.0 * (double)elements, dtype);
   return status;
 }

@@ -10,6 +10,7 @@
 //                         flattened blocked plane ([c][p] -> [c / 8][p][c % 8])
 #include <type_traits>
 #include "blocked16.h"
+#include "launchers.h"
 #include "split_finish.h"
 
 namespace srgan {
@@ -311,7 +312,8 @@ extern "C" {
 // flattened blocked plane tensor with P pixels (P <= 1: identity).
 int srgan_h_pack_matrix(const float* src, void* out, int64_t rows, int64_t cols, int64_t rows_real, int64_t cols_real,
                         int64_t row_stride, int64_t col_stride, int32_t row_plane, int32_t col_plane, int dtype,
-                        hipStream_t stream) {
+                        void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_g(dtype)) return status;
   SRGAN_REQUIRE(src && out && rows > 0 && cols > 0, SRGAN_EINVAL, "srgan_h_pack_matrix arguments");
   const int64_t row_slots = (cols + 7) / 8, slots = rows * row_slots;
@@ -319,20 +321,21 @@ int srgan_h_pack_matrix(const float* src, void* out, int64_t rows, int64_t cols,
   if (row_stride == 1 && col_stride != 1) {
     const int tiles_r = (int)((rows + 63) / 64), tiles_c = (int)((row_slots * 8 + 63) / 64);
     const dim3 tgrid((unsigned)(tiles_r * tiles_c));
-    if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<1>, tgrid, dim3(256), 0, stream, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
-    else hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<2>, tgrid, dim3(256), 0, stream, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
+    if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<1>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
+    else hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<2>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
     return launch_status();
   }
   const dim3 grid((unsigned)((slots + 255) / 256));
-  if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_kernel<1>, grid, dim3(256), 0, stream, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
-  else hipLaunchKernelGGL(h_pack_matrix_kernel<2>, grid, dim3(256), 0, stream, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
+  if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_kernel<1>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
+  else hipLaunchKernelGGL(h_pack_matrix_kernel<2>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
   return launch_status();
 }
 
 // out[N][M'] = epi(B[N][K] * A[M][K]^T [+ bias]) on 16-bit row-major matrices (pitches = ceil(. / 8) slots); M' = out_cols.
 // epi as srgan_h_conv3x3.  The output's columns beyond M (inside its last slot) are written as zeros.
 int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* ref, float slope, int epi, void* out, int32_t M,
-                 int32_t N, int32_t K, int32_t out_cols, int32_t bias_entries, int dtype, hipStream_t stream) {
+                 int32_t N, int32_t K, int32_t out_cols, int32_t bias_entries, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_g(dtype)) return status;
   SRGAN_REQUIRE(a && b && out && M > 0 && N > 0 && K > 0 && out_cols > 0 && epi >= 0 && epi <= 2 && (epi != 2 || ref), SRGAN_EINVAL,
                 "srgan_h_gemm arguments");
@@ -358,7 +361,7 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
   p.split_ws = nullptr; p.split_tickets = nullptr;
   if (split > 1) {
     int ticket_set = -1;
-    float* ws = split_workspace(tiles, split, 64 * 256, 0, stream, &ticket_set);
+    float* ws = split_workspace(tiles, split, 64 * 256, 0, s, &ticket_set);
     unsigned int* tickets = ws ? device_tickets(g_hgemm_split_tickets) : nullptr;
     if (ws && tickets) {
       p.split_ws = ws;
@@ -369,11 +372,11 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
     }
   }
   const dim3 grid((unsigned)tiles, (unsigned)split);
-  const int slot = profile_bracket_begin(stream);
-  if (dtype == 1) hipLaunchKernelGGL(hgemm_kernel<1>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(hgemm_kernel<2>, grid, dim3(256), 0, stream, p);
+  const int slot = profile_bracket_begin(s);
+  if (dtype == 1) hipLaunchKernelGGL(hgemm_kernel<1>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(hgemm_kernel<2>, grid, dim3(256), 0, s, p);
   const int status = launch_status();
-  profile_bracket_end_bytes(slot, stream, M, N, K, 16, 128, 128, split,
+  profile_bracket_end_bytes(slot, s, M, N, K, 16, 128, 128, split,
                             2.0 * ((double)M * K + (double)N * K + (double)N * out_cols * (epi == 2 ? 2 : 1)), dtype);
   return status;
 }
@@ -381,7 +384,8 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
 // gw (fp32) element (m, k) at gw[map(m, row_plane) * ldw_m + map(k, col_plane) * ldw_k] += sum_n S[n][m] * X[n][k] for
 // mapped indices inside [M_real) x [K_real); S is [N][M cols], X is [N][K cols] (16-bit, pitches ceil(. / 8) slots).
 int srgan_h_linear_wgrad(const void* s, const void* x, float* gw, int32_t N, int32_t M, int32_t K, int64_t M_real, int64_t K_real,
-                         int64_t ldw_m, int64_t ldw_k, int32_t row_plane, int32_t col_plane, int dtype, hipStream_t stream) {
+                         int64_t ldw_m, int64_t ldw_k, int32_t row_plane, int32_t col_plane, int dtype, void* stream) {
+  hipStream_t hs = (hipStream_t)stream;
   if (const int status = check_dtype_g(dtype)) return status;
   SRGAN_REQUIRE(s && x && gw && N > 0 && M > 0 && K > 0, SRGAN_EINVAL, "srgan_h_linear_wgrad arguments");
   HLinearWgradParams p;
@@ -392,11 +396,11 @@ int srgan_h_linear_wgrad(const void* s, const void* x, float* gw, int32_t N, int
   p.tiles_m = (p.MS + 15) / 16;
   const int tiles_k = (p.KS + 15) / 16;
   const dim3 grid((unsigned)(p.tiles_m * tiles_k));
-  const int slot = profile_bracket_begin(stream);
-  if (dtype == 1) hipLaunchKernelGGL(hlinear_wgrad_kernel<1>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(hlinear_wgrad_kernel<2>, grid, dim3(256), 0, stream, p);
+  const int slot = profile_bracket_begin(hs);
+  if (dtype == 1) hipLaunchKernelGGL(hlinear_wgrad_kernel<1>, grid, dim3(256), 0, hs, p);
+  else hipLaunchKernelGGL(hlinear_wgrad_kernel<2>, grid, dim3(256), 0, hs, p);
   const int status = launch_status();
-  profile_bracket_end_bytes(slot, stream, M, K, N, 17, 128, 128, 1, 2.0 * (double)N * (M + K) + 8.0 * (double)M * K, dtype);
+  profile_bracket_end_bytes(slot, hs, M, K, N, 17, 128, 128, 1, 2.0 * (double)N * (M + K) + 8.0 * (double)M * K, dtype);
   return status;
 }
 

@@ -22,12 +22,10 @@
 #include <atomic>
 #include <stdlib.h>
 #include "blocked16.h"
+#include "launchers.h"
 #include "split_finish.h"
 
 namespace srgan {
-
-float* partial_workspace(size_t bytes, hipStream_t stream);
-
 
 // (G = channels per slot: 8, or 4 for the fp32 form)
 // mode 0 ("down"): slot (chunk, tap = 2a + b, j = 2 qy + qx, o) = G reduced channels G chunk .. of w[o][.][2a + qy][2b + qx]
@@ -682,7 +680,8 @@ int64_t srgan_h_k4s2_weight_slots(int32_t A, int32_t B, int direction, int dtype
   return (int64_t)4 * (((A + g - 1) / g + K4_CK - 1) / K4_CK) * K4_TAPS * K4_CK * B;
 }
 
-int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B, int direction, int dtype, hipStream_t stream) {
+int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B, int direction, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_k(dtype)) return status;
   SRGAN_REQUIRE(w && packed && A > 0 && B > 0 && (direction == 0 || direction == 1), SRGAN_EINVAL, "srgan_h_pack_k4s2_weights arguments");
 #define K4_PACK(...)                                                                                                     \
@@ -694,14 +693,14 @@ int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B
   if (direction == 0) {
     const int64_t slots = srgan_h_k4s2_weight_slots(A, B, 0, dtype);
     const dim3 grid((unsigned)((slots + 255) / 256));
-    K4_PACK(grid, dim3(256), 0, stream, w, (Slot*)packed, slots, A, B, (int64_t)B * 16, (int64_t)16, 0);
+    K4_PACK(grid, dim3(256), 0, s, w, (Slot*)packed, slots, A, B, (int64_t)B * 16, (int64_t)16, 0);
     return launch_status();
   }
   const int64_t per_class = srgan_h_k4s2_weight_slots(A, B, 1, dtype) / 4;
   const dim3 grid((unsigned)((per_class + 255) / 256));
   for (int cls = 0; cls < 4; ++cls) {
     Slot* into = (Slot*)packed + cls * per_class;
-    K4_PACK(grid, dim3(256), 0, stream, w, into, per_class, B, A, (int64_t)16, (int64_t)B * 16, 1 + cls);
+    K4_PACK(grid, dim3(256), 0, s, w, into, per_class, B, A, (int64_t)16, (int64_t)B * 16, 1 + cls);
   }
 #undef K4_PACK
   return launch_status();
@@ -710,7 +709,8 @@ int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B
 // "down": out[N, rows, H/2, W/2] = epi(conv2d 4x4 / stride 2 / pad 1 of x[N, C_in, H, W]) with the direction-0 operand of
 // srgan_h_pack_k4s2_weights (rows = its A).  epi as srgan_h_conv3x3.
 int srgan_h_conv4x4s2(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
-                      int32_t N, int32_t C_in, int32_t rows, int32_t H, int32_t W, int dtype, hipStream_t stream) {
+                      int32_t N, int32_t C_in, int32_t rows, int32_t H, int32_t W, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_k(dtype)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && rows > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && epi >= 0 &&
                 epi <= 2 && (epi != 2 || ref), SRGAN_EINVAL, "srgan_h_conv4x4s2 arguments (even planes)");
@@ -727,14 +727,15 @@ int srgan_h_conv4x4s2(const void* x, const void* packed, const float* bias, cons
   p.class_stride = 0;
   SRGAN_REQUIRE((int64_t)N * p.CGI * H * W < ((int64_t)1 << 31) && (int64_t)N * p.CGO * p.OH * p.OW < ((int64_t)1 << 31), SRGAN_ERANGE,
                 "srgan_h_conv4x4s2 tensor size");
-  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 16, stream);
+  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 16, s);
 }
 
 // "up": out[N, rows, 2h, 2w] = epi(conv_transpose2d 4x4 / stride 2 / pad 1 of x[N, C_in, h, w]) with the direction-1 operand
 // (rows = its B, C_in = its A): one launch, gridDim.y = the four output parity classes.
 int srgan_h_conv_transpose4x4s2(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi,
                                 void* out, int32_t N, int32_t C_in, int32_t rows, int32_t h, int32_t w, int dtype,
-                                hipStream_t stream) {
+                                void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_k(dtype)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && rows > 0 && h > 0 && w > 0 && epi >= 0 && epi <= 2 && (epi != 2 || ref),
                 SRGAN_EINVAL, "srgan_h_conv_transpose4x4s2 arguments");
@@ -751,14 +752,15 @@ int srgan_h_conv_transpose4x4s2(const void* x, const void* packed, const float* 
   p.class_stride = srgan_h_k4s2_weight_slots(C_in, rows, 1, dtype) / 4;
   SRGAN_REQUIRE((int64_t)N * p.CGI * h * w < ((int64_t)1 << 31) && (int64_t)N * p.CGO * p.OH * p.OW < ((int64_t)1 << 31), SRGAN_ERANGE,
                 "srgan_h_conv_transpose4x4s2 tensor size");
-  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 4, stream);
+  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 4, s);
 }
 
 // gw (fp32 [A][B][4][4] in torch's layout) += the weight gradient of the 4x4 / stride 2 / pad 1 pair from `small` [N, C_small, H/2,
 // W/2] and `big` [N, C_big, H, W].  small_is_rows = 1: gw is indexed [C_small][C_big] (a strided convolution's weight: small = its
 // output gradient); 0: [C_big][C_small] (a transposed convolution's weight: small = its input).
 int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N, int32_t C_big, int32_t C_small, int32_t H, int32_t W,
-                       int small_is_rows, int dtype, hipStream_t stream) {
+                       int small_is_rows, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (const int status = check_dtype_k(dtype)) return status;
   SRGAN_REQUIRE(big && small && gw && N > 0 && C_big > 0 && C_small > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, SRGAN_EINVAL,
                 "srgan_h_k4s2_wgrad arguments");
@@ -787,15 +789,15 @@ int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N,
   if (walkers > p.pixel_tiles) walkers = p.pixel_tiles;
   if (walkers < 1) walkers = 1;
   p.walkers = walkers;
-  p.partial = partial_workspace((size_t)blocks * walkers * 8 * 16 * 256 * sizeof(float), stream);
+  p.partial = partial_workspace((size_t)blocks * walkers * 8 * 16 * 256 * sizeof(float), s);
   SRGAN_REQUIRE(p.partial, SRGAN_EINVAL, "srgan_h_k4s2_wgrad: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)blocks, (unsigned)walkers);
-  const int slot = profile_bracket_begin(stream);
+  const int slot = profile_bracket_begin(s);
 #define HWGRAD4_LAUNCH(TWv, ROWSv, ROWSf)                                                                              \
   do {                                                                                                                  \
-    if (dtype == 0) hipLaunchKernelGGL((hwgrad4x4s2_f32_kernel<TWv, ROWSf>), grid, dim3(256), 0, stream, p);           \
-    else if (dtype == 1) hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 1>), grid, dim3(256), 0, stream, p);      \
-    else hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 2>), grid, dim3(256), 0, stream, p);                      \
+    if (dtype == 0) hipLaunchKernelGGL((hwgrad4x4s2_f32_kernel<TWv, ROWSf>), grid, dim3(256), 0, s, p);                 \
+    else if (dtype == 1) hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 1>), grid, dim3(256), 0, s, p);             \
+    else hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 2>), grid, dim3(256), 0, s, p);                             \
   } while (0)
   if (tw == 32) HWGRAD4_LAUNCH(32, 2, 1);
   else if (tw == 16) HWGRAD4_LAUNCH(16, 4, 2);
@@ -803,11 +805,11 @@ int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N,
   else HWGRAD4_LAUNCH(4, 4, 4);
 #undef HWGRAD4_LAUNCH
   const int64_t sk = small_is_rows ? (int64_t)C_big * 16 : 16, sc = small_is_rows ? 16 : (int64_t)C_small * 16;
-  hipLaunchKernelGGL(hwgrad4x4s2_finish_kernel, dim3((unsigned)(blocks * 64)), dim3(256), 0, stream, p.partial, gw, C_small, C_big,
+  hipLaunchKernelGGL(hwgrad4x4s2_finish_kernel, dim3((unsigned)(blocks * 64)), dim3(256), 0, s, p.partial, gw, C_small, C_big,
                      p.tiles_c, walkers, sk, sc);
   const int status = launch_status();
   const double pixels = (double)N * p.SH * p.SW;
-  profile_bracket_end_bytes(slot, stream, C_small, (int64_t)C_big * 16, (int64_t)pixels, 19, 64, 32, walkers,
+  profile_bracket_end_bytes(slot, s, C_small, (int64_t)C_big * 16, (int64_t)pixels, 19, 64, 32, walkers,
                             2.0 * (pixels * p.CGS * 8 + 4.0 * pixels * p.CGB * 8) + 8.0 * (double)C_small * C_big * 16, dtype);
   return status;
 }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+// The C ABI: every extern "C" definition is compiled against its declaration here.
+#include "../../include/srgan_hip.h"
 
 namespace srgan {
 

@@ -14,6 +14,7 @@
 // before the current chunk's 9 * CI_T / 2 * MI * NI MFMAs, so HBM latency hides under the matrix pipe.
 // Roofline: fp32 MFMA (157.3 TF/s); algorithmic work 2 * 9 * CI * CO FLOP per output pixel.
 #include "common.h"
+#include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -55,12 +56,9 @@ struct Conv3Params {
   int32_t xcd_remap;
 };
 
-constexpr int CONV3_PRO_MAX_CI = 512;
+constexpr int CONV3_PRO_MAX_CI = 512;   // channels of one workgroup's K range whose (a, b) fit the LDS table
 
 __device__ unsigned int g_conv3_split_tickets[SPLIT_TICKET_SETS * SPLIT_TICKET_TILES];
-
-// A stride-2 class of a k4 / s2 / p1 transposed convolution as a 2x2 sub-window of the 3x3 kernel (see conv3x3_run).
-struct Conv3Placement { int32_t taps, out_plane, out_sy, out_sx, out_off; };   // channels of one workgroup's K range whose (a, b) fit the LDS table
 
 // PRO = frozen batch-norm + ReLU fused into the patch staging (reference crowd/models.py:342-345: norm2, relu2,
 // conv2): the (a, b) of the workgroup's input channels sit in a small LDS table and every patch element goes through
@@ -761,11 +759,6 @@ static void launch_conv3_mixed(const Conv3Params& p, int bm, int th, int tw, int
   }
 }
 
-// Declared in gather_gemm_kernels.hip: records a launch for the bench's live event timing.
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
-
 bool conv3x3_enabled() {
   static const bool disabled = getenv("SRGAN_NO_CONV3") != nullptr;
   return !disabled;
@@ -843,10 +836,6 @@ int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int
   const Conv3Plan plan = conv3x3_plan(N, CI, CO, H, W, false);
   return plan.blocks / plan.tiles_m;
 }
-
-void bn_partial_reduce_run(const float* partial, int tiles, int CO, const float* inv_std, float* g_gamma, float* g_beta,
-                           hipStream_t stream);
-float* partial_workspace(size_t bytes, hipStream_t stream);
 
 // out = conv3x3(in, w) (+ bias), generic weight strides (forward and flipped-tap data gradient share the kernel).
 // The caller guarantees dense-or-strided NCHW, 3x3 / stride 1 / pad 1.  `accumulate` adds into out.

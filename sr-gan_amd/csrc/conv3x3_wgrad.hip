@@ -13,6 +13,7 @@
 // (raw loads from clamped addresses; the validity mask is applied when the registers are written to LDS -- a use of
 // the loaded value before the MFMA loop would make the compiler wait for the loads there).
 #include "common.h"
+#include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <string.h>
@@ -437,10 +438,6 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_grouped_finish_kernel(const
   conv3x3_wgrad_finish_chunk(partial_base + job.partial_off, gw, (int)blockIdx.y, (int)blockIdx.x, job.walkers, job.ci_chunks, job.CO,
                              job.CI);
 }
-
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
 
 bool conv3x3_wgrad_enabled() {
   static const bool disabled = getenv("SRGAN_NO_WGRAD3") != nullptr;

@@ -13,6 +13,7 @@
 #include "split_finish.h"
 #include "gather_gemm.h"
 #include "conv_plan.h"
+#include "launchers.h"
 #include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
@@ -870,25 +871,6 @@ int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N
   return SRGAN_OK;
 }
 
-bool conv3x3_enabled();
-int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, int32_t w_so, int32_t w_si, int32_t w_skh,
-                int32_t w_skw, const float* bias, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t H,
-                int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
-                const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const struct Conv3Placement* placement = nullptr);
-struct Conv3Placement { int32_t taps, out_plane, out_sy, out_sx, out_off; };
-bool conv3x3_epilogue_supported(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
-int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
-int64_t pointwise_epilogue_tiles(int32_t N, int32_t HW);
-int bn_partial_reduce_batched_run(const void* jobs, int count, int max_channels, int max_tiles, const float* scratch,
-                                  hipStream_t stream);
-
-bool pointwise_enabled();
-int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, int32_t w_si, const float* bias, float* out,
-                  int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t HW, int accumulate, hipStream_t stream,
-                  const float* const* bn = nullptr, const BnBackwardEpilogue* epilogue = nullptr,
-                  int* plan_only_split = nullptr);
-int conv3x3_splits(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W, int precision = 0);
-
 // 1x1 / stride 1 / unpadded: the register-streamed pointwise kernel (any plane size: an image's last 32-pixel group may
 // be ragged; planes of fewer than 32 pixels stay on the generic kernel).
 static bool use_pointwise(const ConvGeom& g, int out_channels, int force) {
@@ -919,20 +901,6 @@ static bool use_conv3x3_mixed(const ConvGeom& g, int out_channels) {
   return (g.H == 4 && g.W == 4 && out_channels >= 8) || (g.W >= min_width && out_channels >= 1);
 }
 
-bool stem7x7_enabled();
-bool stem7x7_geometry(int32_t C, int32_t K, int32_t R, int32_t S, int32_t sh, int32_t sw, int32_t ph, int32_t pw);
-int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int64_t y_bs, int32_t N, int32_t H, int32_t W,
-                    int32_t K, int32_t OH, int32_t OW, hipStream_t stream);
-int stem7x7_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, float* gw, int32_t N, int32_t H, int32_t W,
-                      int32_t K, int32_t OH, int32_t OW, int accumulate, hipStream_t stream);
-
-int stem7x7_bwd_data_run(const float* gy, int64_t gy_bs, const float* w, float* gx, int64_t gx_bs, int32_t N, int32_t H,
-                         int32_t W, int32_t K, int32_t OH, int32_t OW, hipStream_t stream);
-bool conv3x3_wgrad_enabled();
-int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, float* gw, int32_t N, int32_t CI,
-                      int32_t CO, int32_t H, int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
-                      int precision = 0);
-
 // Weight gradient of a 3x3 / stride 1 / pad 1 convolution with at least one wave's worth of input channels: the
 // LDS-patch kernel of conv3x3_wgrad.hip.
 // `aligned_only`: widths that are a multiple of 4 with 16-byte aligned rows (the float4 staging; the mixed-precision
@@ -948,28 +916,6 @@ static bool wgrad3x3_geometry(const ConvGeom& g, int min_width = 7, bool aligned
 static bool use_wgrad3x3(const ConvGeom& g, const float* x, const float* gy, int force) {
   return force == 0 && conv3x3_wgrad_enabled() && wgrad3x3_geometry(g);
 }
-
-bool pointwise_ksplit_wanted(int32_t N, int32_t K, int32_t M, int32_t HW, bool fused_bn);
-int pointwise_ksplit_run(const float* in, int64_t in_bs, const float* w, const float* bias, float* out, int64_t out_bs,
-                         int32_t N, int32_t K, int32_t M, int32_t HW, int accumulate, hipStream_t stream,
-                         const float* const* bn);
-
-bool pointwise_wgrad_enabled();
-int pointwise_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, float* gw, int32_t N, int32_t CI,
-                        int32_t CO, int32_t HW, int accumulate, hipStream_t stream, const float* const* bn = nullptr);
-
-int pointwise_wgrad_group_plan(int64_t x_off, int64_t x_bs, int64_t gy_off, int64_t gy_bs, float* gw, int64_t gw_off, int32_t N, int32_t CI,
-                               int32_t CO, int32_t HW, const float* const* bn, int32_t group, int64_t group_weights, int64_t partial_offset,
-                               void* job_out, int32_t* grid_x, int32_t* grid_y, int32_t* ragged, int64_t* partial_floats);
-int pointwise_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, int32_t grid_y, int32_t ragged, int32_t fused_bn,
-                              const float* x_base, const float* gy_base, float* gw_base, int64_t flops_mn, int64_t pixels,
-                              int64_t elements, int64_t partial_floats, hipStream_t stream);
-int conv3x3_wgrad_group_plan(int64_t x_off, int64_t x_bs, int64_t gy_off, int64_t gy_bs, float* gw, int64_t gw_off, int32_t N, int32_t CI,
-                             int32_t CO, int32_t H, int32_t W, const float* const* bn, int32_t group, int64_t partial_offset, void* job_out,
-                             int32_t* grid_x, int32_t* grid_y, int32_t* ragged, int64_t* partial_floats);
-int conv3x3_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, int32_t grid_y, int32_t ragged,
-                            const float* x_base, const float* gy_base, float* gw_base, int64_t flops_mn, int64_t pixels,
-                            int64_t elements, int64_t partial_floats, hipStream_t stream);
 
 static bool pointwise_wgrad_geometry(const ConvGeom& g) {
   static const bool no_ragged = getenv("SRGAN_PWG_NO_RAGGED") != nullptr;
@@ -1072,14 +1018,6 @@ int gg_run_group(std::vector<GatherGemm>& plans, float* c_base, int64_t c_elems,
 using namespace srgan;
 
 extern "C" {
-
-int srgan_split_is_ordered(void* stream);
-
-struct srgan_conv_desc {
-  int32_t N, C, H, W, K, R, S, stride_h, stride_w, pad_h, pad_w, OH, OW;
-  int64_t x_batch_stride, y_batch_stride;
-  int32_t compute_dtype;      // 0 fp32, 1 bf16, 2 fp16 MFMA operands (fp32 data and accumulation)
-};
 
 static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
 
@@ -1221,8 +1159,6 @@ int srgan_conv2d_bwd_weight(const srgan_conv_desc* desc, const float* x, const f
 }
 
 // ---- convolutions whose input is relu(batch_norm_eval(x)) evaluated on the fly (DenseNet norm -> relu -> conv)
-struct srgan_bn_relu { const float* mean; const float* inv_std; const float* gamma; const float* beta; };
-
 static bool bn_ok(const srgan_bn_relu* bn) { return bn && bn->mean && bn->inv_std && bn->gamma && bn->beta; }
 
 int srgan_conv2d_bnrelu_supported(const srgan_conv_desc* desc, int pass) {
@@ -1322,8 +1258,6 @@ int srgan_conv2d_bwd_data_bnrelu_partials(const srgan_conv_desc* desc, const flo
   SRGAN_REQUIRE(partials != nullptr, SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu_partials: the partial-sum region");
   return bwd_data_bnrelu(desc, gy, w, bn, x, gx, nullptr, nullptr, partials, accumulate, stream);
 }
-
-struct srgan_bn_reduce_job { int64_t partial_offset; int32_t tiles, channels; const float* inv_std; float* g_gamma; float* g_beta; };
 
 int srgan_bn_partial_reduce_batched(const srgan_bn_reduce_job* jobs_device, int32_t count, int32_t max_channels, int32_t max_tiles,
                                     const float* scratch, void* stream) {
@@ -1485,36 +1419,20 @@ int srgan_split_is_ordered(void* stream) {
   return set >= 0 && set < SPLIT_TICKET_SETS ? 1 : 0;
 }
 
-struct srgan_capabilities_t {
-  int32_t abi_version;         // = srgan_version()
-  int32_t struct_bytes;        // sizeof(this struct) as the library knows it
-  char arch[16];               // "gfx950"
-  uint32_t dtypes;             // bit 0: fp32 (the parity path)
-  uint32_t features;           // SRGAN_FEATURE_* bits
-  int64_t workspace_bytes;     // = srgan_workspace_bytes()
-  int64_t max_tensor_elements; // 2^31 - 1
-};
-
 int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
   SRGAN_REQUIRE(out != nullptr && out_bytes >= (int32_t)sizeof(srgan_capabilities_t), SRGAN_EINVAL,
                 "srgan_capabilities: output struct");
   memset(out, 0, sizeof(*out));
-  out->abi_version = 110;
+  out->abi_version = srgan_version();
   out->struct_bytes = (int32_t)sizeof(*out);
   snprintf(out->arch, sizeof(out->arch), "gfx950");
-  out->dtypes = 0x1u /* fp32 */ | 0x2u /* bf16 MFMA operands */ | 0x4u /* fp16 MFMA operands */;
-  out->features = 0x1u /* fused batch-norm + relu prologues / epilogues */ | 0x2u /* split-K through a workspace */ |
-                  0x4u /* live event profile of the contraction launches */ |
-                  0x8u /* 16-bit blocked data path (srgan_h_*) */ |
-                  0x10u /* every weight-shadow kind as a job of srgan_h_pack_batched */;
+  out->dtypes = SRGAN_DTYPE_F32 | SRGAN_DTYPE_BF16 | SRGAN_DTYPE_F16;
+  out->features = SRGAN_FEATURE_FUSED_BNRELU | SRGAN_FEATURE_SPLITK_WORKSPACE | SRGAN_FEATURE_LIVE_PROFILE |
+                  SRGAN_FEATURE_BLOCKED16 | SRGAN_FEATURE_BATCHED_SHADOWS;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;
 }
-
-int srgan_gemm(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int64_t sak, const float* B,
-               int64_t sbk, int64_t sbj, float* C, int64_t sci, int64_t scj, const float* bias,
-               int32_t bias_on_columns, int accumulate, int force_kernel, int compute_dtype, void* stream);
 
 int srgan_gemm_f32(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int64_t sak, const float* B,
                    int64_t sbk, int64_t sbj, float* C, int64_t sci, int64_t scj, const float* bias,

@@ -19,6 +19,7 @@
 //     half-wave); in a data gradient the batch-norm + ReLU backward of the layer in front is applied on the way (EPI).
 // Roofline: fp32 MFMA 157.3 TF/s, or HBM when CI is small; algorithmic bytes 4 * (CI + CO) per pixel.
 #include "common.h"
+#include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -475,18 +476,6 @@ __global__ __launch_bounds__(256) void bn_partial_reduce_kernel(const float* __r
   bn_partial_reduce_body<ORDERED>(partial, cols, CO, inv_std, g_gamma, g_beta, first, last, (int)blockIdx.x, scratch);
 }
 
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
-float* partial_workspace(size_t bytes, hipStream_t stream);
-bool pointwise_ring_eligible(const float* in, int64_t in_bs, const float* w, int32_t w_so, int32_t w_si, const float* bias,
-                             const float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t HW, bool fused_pro,
-                             const BnBackwardEpilogue* epilogue, int* tile_pixels);
-int pointwise_ring_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, int32_t w_si, float* out, int64_t out_bs,
-                       int32_t N, int32_t CI, int32_t CO, int32_t HW, int accumulate, hipStream_t stream,
-                       const float* const* bn, const BnBackwardEpilogue* epilogue, float* epi_partial, int32_t epi_cols,
-                       int tile_pixels, int32_t* rows_done);
-
 // g_beta[c] += sum_t partial[0][t][c];  g_gamma[c] += inv_std[c] * sum_t partial[1][t][c]   (t = workgroup tiles)
 void bn_partial_reduce_run(const float* partial, int tiles, int CO, const float* inv_std, float* g_gamma, float* g_beta,
                            hipStream_t stream) {
@@ -505,14 +494,13 @@ void bn_partial_reduce_run(const float* partial, int tiles, int CO, const float*
 // One launch for the deferred parameter sums of MANY convolutions (a dense block's backward: two per layer): job z of
 // the table reduces partial[q][tile][c] (q = 0 beta, 1 gamma before inv_std; at scratch + partial_offset) like the kernel
 // above.  The table lives in device memory and is built once per block by the caller (the offsets into the scratch
-// region and the arena pointers do not change between steps).
-struct BnReduceJob { int64_t partial_offset; int32_t tiles, channels; const float* inv_std; float* g_gamma; float* g_beta; };
+// region and the arena pointers do not change between steps).  A job is the ABI's srgan_bn_reduce_job.
 
 template <bool ORDERED>
-__global__ __launch_bounds__(256) void bn_partial_reduce_batched_kernel(const BnReduceJob* __restrict__ jobs,
+__global__ __launch_bounds__(256) void bn_partial_reduce_batched_kernel(const srgan_bn_reduce_job* __restrict__ jobs,
                                                                         const float* __restrict__ scratch) {
   __shared__ float buffer[2][256];
-  const BnReduceJob job = jobs[blockIdx.z];
+  const srgan_bn_reduce_job job = jobs[blockIdx.z];
   int first = 0, last = job.tiles;
   if (!ORDERED) {
     int segments = job.tiles / 32;
@@ -526,17 +514,17 @@ __global__ __launch_bounds__(256) void bn_partial_reduce_batched_kernel(const Bn
                                   first, last, (int)blockIdx.x, buffer);
 }
 
-int bn_partial_reduce_batched_run(const void* jobs, int count, int max_channels, int max_tiles, const float* scratch,
-                                  hipStream_t stream) {
+int bn_partial_reduce_batched_run(const srgan_bn_reduce_job* jobs, int count, int max_channels, int max_tiles,
+                                  const float* scratch, hipStream_t stream) {
   if (!split_atomics_forced()) {
     hipLaunchKernelGGL(bn_partial_reduce_batched_kernel<true>, dim3((max_channels + 15) / 16, 1, count), dim3(256), 0, stream,
-                       reinterpret_cast<const BnReduceJob*>(jobs), scratch);
+                       jobs, scratch);
     return launch_status();
   }
   int segments = max_tiles / 32;
   segments = segments < 1 ? 1 : (segments > 64 ? 64 : segments);
   hipLaunchKernelGGL(bn_partial_reduce_batched_kernel<false>, dim3((max_channels + 63) / 64, segments, count), dim3(256), 0, stream,
-                     reinterpret_cast<const BnReduceJob*>(jobs), scratch);
+                     jobs, scratch);
   return launch_status();
 }
 

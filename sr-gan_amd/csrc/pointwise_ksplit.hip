@@ -12,6 +12,7 @@
 // the next chunk is in flight while the current one is in the matrix pipe.  The four partial tiles are summed through
 // LDS at the end.  No memset, no atomics, the activations are read twice (once per 64-row tile of 128 rows).
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
 namespace srgan {
@@ -141,10 +142,6 @@ __global__ __launch_bounds__(256, 2) void pointwise_ksplit_kernel(const PwKsplit
     else __builtin_nontemporal_store(v, dst);
   }
 }
-
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
 
 bool pointwise_ksplit_enabled() {
   static const bool disabled = getenv("SRGAN_NO_PW_KSPLIT") != nullptr;

@@ -27,6 +27,7 @@
 // gradient).
 #include <atomic>
 #include "common.h"
+#include "launchers.h"
 #include "lds_dma.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -373,10 +374,6 @@ bool pointwise_ring_eligible(const float* in, int64_t in_bs, const float* w, int
   *tile_pixels = pixels;
   return true;
 }
-
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
 
 template <int NI, bool A_KCONTIG, int FUSE>
 static int launch_ring(const RingParams& p, unsigned blocks, hipStream_t stream) {

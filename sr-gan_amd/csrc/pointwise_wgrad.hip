@@ -27,6 +27,7 @@
 // chunk and row block); rows are 128 bytes = half a 256-byte bank row, 16-byte slots XOR-swizzled by the bank-row index
 // (applied to the DMA's source addresses, as in pointwise_ring.hip) -- conflict-free.
 #include "common.h"
+#include "launchers.h"
 #include "lds_dma.h"
 #include "split_finish.h"
 #include <atomic>
@@ -500,10 +501,6 @@ __global__ __launch_bounds__(256) void pointwise_wgrad_grouped_finish_kernel(con
   pointwise_wgrad_finish_tile<TILE, TILE, TILE == PWL_TILE>(partial_base + job.partial_off, gw, (int)blockIdx.y, (int)blockIdx.x, job.split, job.tiles_n,
                                           job.CO, job.CI);
 }
-
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
 
 // The un-fused weight gradient stays on the generic gather-GEMM by default (measured equal: both are bound by the
 // operand stream at 64 x 64 tiles); this kernel serves the fused batch-norm form, where the generic one cannot.

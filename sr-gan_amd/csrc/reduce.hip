@@ -11,9 +11,6 @@
 
 namespace srgan {
 
-float* partial_workspace(size_t bytes, hipStream_t stream);     // gather_gemm_kernels.hip: the caller's per-stream workspace
-int workspace_index(hipStream_t stream);                         // its small integer id (-1: none registered)
-
 constexpr int RED_SEG = 256 * 16;   // smallest run of one row handled by one workgroup (a multiple of 1024 elements)
 
 // out[c] += scale[c] * sum over rows r = n*C + c, i in [0, HW) of a[r, i] * ((b ? b[r, i] : 1) - mean[c])

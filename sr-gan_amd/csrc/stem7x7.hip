@@ -14,6 +14,7 @@
 //             atomic pass per workgroup.
 // Roofline: fp32 MFMA (157.3 TF/s): 2 * 147 * 64 FLOP per output pixel, against 4 * (3 * 4 + 64) B of HBM traffic.
 #include "common.h"
+#include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 
@@ -380,10 +381,6 @@ __global__ __launch_bounds__(256, 2) void stem7x7_bwd_data_kernel(const StemPara
       }
     }
 }
-
-int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn,
-                        int split, int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
 
 bool stem7x7_enabled() {
   static const bool disabled = getenv("SRGAN_NO_STEM") != nullptr;

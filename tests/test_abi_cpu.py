@@ -1,6 +1,6 @@
 """The C-ABI library on the CPU (no GPU, no compute calls): it loads, exports every entry point include/srgan_hip.h
-declares (and the ctypes table binds exactly those), reports its capabilities, refuses a stale build, and rejects bad
-arguments before touching a device."""
+declares (and the ctypes table binds exactly those, with the header's argument and field types), reports its
+capabilities, refuses a stale build, and rejects bad arguments before touching a device."""
 import ctypes
 import os
 import re
@@ -12,9 +12,59 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'srgan_hip.h')
 
 
+def header_code():
+    """include/srgan_hip.h without comments and preprocessor lines (a `#define` or `#endif` is not a return type)."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', '', open(HEADER).read(), flags=re.DOTALL)
+    return re.sub(r'^\s*#[^\n]*', '', text, flags=re.MULTILINE)
+
+
+def header_structs():
+    """{struct name: [(field, class)]} of the header's typedef'd structs; an array field's class is e.g. 'char[16]'."""
+    structs = {}
+    for name, body in re.findall(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\w+\s*;', header_code(), flags=re.DOTALL):
+        fields = structs[name] = []
+        for declaration in body.split(';')[:-1]:
+            c_type, names = re.fullmatch(r'\s*(.+?[\s*])(\w+(?:\[\d+\])?(?:\s*,\s*\w+)*)\s*', declaration).groups()
+            for field in names.split(','):
+                array = re.fullmatch(r'\s*(\w+)\[(\d+)\]', field)
+                fields.append((array[1], '%s[%s]' % (c_type.strip(), array[2])) if array else (field.strip(), c_class(c_type)))
+    return structs
+
+
+def header_prototypes():
+    """{entry point: (C return type, [C argument types])} of every function the header declares."""
+    code = re.sub(r'typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;', '', header_code(), flags=re.DOTALL)
+    code = re.sub(r'extern\s+"C"\s*\{|\}', '', code)
+    prototypes = {}
+    for statement in code.split(';'):
+        match = re.fullmatch(r'\s*(.*?[\s*])(srgan_\w+)\s*\((.*)\)\s*', statement, flags=re.DOTALL)
+        if match:
+            arguments = [' '.join(a.split()) for a in match.group(3).split(',')]
+            arguments = [re.sub(r'\s*\b\w+$', '', a) if re.search(r'[\w*]\s+\w+$', a) else a for a in arguments]
+            prototypes[match.group(2)] = (' '.join(match.group(1).split()), [] if arguments == ['void'] else arguments)
+    return prototypes
+
+
 def declared_entry_points():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.DOTALL)
-    return sorted(set(re.findall(r'\b(srgan_[a-z0-9_]+)\s*\(', text)))
+    return sorted(header_prototypes())
+
+
+def c_class(c_type):
+    """pointer / i32 / i64 / f32 / f64 of a C type from the header (signedness is not compared)."""
+    if '*' in c_type:
+        return 'pointer'
+    c_type = c_type.replace('const ', '').strip()
+    classes = {'int': 'i32', 'int32_t': 'i32', 'uint32_t': 'i32', 'int64_t': 'i64', 'float': 'f32', 'double': 'f64'}
+    return classes[c_type]
+
+
+def ctypes_class(c_type):
+    if c_type in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(c_type, ctypes._Pointer):
+        return 'pointer'
+    if c_type in (ctypes.c_float, ctypes.c_double):
+        return 'f%d' % (8 * ctypes.sizeof(c_type))
+    assert issubclass(c_type, ctypes._SimpleCData) and c_type._type_ in 'bBhHiIlLqQ', c_type
+    return 'i%d' % (8 * ctypes.sizeof(c_type))
 
 
 @pytest.fixture(scope='module')
@@ -35,6 +85,35 @@ def test_every_declared_entry_point_is_exported_and_bound(lib):
     library = lib.library()
     for name in declared:
         assert getattr(library, name) is not None
+
+
+def test_the_ctypes_table_matches_the_header_prototypes(lib):
+    """Every SIGNATURES entry has the header's argument count, argument classes and return class; a pointer to one of the
+    mirrored structs points to the struct the header names."""
+    prototypes = header_prototypes()
+    assert len(prototypes) == len(set(re.findall(r'\b(srgan_\w+)\s*\(', header_code())))       # no declaration skipped
+    mirrors = {lib.ConvDesc: 'srgan_conv_desc', lib.BnRelu: 'srgan_bn_relu', lib.BnReduceJob: 'srgan_bn_reduce_job',
+               lib.Capabilities: 'srgan_capabilities_t'}
+    for name, (argtypes, restype) in lib.SIGNATURES.items():
+        c_return, c_arguments = prototypes[name]
+        assert len(argtypes) == len(c_arguments), (name, len(argtypes), c_arguments)
+        for position, (binding, declared) in enumerate(zip(argtypes, c_arguments)):
+            assert ctypes_class(binding) == c_class(declared), (name, position, binding, declared)
+            if getattr(binding, '_type_', None) in mirrors:
+                assert re.sub(r'\bconst\s+|\s*\*$', '', declared) == mirrors[binding._type_], (name, position, declared)
+        assert ctypes_class(restype) == c_class(c_return), (name, restype, c_return)
+
+
+def test_the_struct_mirrors_match_the_header(lib):
+    """Field names, order and widths of the ctypes.Structure mirrors against the header's structs."""
+    structs = header_structs()
+    mirrors = {'srgan_conv_desc': lib.ConvDesc, 'srgan_bn_relu': lib.BnRelu, 'srgan_bn_reduce_job': lib.BnReduceJob,
+               'srgan_capabilities_t': lib.Capabilities}
+    assert sorted(structs) == sorted(mirrors)
+    for name, mirror in mirrors.items():
+        bound = [(field, 'char[%d]' % ctypes.sizeof(t) if issubclass(t, ctypes.Array) else ctypes_class(t))
+                 for field, t in mirror._fields_]
+        assert bound == structs[name], (name, bound, structs[name])
 
 
 def test_capabilities_and_build_identity(lib):
