@@ -1255,7 +1255,10 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
     int launched;
     if (ring == 3) launched = dtype == 1 ? hconv3_dma_launch<1, 3>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 3>(p, plan, grid, s, zero);
     else launched = dtype == 1 ? hconv3_dma_launch<1, 2>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 2>(p, plan, grid, s, zero);
-    if (launched != SRGAN_OK) return launched;
+    if (launched != SRGAN_OK) {
+      profile_bracket_end(slot, s, 0, 0, 0, 14, plan.bm, plan.ni * 128, split);      // close the bracket this call opened
+      return launched;
+    }
   }
   else if (dtype == 1) hconv3_launch<1>(p, plan, grid, s);
   else hconv3_launch<2>(p, plan, grid, s);

@@ -1,4 +1,5 @@
-"""Shared helpers for the test-suite (golden loading, tolerances)."""
+"""Shared helpers for the test-suite (golden loading, tolerances, the contraction profile report)."""
+import ctypes
 import os
 from types import SimpleNamespace
 
@@ -62,3 +63,48 @@ def assert_close_norm(actual, expected, rtol=1e-3, what=''):
     denom = max(np.abs(expected).max(), 1e-30)
     err = np.abs(actual - expected).max() / denom
     assert err <= rtol, f'{what}: max err / max|expected| = {err:.3e} > {rtol}'
+
+
+def _check(status, what):
+    from srgan_amd import _lib
+    _lib.check(status, what)
+
+
+class profiled:
+    """srgan_profile_begin ... srgan_profile_end around a block; .lines = the report's (M, N, K, kind, bm, bn, split) rows."""
+
+    def __init__(self, lib):
+        self.lib, self.lines, self.text = lib, [], ''
+
+    def __enter__(self):
+        _check(self.lib.srgan_profile_begin(), 'srgan_profile_begin')
+        return self
+
+    def __exit__(self, kind, *rest):
+        ms, flops, mfma, launches = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+        _check(self.lib.srgan_profile_end(ctypes.byref(ms), ctypes.byref(flops), ctypes.byref(mfma), ctypes.byref(launches)),
+               'srgan_profile_end')
+        size = self.lib.srgan_profile_report(None, 0)
+        buffer = ctypes.create_string_buffer(int(size) + 1)
+        self.lib.srgan_profile_report(buffer, size + 1)
+        self.text = buffer.value.decode()
+        for line in self.text.splitlines():
+            fields = line.split()
+            if len(fields) >= 7 and not line.startswith('#'):
+                self.lines.append(tuple(int(v) for v in fields[:7]))
+        return False
+
+    @property
+    def kinds(self):
+        return {line[3] for line in self.lines}
+
+    def assert_reached(self, reach, split, what):
+        from contraction_cases import KINDS, KINDS16
+        names = {**KINDS, **KINDS16}
+        missing = sorted(set(reach) - self.kinds)
+        assert not missing, (f'{what}: declared kinds {[names[k] for k in missing]} not launched; launched '
+                             f'{ {k: names.get(k, str(k)) for k in self.kinds} }\n'
+                             f'M N K kind bm bn split ...\n{self.text}')
+        if split:
+            assert any(line[3] in reach and line[6] > 1 for line in self.lines), \
+                f'{what}: no launch of {sorted(reach)} with split > 1\nM N K kind bm bn split ...\n{self.text}'

@@ -114,16 +114,18 @@ def test_conv3x3_forward_data_gradient_and_weight_gradient_are_exact_on_integers
         assert torch.equal(got, rounded(plain * torch.where(ref > 0, 1.0, 0.5), mode))
         assert torch.equal(nchw(B, B._layer(sb, layer, shadow, True, 0, 1.0, None, False)), rounded(plain, mode))
         # weight gradient (fp32, accumulated into): exact integers
-        into = torch.full((k, c, 3, 3), 7.0, device='cuda')
+        old = integers((k, c, 3, 3), -64, 64, 6)                       # distinct old values: an epilogue must read its own
+        into = old.clone()
         B._weight_gradient(shadow, layer, xb, sb, into)
-        want = F.conv2d_backward_weight(F.leaf(x), F.leaf(s), (k, c, 3, 3), (1, 1), (1, 1)).data + 7.0
+        want = F.conv2d_backward_weight(F.leaf(x), F.leaf(s), (k, c, 3, 3), (1, 1), (1, 1)).data + old
         assert torch.equal(into, want)
         # bias gradient
-        sums = torch.full((k,), 1.0, device='cuda')
+        old = integers((k,), -64, 64, 7)
+        sums = old.clone()
         from srgan_amd import _lib
         _lib.check(_lib.library().srgan_h_channel_sums(sb.data.data_ptr(), sums.data_ptr(), n, k, h * w, B.CODES[mode], F._stream()),
                    'srgan_h_channel_sums')
-        assert torch.equal(sums, s.sum(dim=(0, 2, 3)) + 1.0)
+        assert torch.equal(sums, s.sum(dim=(0, 2, 3)) + old)
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -197,9 +199,10 @@ def test_linear_layers_behind_a_flattened_plane_are_exact_on_integers(F, B, mode
         back = gx.data.view(n, (c + 7) // 8, h, w, 8)
         unblocked = back.permute(0, 1, 4, 2, 3).reshape(n, -1, h, w)[:, :c].float()
         assert torch.equal(unblocked, rounded((s @ layer.weight.data).view(n, c, h, w), mode))
-        into = torch.full_like(layer.weight.data, 3.0)
+        old = integers(tuple(layer.weight.shape), -64, 64, 5)
+        into = old.clone()
         B._weight_gradient(shadow, layer, flat, sb, into)
-        assert torch.equal(into, s.t() @ x.view(n, -1) + 3.0)
+        assert torch.equal(into, s.t() @ x.view(n, -1) + old)
 
 
 def _vgg(size, scale):
@@ -394,9 +397,10 @@ def test_4x4_stride_2_family_is_exact_on_integers(F, B, mode, case):
         refb = blocked(F, B, ref, mode)
         want = F.conv2d_backward_data(F.leaf(small), F.leaf(conv.weight.data), (n, b, h, w), (2, 2), (1, 1)).data
         assert torch.equal(nchw(B, B._layer(smallb, conv, shadow, True, 2, 0.5, refb.data, False)), rounded(want * torch.where(ref > 0, 1.0, 0.5), mode))
-        into = torch.full_like(conv.weight.data, 5.0)
+        old = integers(tuple(conv.weight.shape), -64, 64, 7)
+        into = old.clone()
         B._weight_gradient(shadow, conv, bigb, smallb, into)
-        assert torch.equal(into, F.conv2d_backward_weight(F.leaf(big), F.leaf(small), tuple(conv.weight.shape), (2, 2), (1, 1)).data + 5.0)
+        assert torch.equal(into, F.conv2d_backward_weight(F.leaf(big), F.leaf(small), tuple(conv.weight.shape), (2, 2), (1, 1)).data + old)
         # transposed convolution: forward, its data gradient (masked), its weight gradient
         want = F.conv_transpose2d(F.leaf(small), F.leaf(deconv.weight.data), F.leaf(deconv.bias.data), 2, 1).data
         assert torch.equal(nchw(B, B.conv_transpose4x4s2(smallb, deconv, slope=0.25)), rounded(leaky(want, 0.25), mode))
@@ -405,10 +409,11 @@ def test_4x4_stride_2_family_is_exact_on_integers(F, B, mode, case):
         want = F.conv2d(F.leaf(big), F.leaf(deconv.weight.data), None, 2, 1).data          # d convT / d input = the strided conv
         got = nchw(B, B._layer(bigb, deconv, shadow_t, True, 2, 0.5, blocked(F, B, ref_small, mode).data, False))
         assert torch.equal(got, rounded(want * torch.where(ref_small > 0, 1.0, 0.5), mode))
-        into = torch.full_like(deconv.weight.data, -2.0)
+        old = integers(tuple(deconv.weight.shape), -64, 64, 8)
+        into = old.clone()
         B._weight_gradient(shadow_t, deconv, smallb, bigb, into)
         want = F.conv2d_backward_weight(F.leaf(big), F.leaf(small), tuple(deconv.weight.shape), (2, 2), (1, 1)).data
-        assert torch.equal(into, want - 2.0)
+        assert torch.equal(into, want + old)
 
 
 @pytest.mark.parametrize('mode', MODES)
@@ -430,9 +435,10 @@ def test_seed_transposed_convolution_is_exact_on_integers(F, B, mode, case):
         shadow = B.shadow_of(layer, 'linear_t', B.CODES[mode])
         back = B._layer(gb, layer, shadow, True, 0, 1.0, None, False)
         assert torch.equal(B.unpack(back).data, rounded(torch.einsum('ncrs,kcrs->nk', g, layer.weight.data), mode))
-        into = torch.full_like(layer.weight.data, 1.0)
+        old = integers(tuple(layer.weight.shape), -64, 64, 5)
+        into = old.clone()
         B._weight_gradient(shadow, layer, zb, gb, into)
-        assert torch.equal(into, torch.einsum('nk,ncrs->kcrs', z, g) + 1.0)
+        assert torch.equal(into, torch.einsum('nk,ncrs->kcrs', z, g) + old)
 
 
 def _dcgan_pass(F, size, storage, mode, second_order, conv_dim=32):
@@ -530,3 +536,190 @@ def test_blocked_fp32_stages_in_a_crowd_step_match_the_goldens(F, name, steps):
     import srgan_amd
     import test_steps_gpu as reference_tests
     reference_tests.test_crowd_steps(srgan_amd, name, 64, steps, False, extra_settings=dict(blocked_fp32=True))
+
+
+# ------------------------------------------------------------------------------------------------- epilogue rounding
+# Operands exact in bf16 and fp16 (x integers in [-3, 3], weights k / 8 with |k| <= 16; fp32 biases, integers up to 1024 so that
+# the forward results need more than fp16's 11 bits even on three input channels) whose results carry more significand bits
+# than either type holds: most outputs of the 16-bit kernels are then a rounding, and each must equal the float64
+# result rounded once to nearest even (torch's conversion) -- the reference is computed on the CPU in float64, not by the fp32
+# kernels.  All partial sums stay below 2^21 (three fractional bits), so the fp32 accumulation itself is exact.
+def eighths(shape, seed):
+    return integers(shape, -16, 16, seed) / 8.0
+
+
+def round16(t, mode):
+    """float64 / float32 -> the 16-bit type (round to nearest even) -> float32 on the device."""
+    return t.to(TORCH[mode]).float().cuda()
+
+
+def leaky_reference(s, slope):
+    """What a kernel computes for leaky_relu(s) in fp32 with the slope as an fp32 number: exact for slope 0.5 and 0,
+    round32(s * float32(0.2)) for the product's 0.2."""
+    s32 = s.float()
+    return torch.where(s32 > 0, s32, s32 * torch.tensor(slope, dtype=torch.float32))
+
+
+def assert_below_2_21(magnitude, what):
+    assert magnitude < 2 ** 21, f'{what}: partial sums reach {magnitude:g}: the case is broken'
+
+
+def _rounding_report(F):
+    from helpers import profiled
+    from srgan_amd import _lib
+    return profiled(_lib.library())
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', CONVS)
+def test_conv3x3_epilogues_round_to_nearest_even(F, B, mode, case):
+    """srgan_h_conv3x3: forward with the plain / bias + ReLU / leaky (0.5, 0.2) epilogues, data gradient plain and with the mask
+    by reference at slope 0.5; then the weight gradient (hwgrad3x3, exact fp32 accumulated onto random integers)."""
+    n, c, h, w, k = case
+    layer = torch.nn.Conv2d(c, k, 3, padding=1).cuda()
+    with torch.no_grad():
+        layer.weight.copy_(eighths((k, c, 3, 3), 11))
+        layer.bias.copy_(integers((k,), -1024, 1024, 12))
+    x = integers((n, c, h, w), -3, 3, 13)
+    s = integers((n, k, h, w), -3, 3, 14)
+    ref = integers((n, c, h, w), -1, 1, 15)
+    x64, s64, w64, b64 = (t.double().cpu() for t in (x, s, layer.weight.data, layer.bias.data))
+    plain = torch.nn.functional.conv2d(x64, w64, b64, padding=1)
+    back = torch.nn.grad.conv2d_input(x64.shape, w64, s64, 1, 1)
+    assert_below_2_21(max(float(torch.nn.functional.conv2d(x64.abs(), w64.abs(), b64.abs(), padding=1).max()),
+                          float(torch.nn.grad.conv2d_input(x64.shape, w64.abs(), s64.abs(), 1, 1).max())), f'{case}')
+    assert (plain.to(TORCH[mode]).double() != plain).float().mean() > 0.25, 'the outputs must need rounding for the test to bind'
+    from srgan_amd.tape import no_grad
+    with no_grad(), _rounding_report(F) as report:
+        xb = blocked(F, B, x, mode)
+        assert torch.equal(nchw(B, B.conv3x3(xb, layer)), round16(plain, mode))
+        assert torch.equal(nchw(B, B.conv3x3(xb, layer, slope=0.0)), round16(plain.relu(), mode))
+        assert torch.equal(nchw(B, B.conv3x3(xb, layer, slope=0.5)), round16(torch.where(plain > 0, plain, plain * 0.5), mode))
+        assert torch.equal(nchw(B, B.conv3x3(xb, layer, slope=0.2)), round16(leaky_reference(plain, 0.2), mode))
+        sb, refb = blocked(F, B, s, mode), blocked(F, B, ref, mode)
+        shadow = B.shadow_of(layer, 'conv3x3', B.CODES[mode])
+        assert torch.equal(nchw(B, B._layer(sb, layer, shadow, True, 0, 1.0, None, False)), round16(back, mode))
+        masked = back * torch.where(ref.cpu() > 0, 1.0, 0.5).double()
+        assert torch.equal(nchw(B, B._layer(sb, layer, shadow, True, 2, 0.5, refb.data, False)), round16(masked, mode))
+        old = integers((k, c, 3, 3), -64, 64, 16)
+        into = old.clone()
+        B._weight_gradient(shadow, layer, xb, sb, into)
+        assert torch.equal(into.cpu().double(), torch.nn.grad.conv2d_weight(x64, (k, c, 3, 3), s64, 1, 1) + old.cpu().double())
+    report.assert_reached({14, 15}, False, f'{case} {mode}')
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', LINEARS)
+def test_gemm_epilogues_round_to_nearest_even(F, B, mode, case):
+    """srgan_h_gemm (a linear layer behind a flattened plane): plain, bias + ReLU and leaky 0.2; the data gradient plain."""
+    n, c, h, w, outputs = case
+    inputs = c * h * w
+    layer = torch.nn.Linear(inputs, outputs).cuda()
+    with torch.no_grad():
+        layer.weight.copy_(eighths((outputs, inputs), 21))
+        layer.bias.copy_(integers((outputs,), -1024, 1024, 22))
+    x = integers((n, c, h, w), -3, 3, 23)
+    s = integers((n, outputs), -3, 3, 24)
+    x64, s64, w64, b64 = (t.double().cpu() for t in (x, s, layer.weight.data, layer.bias.data))
+    want = torch.nn.functional.linear(x64.view(n, -1), w64, b64)
+    assert_below_2_21(max(float((x64.view(n, -1).abs() @ w64.abs().t()).max()) + 1024, float((s64.abs() @ w64.abs()).max())), f'{case}')
+    from srgan_amd.tape import no_grad
+    with no_grad(), _rounding_report(F) as report:
+        flat = B.flatten(blocked(F, B, x, mode))
+        assert torch.equal(B.unpack(B.linear(flat, layer)).data, round16(want, mode))
+        assert torch.equal(B.unpack(B.linear(flat, layer, slope=0.0)).data, round16(want.relu(), mode))
+        assert torch.equal(B.unpack(B.linear(flat, layer, slope=0.2)).data, round16(leaky_reference(want, 0.2), mode))
+        sb = blocked(F, B, s, mode)
+        shadow = B.shadow_of(layer, 'linear', B.CODES[mode], in_blocked=flat.meta.c, plane=flat.meta.plane)
+        gx = B._layer(sb, layer, shadow, True, 0, 1.0, None, False)
+        back = gx.data.view(n, (c + 7) // 8, h, w, 8).permute(0, 1, 4, 2, 3).reshape(n, -1, h, w)[:, :c].float()
+        assert torch.equal(back, round16((s64 @ w64).view(n, c, h, w), mode))
+        old = integers((outputs, inputs), -64, 64, 25)
+        into = old.clone()
+        B._weight_gradient(shadow, layer, flat, sb, into)
+        assert torch.equal(into.cpu().double(), s64.t() @ x64.view(n, -1) + old.cpu().double())
+    report.assert_reached({16, 17}, False, f'{case} {mode}')
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', K4S2)
+def test_4x4_stride_2_epilogues_round_to_nearest_even(F, B, mode, case):
+    """srgan_h_conv4x4s2 / srgan_h_conv_transpose4x4s2: plain and leaky 0.2 forward of both directions, the strided
+    convolution's data gradient with the mask by reference at slope 0.5."""
+    n, a, b, h, w = case
+    conv = torch.nn.Conv2d(b, a, 4, 2, 1).cuda()
+    deconv = torch.nn.ConvTranspose2d(a, b, 4, 2, 1).cuda()
+    with torch.no_grad():
+        for index, layer in enumerate((conv, deconv)):
+            layer.weight.copy_(eighths(tuple(layer.weight.shape), 31 + index))
+            layer.bias.copy_(integers(tuple(layer.bias.shape), -1024, 1024, 33 + index))
+    big = integers((n, b, h, w), -3, 3, 35)
+    small = integers((n, a, h // 2, w // 2), -3, 3, 36)
+    ref = integers((n, b, h, w), -1, 1, 37)
+    big64, small64 = big.double().cpu(), small.double().cpu()
+    cw, cb = conv.weight.data.double().cpu(), conv.bias.data.double().cpu()
+    dw, db = deconv.weight.data.double().cpu(), deconv.bias.data.double().cpu()
+    down = torch.nn.functional.conv2d(big64, cw, cb, 2, 1)
+    up = torch.nn.functional.conv_transpose2d(small64, dw, db, 2, 1)
+    back = torch.nn.grad.conv2d_input(big64.shape, cw, small64, 2, 1) * torch.where(ref.cpu() > 0, 1.0, 0.5).double()
+    assert_below_2_21(max(float(torch.nn.functional.conv2d(big64.abs(), cw.abs(), cb.abs(), 2, 1).max()),
+                          float(torch.nn.functional.conv_transpose2d(small64.abs(), dw.abs(), db.abs(), 2, 1).max()),
+                          float(torch.nn.grad.conv2d_input(big64.shape, cw.abs(), small64.abs(), 2, 1).max())), f'{case}')
+    from srgan_amd.tape import no_grad
+    with no_grad(), _rounding_report(F) as report:
+        bigb, smallb = blocked(F, B, big, mode), blocked(F, B, small, mode)
+        assert torch.equal(nchw(B, B.conv4x4s2(bigb, conv)), round16(down, mode))
+        assert torch.equal(nchw(B, B.conv4x4s2(bigb, conv, slope=0.2)), round16(leaky_reference(down, 0.2), mode))
+        assert torch.equal(nchw(B, B.conv_transpose4x4s2(smallb, deconv)), round16(up, mode))
+        assert torch.equal(nchw(B, B.conv_transpose4x4s2(smallb, deconv, slope=0.2)), round16(leaky_reference(up, 0.2), mode))
+        shadow = B.shadow_of(conv, 'k4s2', B.CODES[mode])
+        got = nchw(B, B._layer(smallb, conv, shadow, True, 2, 0.5, blocked(F, B, ref, mode).data, False))
+        assert torch.equal(got, round16(back, mode))
+        old = integers(tuple(conv.weight.shape), -64, 64, 38)
+        into = old.clone()
+        B._weight_gradient(shadow, conv, bigb, smallb, into)
+        want = torch.nn.grad.conv2d_weight(big64, tuple(conv.weight.shape), small64, 2, 1) + old.cpu().double()
+        assert torch.equal(into.cpu().double(), want)
+    report.assert_reached({18, 19}, False, f'{case} {mode}')
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', [(7, 256, 512, 4, 12), (130, 40, 24, 4, 4), (3, 16, 8, 2, 3)])
+def test_seed_transposed_convolution_rounds_to_nearest_even(F, B, mode, case):
+    """The generator's seed layer (conv_transpose2d of a 1 x 1 code) on srgan_h_gemm: plain and leaky 0.2."""
+    n, c_in, c_out, r, s = case
+    layer = torch.nn.ConvTranspose2d(c_in, c_out, (r, s), 1, 0).cuda()
+    with torch.no_grad():
+        layer.weight.copy_(eighths(tuple(layer.weight.shape), 41))
+        layer.bias.copy_(integers((c_out,), -1024, 1024, 42))
+    z = integers((n, c_in), -3, 3, 43)
+    z64, w64, b64 = z.double().cpu(), layer.weight.data.double().cpu(), layer.bias.data.double().cpu()
+    want = torch.nn.functional.conv_transpose2d(z64.view(n, c_in, 1, 1), w64, b64)
+    from srgan_amd.tape import no_grad
+    with no_grad():
+        zb = blocked(F, B, z, mode)
+        assert torch.equal(nchw(B, B.seed_conv_transpose(zb, layer)), round16(want, mode))
+        assert torch.equal(nchw(B, B.seed_conv_transpose(zb, layer, slope=0.2)), round16(leaky_reference(want, 0.2), mode))
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_add_and_pack_round_to_nearest_even(F, B, mode):
+    """srgan_h_add of two 16-bit tensors whose exact sum needs more bits than the type holds, and srgan_h_pack of fp32 values
+    with a mask (slope 0.5) and without: one rounding to nearest even each."""
+    shape = (3, 21, 6, 10)
+    a = integers(shape, -255, 255, 51)
+    b = integers(shape, -64, 64, 52) / 64.0
+    ref = integers(shape, -1, 1, 53)
+    x = integers(shape, -4096, 4096, 54) / 64.0                     # 13 significant bits: more than bf16 and fp16 hold
+    a16, b16 = a.to(TORCH[mode]), b.to(TORCH[mode])
+    assert torch.equal(a16.float(), a) and torch.equal(b16.float(), b)
+    from srgan_amd.tape import no_grad
+    with no_grad():
+        ab, bb = blocked(F, B, a, mode), blocked(F, B, b, mode)
+        total = a.double().cpu() + b.double().cpu()
+        assert (total.to(TORCH[mode]).double() != total).any()
+        assert torch.equal(nchw(B, B.add(ab, bb)), round16(total, mode))
+        assert torch.equal(nchw(B, blocked(F, B, x, mode)), round16(x.double().cpu(), mode))
+        refb = blocked(F, B, ref, mode)
+        masked = x.double().cpu() * torch.where(ref.cpu() > 0, 1.0, 0.5).double()
+        assert torch.equal(nchw(B, B.pack(F.leaf(x), B.CODES[mode], refb.data, 0.5)), round16(masked, mode))

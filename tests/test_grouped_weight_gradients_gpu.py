@@ -66,7 +66,8 @@ def test_grouped_1x1_weight_gradients_through_the_abi(pkg, plane, shares):
     device = torch.device('cuda', 0)
     d_buffer, d_gy = buffer.to(device), gy.to(device)
     keep, slots = [], (ctypes.c_byte * (128 * len(cins)))()
-    gws = [torch.full((width, c, 1, 1), 0.25, device=device) for c in cins]
+    prefills = [torch.randn(width, c, 1, 1, generator=generator) for c in cins]
+    gws = [prefill.to(device) for prefill in prefills]
     grid_x = grid_y = variants = 0
     partial_at = taps = elements = 0
     weights = sum(width * c for c in cins) if shares else 0
@@ -90,15 +91,15 @@ def test_grouped_1x1_weight_gradients_through_the_abi(pkg, plane, shares):
     workspace = _lib._workspaces[(torch.cuda.current_device(), stream)]
     results = []
     for run in range(2):
-        for gw in gws:
-            gw.fill_(0.25)
+        for gw, prefill in zip(gws, prefills):
+            gw.copy_(prefill)
         workspace.fill_(float('nan'))
         _lib.check(lib.srgan_wgrad_group_run(table.data_ptr(), len(cins), 1, grid_x, grid_y, variants, 1, d_buffer.data_ptr(),
                                              d_gy.data_ptr(), None, taps, n * hw, elements, partial_at, stream), 'srgan_wgrad_group_run')
         torch.cuda.synchronize()
         results.append([gw.clone() for gw in gws])
     for index, c in enumerate(cins):
-        got, expected = results[0][index].cpu().double() - 0.25, want[index]
+        got, expected = results[0][index].cpu().double() - prefills[index].double(), want[index]
         scale = float(expected.abs().max())
         assert float((got - expected).abs().max()) <= 3e-5 * scale, f'{c} input channels on {h} x {w}'
         assert torch.equal(results[0][index], results[1][index]), f'{c} input channels: two runs differ'

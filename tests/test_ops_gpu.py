@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+import contraction_cases
+
 
 def test_product_fails_loudly_without_gpu_tensors():
     """CPU: the product path has no CPU fallback."""
@@ -43,83 +45,7 @@ def close(actual, expected, rtol=1e-3, what=''):
     assert err <= rtol, f'{what}: max err / max|ref| = {err:.3e}'
 
 
-CONV_CASES = [
-    # N, C, H, W, K, R, S, stride, pad
-    (2, 3, 9, 8, 5, 3, 3, (1, 1), (1, 1)),
-    (2, 4, 7, 7, 6, 1, 1, (1, 1), (0, 0)),
-    (2, 3, 12, 10, 4, 4, 4, (2, 2), (1, 1)),
-    (1, 3, 15, 13, 4, 7, 7, (2, 2), (3, 3)),
-    (2, 2, 8, 8, 3, 2, 2, (2, 2), (0, 0)),
-    (3, 5, 4, 6, 7, 4, 6, (1, 1), (0, 0)),
-    (1, 2, 10, 10, 3, 3, 3, (3, 3), (1, 1)),
-    # DenseNet / DCGAN / VGG tile-boundary shapes (multi-tile, split-K, all MFMA tile configs)
-    (4, 256, 28, 28, 128, 1, 1, (1, 1), (0, 0)),
-    (4, 128, 28, 28, 32, 3, 3, (1, 1), (1, 1)),
-    (3, 200, 7, 7, 128, 1, 1, (1, 1), (0, 0)),
-    (2, 3, 64, 64, 64, 7, 7, (2, 2), (3, 3)),
-    (2, 64, 32, 32, 128, 4, 4, (2, 2), (1, 1)),
-    (2, 64, 20, 20, 64, 3, 3, (1, 1), (1, 1)),
-    (2, 48, 8, 8, 1, 8, 8, (8, 8), (0, 0)),          # map head in conv form (K = 1 -> direct kernel)
-    (2, 32, 16, 16, 20, 16, 16, (1, 1), (0, 0)),     # "linear" conv with a long reduction
-    (5, 70, 9, 9, 40, 3, 3, (1, 1), (1, 1)),         # ragged in every dimension
-    # pointwise shapes eligible for 16-byte staging (all extents multiples of 4) and near-misses
-    (2, 64, 16, 16, 96, 1, 1, (1, 1), (0, 0)),
-    (2, 160, 32, 32, 128, 1, 1, (1, 1), (0, 0)),
-    (1, 36, 8, 12, 20, 1, 1, (1, 1), (0, 0)),
-    (2, 64, 16, 18, 32, 1, 1, (1, 1), (0, 0)),
-    (3, 896, 16, 16, 448, 1, 1, (1, 1), (0, 0)),
-    # data gradient with <= 128 output channels: the resident-weight kernel, remainder tiles of 96 / 64 rows
-    (2, 224, 16, 16, 128, 1, 1, (1, 1), (0, 0)),
-    # few pixels, many input channels: the forward takes the kernel that splits K over the waves of a workgroup
-    (2, 288, 16, 16, 100, 1, 1, (1, 1), (0, 0)),
-    (4, 1024, 8, 8, 136, 1, 1, (1, 1), (0, 0)),
-    (2, 192, 8, 32, 64, 1, 1, (1, 1), (0, 0)),
-    # many input channels on planes that are no multiple of 32 pixels (the 14 x 14 and 7 x 7 planes of the reference's 224 x 224
-    # patches): the streaming kernel with ragged pixel groups and a K split finished in a fixed order
-    (16, 256, 14, 14, 128, 1, 1, (1, 1), (0, 0)),
-    (4, 1024, 7, 7, 128, 1, 1, (1, 1), (0, 0)),
-    (3, 512, 14, 14, 136, 1, 1, (1, 1), (0, 0)),
-    (1, 320, 6, 6, 40, 1, 1, (1, 1), (0, 0)),
-    # 3x3 / s1 / p1 shapes for the LDS-halo kernel (force = 0): all three channel-tile widths, ragged tiles,
-    # fewer input channels than one chunk, split over input-channel chunks
-    (2, 128, 32, 32, 32, 3, 3, (1, 1), (1, 1)),
-    (1, 3, 40, 48, 64, 3, 3, (1, 1), (1, 1)),
-    (2, 32, 16, 64, 130, 3, 3, (1, 1), (1, 1)),
-    (2, 24, 33, 35, 16, 3, 3, (1, 1), (1, 1)),
-    (16, 128, 64, 64, 32, 3, 3, (1, 1), (1, 1)),
-    (2, 128, 16, 16, 32, 3, 3, (1, 1), (1, 1)),      # 16-wide images: two image rows per 32-lane column block
-    (3, 40, 13, 16, 24, 3, 3, (1, 1), (1, 1)),
-    (2, 128, 14, 14, 32, 3, 3, (1, 1), (1, 1)),      # 14-wide planes of the 224-pixel configuration: two dead columns per tile
-    (2, 32, 14, 13, 128, 3, 3, (1, 1), (1, 1)),
-    (3, 128, 7, 7, 32, 3, 3, (1, 1), (1, 1)),
-    (3, 200, 20, 24, 40, 3, 3, (1, 1), (1, 1)),      # LDS-patch weight gradient: ragged channel chunks and tiles
-    (4, 3, 96, 96, 16, 7, 7, (2, 2), (3, 3)),        # stem: the 3-row image gradient takes the few-rows kernel
-    (2, 5, 72, 72, 7, 3, 3, (1, 1), (1, 1)),         # 5 and 7 rows (MR = 8) in the few-rows kernel
-    (8, 2, 256, 128, 3, 2, 2, (2, 2), (0, 0)),       # weight gradient 3 x 8 over K = 65536 pixels: lanes-along-K kernel
-    # k4 / s2 / p1 at the DCGAN pair's own shapes (reference age/models.py:61-65 on 64 x 192 driving frames and 128 x 128
-    # faces, crowd/models.py:132-136 backwards): three input channels, rectangular and ragged planes, 24- to 512-row outputs,
-    # K splits with the ordered finish
-    (3, 3, 64, 192, 64, 4, 4, (2, 2), (1, 1)),
-    (2, 64, 32, 96, 128, 4, 4, (2, 2), (1, 1)),
-    (2, 128, 16, 48, 256, 4, 4, (2, 2), (1, 1)),
-    (2, 256, 16, 24, 512, 4, 4, (2, 2), (1, 1)),
-    (5, 20, 36, 44, 24, 4, 4, (2, 2), (1, 1)),
-    (1, 64, 128, 128, 32, 4, 4, (2, 2), (1, 1)),
-    # the LDS-DMA 1x1 kernel (pointwise_ring.hip; whole 128-row tiles, >= 192 workgroups): 128- and 64-pixel tiles, weights
-    # k-contiguous (forward) and m-contiguous (data gradient), several row tiles, remainder rows of 32 / 96 on the old kernel
-    (16, 128, 64, 64, 128, 1, 1, (1, 1), (0, 0)),
-    (16, 256, 32, 32, 128, 1, 1, (1, 1), (0, 0)),
-    (4, 160, 64, 64, 288, 1, 1, (1, 1), (0, 0)),
-    (6, 96, 64, 64, 224, 1, 1, (1, 1), (0, 0)),
-    (24, 128, 24, 12, 128, 1, 1, (1, 1), (0, 0)),    # planes of 9 x 32 pixels: the 32-pixel tile, both weight layouts
-    # the map modules' 2x2 / s2 convolutions (reference crowd/models.py:131-133) at their own channel counts: tiny weight
-    # gradients from 10^4 - 10^5 pixels (many K slices, ordered finish), rectangular planes, an odd input height
-    (3, 8, 128, 128, 16, 2, 2, (2, 2), (0, 0)),
-    (2, 16, 64, 128, 32, 2, 2, (2, 2), (0, 0)),
-    (2, 1, 64, 64, 8, 2, 2, (2, 2), (0, 0)),
-    (2, 5, 67, 64, 20, 2, 2, (2, 2), (0, 0)),
-    (1, 3, 4, 64, 7, 2, 2, (2, 2), (0, 0)),
-]
+CONV_CASES = [entry.shape for entry in contraction_cases.CONV_CASES]     # (N, C, H, W, K, R, S, stride, pad)
 
 
 @gpu
@@ -252,10 +178,11 @@ def test_row_reductions_are_one_launch_in_a_fixed_order(F):
         for _ in range(3):
             assert torch.equal(F.row_dot(xv, xv).data, first), 'the reduction order moved between two runs'
         # accumulate: out += ...
-        out = torch.full((rows,), 2.5, device='cuda')
+        old = torch.randn(rows, generator=torch.Generator().manual_seed(rows)) * 2
+        out = old.cuda()
         _lib.check(lib.srgan_chan_reduce(xv.data.data_ptr(), None, None, None, out.data_ptr(), 1, rows, length, 1,
                                          _lib.stream_handle()), 'srgan_chan_reduce')
-        close(out, x.double().sum(1).float() + 2.5, 1e-3, 'accumulate')
+        close(out, x.double().sum(1).float() + old, 1e-3, 'accumulate')
     # two streams at once, many times: each stream's results must be its own
     a, b = dev(torch.randn(16, 400000, generator=gen)), dev(torch.randn(16, 400000, generator=gen))
     av, bv = F.leaf(a), F.leaf(b)
@@ -496,10 +423,11 @@ def test_fused_batch_norm_convolutions(F):
         _lib.check(lib.srgan_conv2d_fwd_bnrelu(desc, d['wide'].data_ptr(), bn, d['weight'].data_ptr(), None, y.data_ptr(),
                                                stream), 'fwd_bnrelu')
         close(y, y_ref, what=f'fused bn conv forward {c}->{k} k{r}')
-        gw = torch.full(weight.shape, 0.5, device='cuda')
+        old = torch.randn(weight.shape, generator=torch.Generator().manual_seed(c * k + r)) * 0.5
+        gw = old.cuda()
         _lib.check(lib.srgan_conv2d_bwd_weight_bnrelu(desc, d['wide'].data_ptr(), bn, d['gy'].data_ptr(), gw.data_ptr(), 1,
                                                       stream), 'bwd_weight_bnrelu')
-        close(gw, gw_ref + 0.5, what=f'fused bn conv weight gradient {c}->{k} k{r} (accumulate)')
+        close(gw, gw_ref + old, what=f'fused bn conv weight gradient {c}->{k} k{r} (accumulate)')
         _lib.check(lib.srgan_conv2d_bwd_weight_bnrelu(desc, d['wide'].data_ptr(), bn, d['gy'].data_ptr(), gw.data_ptr(), 0,
                                                       stream), 'bwd_weight_bnrelu')
         close(gw, gw_ref, what=f'fused bn conv weight gradient {c}->{k} k{r}')
@@ -571,7 +499,8 @@ def test_fused_batch_norm_backward_in_the_data_gradient(F):
         old = torch.randn(n, total, h, w, generator=gen)
         for accumulate in ((0, 1) if r == 1 else (0,)):
             gx_wide = dev(old)
-            g_gamma, g_beta = torch.full((c,), 0.25, device='cuda'), torch.full((c,), -0.5, device='cuda')
+            old_gamma, old_beta = torch.randn(2, c, generator=torch.Generator().manual_seed(c * k + accumulate)) * 0.5
+            g_gamma, g_beta = old_gamma.cuda(), old_beta.cuda()
             _lib.check(lib.srgan_conv2d_bwd_data_bnrelu(desc, gy_pointer, d['weight'].data_ptr(), bn,
                                                         d['wide'].data_ptr(), gx_wide.data_ptr(), g_gamma.data_ptr(),
                                                         g_beta.data_ptr(), accumulate, stream), 'bwd_data_bnrelu')
@@ -579,8 +508,8 @@ def test_fused_batch_norm_backward_in_the_data_gradient(F):
             close(gx_wide[:, :c], gx_ref + (old[:, :c] if accumulate else 0.0), what=what + ' gx')
             if total > c:
                 close(gx_wide[:, c:], old[:, c:], 0.0, what + ' (channels beyond the view untouched)')
-            close(g_gamma, ggamma_ref + 0.25, what=what + ' gamma gradient')
-            close(g_beta, gbeta_ref - 0.5, what=what + ' beta gradient')
+            close(g_gamma, ggamma_ref + old_gamma, what=what + ' gamma gradient')
+            close(g_beta, gbeta_ref + old_beta, what=what + ' beta gradient')
         gx_wide = dev(old)                          # input gradient only (frozen parameters)
         _lib.check(lib.srgan_conv2d_bwd_data_bnrelu(desc, gy_pointer, d['weight'].data_ptr(), bn,
                                                     d['wide'].data_ptr(), gx_wide.data_ptr(), None, None, 0, stream),
