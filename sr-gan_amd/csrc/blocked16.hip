@@ -288,7 +288,6 @@ struct HConv3Params {
   int32_t tiles_x, tiles_y, tiles_m;
   float* split_ws; unsigned int* split_tickets;
   int32_t xcd_remap;
-  int32_t debug;               // SRGAN_H_EXPERIMENT (timing experiments, wrong results): 1 = no staging after the prologue
 };
 
 __device__ unsigned int g_hconv3_split_tickets[SPLIT_TICKET_SETS * SPLIT_TICKET_TILES];
@@ -622,7 +621,6 @@ __global__ __launch_bounds__(256, RING == 2 ? 2 : 1) void hconv3x3_dma_kernel(co
 #pragma unroll
   for (int d = 0; d < RING - 1; ++d)
     if (d < chunks) issue(d, d);
-  if ((p.debug & 1) && RING - 1 < chunks) issue(RING - 1, RING - 1);       // (experiment: every stage holds finite data)
   hconv3_stage_bias<BM>(p.bias, p.epi, p.C_real, m0, bias_rows);           // behind the first chunk's requests, not in front of them
   int stage = 0;
   for (int c = 0; c < chunks; ++c) {
@@ -630,7 +628,7 @@ __global__ __launch_bounds__(256, RING == 2 ? 2 : 1) void hconv3x3_dma_kernel(co
     // chunk c + RING - 1 goes into (it held chunk c - 1)
     if (RING == 3 && c + 1 < chunks) h_dma_wait_and_barrier<L>();
     else h_dma_wait_and_barrier<0>();
-    if (c + RING - 1 < chunks && !(p.debug & 1)) issue(c + RING - 1, (stage + RING - 1) % RING);
+    if (c + RING - 1 < chunks) issue(c + RING - 1, (stage + RING - 1) % RING);
     const Slot* st = ring + stage * STAGE_Q;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
@@ -659,8 +657,6 @@ static bool hconv3_plan(int32_t N, int32_t CGI, int32_t CO_rows, int32_t H, int3
   else if (W == 8 && H == 8) { tw = 8; rows_for_ni[1] = rows_for_ni[2] = rows_for_ni[4] = 8; }   // whole images side by side
   else if (W == 4 && H == 4) { tw = 4; rows_for_ni[1] = 4; }                                      // (32 KB of LDS per stage at NI = 2)
   else { tw = 16; rows_for_ni[1] = 8; rows_for_ni[2] = 16; if (H == 16) rows_for_ni[4] = 16; }    // (NI = 4: two whole images)
-  static const bool no_wide = getenv("SRGAN_H_NO_WIDE_TILE") != nullptr;
-  if (no_wide) rows_for_ni[4] = 0;
   plan.tw = tw;
   plan.bm = CO_rows > 32 ? 64 : 32;
   plan.tiles_m = (CO_rows + plan.bm - 1) / plan.bm;
@@ -1041,8 +1037,7 @@ int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_
   if (parts < 1) parts = 1;
   while (parts > 1 && (int64_t)parts * CG > 4096) parts >>= 1;
   unsigned int* tickets = nullptr;
-  static const bool two_launches = getenv("SRGAN_H_SUMS_TWO_LAUNCHES") != nullptr;
-  float* part = two_launches ? nullptr : row_finish_workspace(CG, parts, 8, g_h_sum_tickets, s, &tickets);
+  float* part = row_finish_workspace(CG, parts, 8, g_h_sum_tickets, s, &tickets);
   if (!part) {
     tickets = nullptr;
     part = partial_workspace((size_t)CG * parts * 8 * sizeof(float), s);
@@ -1238,8 +1233,6 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
     }
   }
   p.xcd_remap = (plan.blocks % 8 == 0 && plan.blocks >= 64) ? 1 : 0;
-  static const int experiment = getenv("SRGAN_H_EXPERIMENT") ? atoi(getenv("SRGAN_H_EXPERIMENT")) : 0;
-  p.debug = experiment;
   const dim3 grid((unsigned)plan.blocks, (unsigned)split, 1);
   // LDS-DMA ring for 64-row tiles with an unsplit K.  SRGAN_H_DMA_RING: 0 = off (register staging), 2 / 3 = that many stages;
   // default two stages = two workgroups per CU.  Measured (profiles/r06h_*, scratch/h_conv_bench.py): three stages -- two chunks
@@ -1289,8 +1282,7 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
   p.tiles_n = (N + img - 1) / img;
   p.pixel_tiles = p.tiles_x * p.tiles_y * p.tiles_n;
   p.tiles_ci = (C_in + 63) / 64;
-  static const bool no_tall = getenv("SRGAN_H_WGRAD_64") != nullptr;
-  const int mb = (C_out >= 128 && !no_tall) ? 4 : 2;                 // 128- or 64-row blocks of gw
+  const int mb = C_out >= 128 ? 4 : 2;                // 128- or 64-row blocks of gw
   const int tiles_co = (C_out + 32 * mb - 1) / (32 * mb);
   const int blocks = p.tiles_ci * tiles_co;
   // Walkers per block: enough workgroups to occupy the chip, but every walker leaves its accumulators (147 / 295 KB) as a partial
@@ -1298,9 +1290,7 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
   // part of the launch on both ends of VGG (1 block x 1024 walkers; 64 blocks x 16 walkers: 151 MB each, profiles/r06b_*).
   // (64-row blocks run two workgroups per CU: where a walker still gets a long run of tiles -- the 64-channel layers on 64 x 64
   // planes: one block, 8192+ tiles -- all 512 slots are filled; elsewhere 320, for the partial traffic)
-  static const char* forced_walkers = getenv("SRGAN_H_WGRAD_WALKERS");
-  int target = mb == 4 ? 256 : ((int64_t)p.pixel_tiles >= (int64_t)16 * 512 * blocks ? 512 : 320);
-  if (forced_walkers) target = atoi(forced_walkers);
+  const int target = mb == 4 ? 256 : ((int64_t)p.pixel_tiles >= (int64_t)16 * 512 * blocks ? 512 : 320);
   int walkers = (target + blocks - 1) / blocks;
   if (walkers > p.pixel_tiles) walkers = p.pixel_tiles;
   if (walkers < 1) walkers = 1;

@@ -783,8 +783,7 @@ int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N,
   p.tiles_c = (C_big + 31) / 32;
   const int tiles_k = (C_small + 63) / 64;
   const int blocks = p.tiles_c * tiles_k;
-  static const char* forced_walkers = getenv("SRGAN_H_K4_WALKERS");
-  const int target = forced_walkers ? atoi(forced_walkers) : 512;      // two workgroups per CU x 256 CUs (384: -1.4 % on driving-fp16)
+  constexpr int target = 512;      // two workgroups per CU x 256 CUs (384: -1.4 % on driving-fp16)
   int walkers = (target + blocks - 1) / blocks;
   if (walkers > p.pixel_tiles) walkers = p.pixel_tiles;
   if (walkers < 1) walkers = 1;

@@ -695,11 +695,9 @@ static void launch_conv3_plain(const Conv3Params& p, int th, dim3 grid, hipStrea
 
 template <int BM, int CI_T, int TW>
 static void launch_conv3_w(const Conv3Params& p, int th, dim3 grid, hipStream_t stream) {
-  if (p.epi_x) {                       // (the plan admits the epilogue for 32- and 64-row tiles only)
-    if constexpr (BM <= 64) {
-      if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
-      else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
-    }
+  if (p.epi_x) {
+    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
   } else if (p.bn_mean) {
     if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, true, TW>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, true, TW>), grid, dim3(256), 0, stream, p);
@@ -759,11 +757,6 @@ static void launch_conv3_mixed(const Conv3Params& p, int bm, int th, int tw, int
   }
 }
 
-bool conv3x3_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_CONV3") != nullptr;
-  return !disabled;
-}
-
 // Tile choice: the widest output-channel tile (fewest re-reads of the input patch) and the 8-row pixel tile, as long
 // as that still gives ~2 workgroups per CU; otherwise narrower / shorter tiles; input-channel splitting (fp32 atomics
 // into a pre-zeroed output) only as the last resort and never below two chunks per workgroup.
@@ -773,8 +766,7 @@ static Conv3Plan conv3x3_plan(int32_t N, int32_t CI, int32_t CO, int32_t H, int3
                               int precision = 0, bool small_ok = true) {
   Conv3Plan plan;
   // mixed precision on 4 x 4 / 8 x 8 planes: whole images side by side in a 128-pixel tile (conv3x3_mixed_small_kernel)
-  static const bool no_small = getenv("SRGAN_NO_CONV3_SMALL") != nullptr;
-  plan.small = precision != 0 && small_ok && !no_small && H == W && (W == 4 || W == 8);
+  plan.small = precision != 0 && small_ok && H == W && (W == 4 || W == 8);
   if (plan.small) {
     const int images = 128 / (H * W);
     plan.tw = W; plan.th = 4; plan.ci_t = 16; plan.tiles_x = 1;
@@ -786,12 +778,8 @@ static Conv3Plan conv3x3_plan(int32_t N, int32_t CI, int32_t CO, int32_t H, int3
   const int tw = W <= 16 ? 16 : 32;      // 16-wide images: a 32-lane column block = two image rows (no dead columns)
   plan.tw = tw;
   plan.tiles_x = (W + tw - 1) / tw;
-  static const int bm_cap = getenv("SRGAN_CONV3_BM") ? atoi(getenv("SRGAN_CONV3_BM")) : 64;   // 64 rows: +0.4 % in-step over 128
-  int bm = CO > 64 ? 128 : (CO > 32 ? 64 : 32);
-  if (bm > bm_cap) bm = bm_cap;
-  if (precision && bm > 64) bm = 64;          // mixed precision: 32- / 64-row tiles, 16-channel chunks
-  static const int th_cap = getenv("SRGAN_CONV3_TH") ? atoi(getenv("SRGAN_CONV3_TH")) : 8;
-  int th = (bm == 128 || tw == 16 || th_cap < 8) ? 4 : 8;   // 128 rows / 16-wide tiles always use 4 column blocks per workgroup
+  int bm = CO > 32 ? 64 : 32;            // 64 rows at most: +0.4 % in-step over 128
+  int th = tw == 16 ? 4 : 8;             // 16-wide tiles always use 4 column blocks per workgroup
   auto rows = [&](int th_) { return th_ * (32 / tw); };
   auto count = [&](int bm_, int th_) {
     return (int64_t)N * ((H + rows(th_) - 1) / rows(th_)) * plan.tiles_x * ((CO + bm_ - 1) / bm_);
@@ -802,9 +790,7 @@ static Conv3Plan conv3x3_plan(int32_t N, int32_t CI, int32_t CO, int32_t H, int3
     else break;
   }
   plan.bm = bm; plan.th = th;
-  static const int ci_t32 = getenv("SRGAN_CONV3_CIT32") ? atoi(getenv("SRGAN_CONV3_CIT32")) : 8;
-  static const int ci_t64 = getenv("SRGAN_CONV3_CIT64") ? atoi(getenv("SRGAN_CONV3_CIT64")) : 4;
-  plan.ci_t = bm == 128 ? 4 : (bm == 64 ? ci_t64 : ci_t32);     // keeps the staged registers + accumulators <= 256
+  plan.ci_t = bm == 64 ? 4 : 8;     // keeps the staged registers + accumulators <= 256
   if (precision) plan.ci_t = 16;
   plan.tiles_m = (CO + bm - 1) / bm;
   plan.tiles_y = (H + rows(th) - 1) / rows(th);
@@ -812,7 +798,7 @@ static Conv3Plan conv3x3_plan(int32_t N, int32_t CI, int32_t CO, int32_t H, int3
   }
   const int chunks = (CI + plan.ci_t - 1) / plan.ci_t;
   int split = 1;
-  static const int split_below = getenv("SRGAN_CONV3_SPLIT_BELOW") ? atoi(getenv("SRGAN_CONV3_SPLIT_BELOW")) : 384;
+  constexpr int split_below = 384;
   if (allow_split && plan.blocks < split_below && chunks >= 4) {
     split = (int)((512 + plan.blocks - 1) / plan.blocks);
     if (split > chunks / 2) split = chunks / 2;
@@ -904,8 +890,7 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
                     "stream first (srgan_set_workspace, >= srgan_workspace_bytes())");
     }
   }
-  static const bool no_xcd = getenv("SRGAN_NO_XCD_ORDER") != nullptr;
-  p.xcd_remap = (!no_xcd && blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
+  p.xcd_remap = (blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
   dim3 grid((unsigned)blocks, (unsigned)split, 1);
   const int profile_slot = profile_bracket_begin(stream);
   if (precision) {
@@ -921,11 +906,8 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
     else if (plan.small) launch_conv3_mixed_small<8>(p, bm, precision, grid, stream);
     else launch_conv3_mixed(p, bm, th, tw, precision, grid, stream);
   }
-  else if (bm == 32 && plan.ci_t == 16) launch_conv3<32, 16>(p, th, tw, grid, stream);
   else if (bm == 32) launch_conv3<32, 8>(p, th, tw, grid, stream);
-  else if (bm == 64 && plan.ci_t == 8) launch_conv3<64, 8>(p, th, tw, grid, stream);
-  else if (bm == 64) launch_conv3<64, 4>(p, th, tw, grid, stream);
-  else launch_conv3<128, 4>(p, 4, tw, grid, stream);
+  else launch_conv3<64, 4>(p, th, tw, grid, stream);
   if (p.epi_partial && !epilogue->partial_out)
     bn_partial_reduce_run(p.epi_partial, p.epi_tiles, CO, p.bn_inv, epilogue->g_gamma, epilogue->g_beta, stream);
   const int status = launch_status();

@@ -30,7 +30,6 @@ struct Wgrad3Params {
   int64_t x_bs, gy_bs;
   int32_t N, CI, CO, H, W;
   int32_t tiles_x, tiles_y, tiles;
-  int32_t debug;                  // tuning experiments (SRGAN_WGRAD3_DEBUG): 1 skip the atomic pass
   float* partial;                 // non-NULL (round 5): walker `w` of channel chunk `c` stores its 32 x 288 block at
                                   // partial[(c * walkers + w) * 9216 ...]; conv3x3_wgrad_finish adds the walkers in order
   // x is relu(batch_norm_eval(x)) computed on the fly (per input channel) when bn_mean != NULL
@@ -308,7 +307,6 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const Wgrad3Params& p, const 
   // 4 * (lane >> 5) (co).  In that layout a wave's lanes are 36 bytes apart in gw (one L2 atomic transaction per
   // lane: measured 630 us per launch), so the 32 x 288 block is transposed through LDS and the atomics go out with
   // lanes along the contiguous (ci, tap) run of each output-channel row.
-  if (p.debug & 1) return;
   const int run = min(WG3_CI, p.CI - ci0) * 9;       // valid floats of each row
 #pragma unroll
   for (int half = 0; half < 2; ++half) {             // rows 16 * half ... : accumulator registers 8 * half ...
@@ -422,7 +420,7 @@ __global__ __launch_bounds__(WG3_THREADS, 3) void conv3x3_wgrad_grouped_kernel(c
   p.x = x_base + job.x_off; p.gy = gy_base + job.gy_off; p.x_bs = job.x_bs; p.gy_bs = job.gy_bs;
   p.gw = gw_base ? gw_base + (int64_t)(intptr_t)job.gw : job.gw;      // (an element offset into the per-step buffer)
   p.N = job.N; p.CI = job.CI; p.CO = job.CO; p.H = job.H; p.W = job.W;
-  p.tiles_x = job.tiles_x; p.tiles_y = job.tiles_y; p.tiles = job.tiles; p.debug = 0;
+  p.tiles_x = job.tiles_x; p.tiles_y = job.tiles_y; p.tiles = job.tiles;
   p.bn_mean = job.bn_mean; p.bn_inv = job.bn_inv; p.bn_gamma = job.bn_gamma; p.bn_beta = job.bn_beta;
   p.partial = partial_base ? partial_base + job.partial_off : nullptr;
   const int co_chunk = chunk / job.ci_chunks;
@@ -439,21 +437,14 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_grouped_finish_kernel(const
                              job.CI);
 }
 
-bool conv3x3_wgrad_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_WGRAD3") != nullptr;
-  return !disabled;
-}
-
 // Walkers over the pixel tiles: five resident 3-wave workgroups per CU (120 VGPRs, 22 KB of LDS) over the whole grid, and
 // at least `depth` tiles per walker so that the atomic pass (32 x 288 floats per workgroup) is amortised.
 static int conv3x3_wgrad_walkers(int tiles, int ci_chunks, int co_chunks, int group = 1) {
-  static const int resident = getenv("SRGAN_WGRAD3_WGS") ? atoi(getenv("SRGAN_WGRAD3_WGS")) : 1280;
-  static const int depth_override = getenv("SRGAN_WGRAD3_DEPTH") ? atoi(getenv("SRGAN_WGRAD3_DEPTH")) : 0;
+  constexpr int resident = 1280;
   // measured on 128 -> 32 channels, batch 16: 64x64 images best at 8 tiles per walker, 32x32 at 4, 16x16 at 1 (batch
   // 48 at 16x16 = 192 tiles: 48 us at depth 1 -- 768 workgroups x 9216 atomics -- so 4 from 128 tiles up)
-  const int depth = depth_override > 0 ? depth_override : (tiles >= 1024 ? 8 : (tiles >= 128 ? 4 : 1));
-  static const int oversubscription = getenv("SRGAN_GROUP_OVERSUB") ? atoi(getenv("SRGAN_GROUP_OVERSUB")) : 4;
-  const int wanted = group > 1 ? (resident * oversubscription + group - 1) / group : resident;
+  const int depth = tiles >= 1024 ? 8 : (tiles >= 128 ? 4 : 1);
+  const int wanted = group > 1 ? (resident * GROUP_OVERSUBSCRIPTION + group - 1) / group : resident;
   int walkers = wanted / (ci_chunks * co_chunks);
   if (walkers > (tiles + depth - 1) / depth) walkers = (tiles + depth - 1) / depth;
   if (group > 1 && walkers > 8) walkers -= walkers % 8;     // whole units of the grouped kernel's XCD-aware order
@@ -468,16 +459,13 @@ static int conv3x3_wgrad_walkers(int tiles, int ci_chunks, int co_chunks, int gr
 int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, float* gw, int32_t N, int32_t CI,
                       int32_t CO, int32_t H, int32_t W, int accumulate, hipStream_t stream, const float* const* bn,
                       int precision) {
-  static const int th_override = getenv("SRGAN_WGRAD3_TH") ? atoi(getenv("SRGAN_WGRAD3_TH")) : 0;
   Wgrad3Params p;
   p.x = x; p.gy = gy; p.gw = gw; p.x_bs = x_bs; p.gy_bs = gy_bs;
   p.N = N; p.CI = CI; p.CO = CO; p.H = H; p.W = W;
-  p.debug = getenv("SRGAN_WGRAD3_DEBUG") ? atoi(getenv("SRGAN_WGRAD3_DEBUG")) : 0;
   p.bn_mean = bn ? bn[0] : nullptr; p.bn_inv = bn ? bn[1] : nullptr;
   p.bn_gamma = bn ? bn[2] : nullptr; p.bn_beta = bn ? bn[3] : nullptr;
   const int ci_chunks = (CI + WG3_CI - 1) / WG3_CI, co_chunks = (CO + WG3_CO - 1) / WG3_CO;
-  int th = 4;                                  // 4-row tiles: fewer halo rows per pixel (2-row tiles never measured better)
-  if (th_override == 2 || th_override == 4) th = th_override;
+  constexpr int th = 4;                        // 4-row tiles: fewer halo rows per pixel (2-row tiles never measured better)
   p.tiles_x = (W + WG3_TW - 1) / WG3_TW;
   p.tiles_y = (H + th - 1) / th;
   const int64_t tiles = (int64_t)N * p.tiles_y * p.tiles_x;
@@ -489,7 +477,7 @@ int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
   if (!accumulate) if (const int status = zero_floats(gw, (int64_t)CO * CI * 9, stream)) return status;
   // several walkers per channel chunk: each keeps its 32 x 288 block in the workspace, a second kernel adds them in order
   p.partial = nullptr;
-  if (walkers > 1 && !split_atomics_forced() && !(p.debug & 1))
+  if (walkers > 1 && !split_atomics_forced())
     p.partial = partial_workspace((size_t)ci_chunks * co_chunks * walkers * (WG3_CO * WG3_CI * 9) * sizeof(float), stream);
   const int64_t blocks = (int64_t)((walkers + 7) / 8) * 8 * ci_chunks * co_chunks;
   SRGAN_REQUIRE(blocks < ((int64_t)1 << 31), SRGAN_ERANGE, "conv3x3 wgrad grid");
@@ -500,8 +488,7 @@ int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
   if (precision == 1) SRGAN_WG3_LAUNCH(4, 1);
   else if (precision == 2) SRGAN_WG3_LAUNCH(4, 2);
   else if (ragged) SRGAN_WG3_LAUNCH(4, 0, true);
-  else if (th == 4) SRGAN_WG3_LAUNCH(4);
-  else SRGAN_WG3_LAUNCH(2);
+  else SRGAN_WG3_LAUNCH(4);
 #undef SRGAN_WG3_LAUNCH
   if (p.partial)
     hipLaunchKernelGGL(conv3x3_wgrad_finish_kernel, dim3(WG3_FINISH_SLABS, (unsigned)(ci_chunks * co_chunks)), dim3(256), 0, stream, p,

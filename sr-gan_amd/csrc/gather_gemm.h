@@ -115,7 +115,6 @@ struct GatherGemm {
   int32_t a_kfast, b_kfast;                              // staging order: lanes along k (1) or along m/n (0)
   int32_t mode;                                          // StoreMode
   int32_t split_k, k_per_split;                          // filled by the launcher
-  int32_t debug;                                         // tuning experiments (SRGAN_GG_DEBUG): 1 no re-staging, 2 no MFMA
   float* partial;                                        // GG_PARTIAL: K-slice z stores to partial[(z*M + i)*N + j]; GG_ORDERED_*: [tile][slice][accumulators]
   unsigned int* tickets;                                 // GG_ORDERED_*: one per output tile
   int32_t use_partial;                                   // launcher: SplitCombine -- how the K slices are combined

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
     stage();
     __syncthreads();
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
-      const bool more = (k0 + BK < kend) && !(p.debug & 1);
+      const bool more = k0 + BK < kend;
       if (more) fetch(k0 + BK);
       if constexpr (PREC != 0) {
         static_assert(PREC == 0 || BK % 16 == 0, "16-deep MFMA steps");
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
         }
       } else
 #pragma unroll
-      for (int kk = 0; kk < ((p.debug & 2) ? 0 : BK); kk += 2) {
+      for (int kk = 0; kk < BK; kk += 2) {
         float a[MI], b[NI];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) a[mi] = As[(kk + lhi) * LDA + wm0 + mi * 32 + l31];
@@ -624,6 +624,8 @@ float* partial_workspace(size_t bytes, hipStream_t stream) {
 
 // ------------------------------------------------------------------------------------------- launcher
 struct GGConfig { int kind; int bm, bn; int tiles; };   // kind 0 direct, 1 mfma
+constexpr int GG_TILE_TARGET = 1024;      // workgroups a launch aims for (4 per CU): choose_config's tile, choose_split's K split
+constexpr int CONV3_MIN_WIDTH = 7;        // narrowest plane of the LDS-halo 3x3 kernel (the 14- and 7-wide planes at 224)
 
 static GGConfig choose_config(const GatherGemm& p, int force) {
   GGConfig c;
@@ -634,14 +636,12 @@ static GGConfig choose_config(const GatherGemm& p, int force) {
     c.tiles = p.M * ((p.N + 255) / 256);
     return c;
   }
-  static const bool no_dot = getenv("SRGAN_NO_DOT") != nullptr;
-  if (force == 0 && !no_dot && p.M <= 8 && p.N <= 8 && p.K >= 65536) {     // kind 9: lanes along K
+  if (force == 0 && p.M <= 8 && p.N <= 8 && p.K >= 65536) {     // kind 9: lanes along K
     c.kind = 9; c.bm = 8; c.bn = 8;
     c.tiles = 1;
     return c;
   }
-  static const bool no_rows = getenv("SRGAN_NO_ROWS") != nullptr;
-  if (force == 0 && !no_rows && p.M <= 8 && p.N >= 4096) {     // kind 5: the few-rows kernel
+  if (force == 0 && p.M <= 8 && p.N >= 4096) {     // kind 5: the few-rows kernel
     c.kind = 5; c.bm = p.M <= 4 ? 4 : 8; c.bn = 256;
     c.tiles = (p.N + 255) / 256;
     return c;
@@ -649,25 +649,22 @@ static GGConfig choose_config(const GatherGemm& p, int force) {
   c.kind = 1;
   // Largest tile that still yields >= target workgroups (4 per CU: staging of one hides under the MFMAs of the
   // others); otherwise the smallest tile of the class, topped up by split-K in choose_split.
-  static const int target = getenv("SRGAN_TILE_TARGET") ? atoi(getenv("SRGAN_TILE_TARGET")) : 1024;
   static const int candidates[3][3][2] = {{{128, 128}, {128, 64}, {64, 64}},     // M > 64
                                           {{64, 128}, {64, 64}, {64, 64}},        // 32 < M <= 64
                                           {{32, 256}, {32, 128}, {32, 128}}};     // M <= 32
   const int cls = p.M > 64 ? 0 : (p.M > 32 ? 1 : 2);
   // Long-K problems (weight gradients: K = pixels) get their parallelism from split-K anyway, so they take the
   // largest tile: at 64 x 64 the operand stream (16 FLOP/B) is HBM-bound at ~80 TF/s.
-  static const bool big_tiles = getenv("SRGAN_NO_BIG_TILES") == nullptr;
-  if (big_tiles && p.K >= 131072 && p.M >= 96 && p.N >= 96) {
+  if (p.K >= 131072 && p.M >= 96 && p.N >= 96) {
     c.bm = 128; c.bn = 128;
     c.tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
     return c;
   }
-  static const int first = getenv("SRGAN_GG_FIRST_TILE") ? atoi(getenv("SRGAN_GG_FIRST_TILE")) : 0;
-  for (int i = first; i < 3; ++i) {
+  for (int i = 0; i < 3; ++i) {
     c.bm = candidates[cls][i][0];
     c.bn = candidates[cls][i][1];
     c.tiles = ((p.M + c.bm - 1) / c.bm) * ((p.N + c.bn - 1) / c.bn);
-    if (c.tiles >= target) break;
+    if (c.tiles >= GG_TILE_TARGET) break;
   }
   return c;
 }
@@ -675,7 +672,7 @@ static GGConfig choose_config(const GatherGemm& p, int force) {
 static void choose_split(GatherGemm& p, const GGConfig& c, bool allow_split) {
   p.split_k = 1;
   p.k_per_split = p.K > 0 ? ((p.K + GG_BK - 1) / GG_BK) * GG_BK : GG_BK;
-  static const int target = getenv("SRGAN_TILE_TARGET") ? atoi(getenv("SRGAN_TILE_TARGET")) : 1024;
+  constexpr int target = GG_TILE_TARGET;
   if (!allow_split || p.K < 128 || c.tiles * 4 >= target * 3) return;
   const int want = (target + c.tiles - 1) / c.tiles;
   const int max_split = p.K / 64;
@@ -712,8 +709,7 @@ static bool dec_vec_slow(const Dec3& d) {
 
 // Both operands 16-byte stageable (1x1 convolutions / linear layers on contiguous data, no halo).
 static bool vec_eligible(const GatherGemm& p) {
-  static const bool disabled = getenv("SRGAN_NO_VEC") != nullptr;
-  if (disabled || p.hlim != 1 || p.wlim != 1) return false;
+  if (p.hlim != 1 || p.wlim != 1) return false;
   if (((uintptr_t)p.A | (uintptr_t)p.B) & 15) return false;
   const bool a = p.a_kfast ? (dec_vec_fast(p.ak) && dec_vec_slow(p.am)) : (dec_vec_fast(p.am) && dec_vec_slow(p.ak));
   const bool b = p.b_kfast ? (dec_vec_fast(p.bk) && dec_vec_slow(p.bn)) : (dec_vec_fast(p.bn) && dec_vec_slow(p.bk));
@@ -745,8 +741,6 @@ static int64_t mfma_tile_floats(const GGConfig& c) { return (int64_t)c.bm * c.bn
 // whether the launch needs a zeroed (or live) C because it combines them with fp32 atomics -- only when the stream has
 // no workspace (or SRGAN_ATOMIC_SPLIT=1): otherwise the slices meet in a fixed order, through the workspace.
 bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
-  static const int debug = getenv("SRGAN_GG_DEBUG") ? atoi(getenv("SRGAN_GG_DEBUG")) : 0;
-  p.debug = debug;
   p.tickets = nullptr;
   GGConfig c = choose_config(p, force);
   if (c.kind == 9) {                       // workgroups of 256 k-lanes, ~16 k per thread
@@ -759,11 +753,10 @@ bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
   if (out) *out = c;
   p.use_partial = GG_COMBINE_ATOMIC;
   if (p.split_k <= 1) return false;
-  static const bool no_partial = getenv("SRGAN_NO_PARTIAL") != nullptr;
   const int64_t mn = (int64_t)p.M * p.N;
   const bool fits = (size_t)mn * p.split_k * sizeof(float) <= WORKSPACE_BYTES;
   // (up to 4096 outputs: at 960 outputs x 1024 slices the atomics still serialised -- 310 us for 36 MB of operands)
-  if (!no_partial && c.kind == 1 && p.split_k >= 16 && mn <= 4096 && fits) {
+  if (c.kind == 1 && p.split_k >= 16 && mn <= 4096 && fits) {
     p.use_partial = GG_COMBINE_PARTIAL_TINY;
     return false;
   }
@@ -875,17 +868,15 @@ int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N
 // be ragged; planes of fewer than 32 pixels stay on the generic kernel).
 static bool use_pointwise(const ConvGeom& g, int out_channels, int force) {
   const int in_channels = out_channels == g.K ? g.C : g.K;     // forward: C -> K; data gradient: K -> C
-  static const bool ragged = getenv("SRGAN_PW_NO_RAGGED") == nullptr;
-  const bool plane_ok = (g.H * g.W) % 32 == 0 || (ragged && g.H * g.W >= 32);
-  return force == 0 && pointwise_enabled() && pointwise(g) && plane_ok && out_channels >= 8 && in_channels % 2 == 0;
+  const bool plane_ok = g.H * g.W >= 32;       // (geom_ok: H, W >= 1)
+  return force == 0 && pointwise(g) && plane_ok && out_channels >= 8 && in_channels % 2 == 0;
 }
 
 // 3x3 / stride 1 / pad 1 with enough width to fill most of a 16-pixel tile row (two image rows share a 32-pixel MFMA
 // column block): the LDS-halo kernel.
 static bool use_conv3x3(const ConvGeom& g, int out_channels, int force) {
-  static const int min_width = getenv("SRGAN_CONV3_MIN_W") ? atoi(getenv("SRGAN_CONV3_MIN_W")) : 7;   // the 14- and 7-wide planes at 224
-  return force == 0 && conv3x3_enabled() && g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 &&
-         g.W >= min_width && out_channels >= 8;
+  return force == 0 && g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 &&
+         g.W >= CONV3_MIN_WIDTH && out_channels >= 8;
 }
 
 // Mixed precision also takes the 4 x 4 planes (whole images side by side in a tile: conv3x3_mixed_small_kernel) and
@@ -893,12 +884,10 @@ static bool use_conv3x3(const ConvGeom& g, int out_channels, int force) {
 // discriminators asks for (reference srgan.py:366-370): 29 of a 32-row tile's rows are padding there, and the generic
 // kernel's gather still made it six times slower (5.9 TF/s on [3 x 524 288] x 576).
 static bool use_conv3x3_mixed(const ConvGeom& g, int out_channels) {
-  static const bool no_small = getenv("SRGAN_NO_CONV3_SMALL") != nullptr;
   if (use_conv3x3(g, out_channels, 0)) return true;
-  const bool geometry = conv3x3_enabled() && g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1;
-  if (no_small || !geometry) return false;
-  static const int min_width = getenv("SRGAN_CONV3_MIN_W") ? atoi(getenv("SRGAN_CONV3_MIN_W")) : 7;
-  return (g.H == 4 && g.W == 4 && out_channels >= 8) || (g.W >= min_width && out_channels >= 1);
+  const bool geometry = g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1;
+  if (!geometry) return false;
+  return (g.H == 4 && g.W == 4 && out_channels >= 8) || (g.W >= CONV3_MIN_WIDTH && out_channels >= 1);
 }
 
 // Weight gradient of a 3x3 / stride 1 / pad 1 convolution with at least one wave's worth of input channels: the
@@ -906,20 +895,16 @@ static bool use_conv3x3_mixed(const ConvGeom& g, int out_channels) {
 // `aligned_only`: widths that are a multiple of 4 with 16-byte aligned rows (the float4 staging; the mixed-precision
 // variants have no other); otherwise the kernel's ragged variant also takes the 14- and 7-wide planes of 224 x 224.
 static bool wgrad3x3_geometry(const ConvGeom& g, int min_width = 7, bool aligned_only = false) {
-  static const bool no_ragged = getenv("SRGAN_WGRAD3_NO_RAGGED") != nullptr;
   const bool aligned = g.W % 4 == 0 && g.x_bs % 4 == 0 && g.y_bs % 4 == 0;
-  if (!aligned && (aligned_only || no_ragged)) return false;
-  if (no_ragged && !aligned_only) min_width = 16;              // the selection before the ragged variant existed
+  if (!aligned && aligned_only) return false;
   return g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.W >= min_width && g.C >= 32;
 }
 
 static bool use_wgrad3x3(const ConvGeom& g, const float* x, const float* gy, int force) {
-  return force == 0 && conv3x3_wgrad_enabled() && wgrad3x3_geometry(g);
+  return force == 0 && wgrad3x3_geometry(g);
 }
 
 static bool pointwise_wgrad_geometry(const ConvGeom& g) {
-  static const bool no_ragged = getenv("SRGAN_PWG_NO_RAGGED") != nullptr;
-  if (no_ragged && ((g.H * g.W) % 32 != 0 || g.x_bs % 4 != 0 || g.y_bs % 4 != 0)) return false;
   return pointwise(g) && g.H * g.W >= 32 && g.C >= 16 && g.K >= 16;
 }
 
@@ -1062,7 +1047,7 @@ int srgan_conv2d_fwd(const srgan_conv_desc* desc, const float* x, const float* w
   if (use_conv3x3(g, g.K, force_kernel))
     return conv3x3_run(x, g.x_bs, w, 0, g.C * 9, 9, 3, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H, g.W, 0,
                        (hipStream_t)stream);
-  if (force_kernel == 0 && dtype == 0 && bias == nullptr && stem7x7_enabled() &&
+  if (force_kernel == 0 && dtype == 0 && bias == nullptr &&
       stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw))
     return stem7x7_fwd_run(x, g.x_bs, w, y, g.y_bs, g.N, g.H, g.W, g.K, g.OH, g.OW, (hipStream_t)stream);
   std::vector<GatherGemm> plans{plan_conv_fwd(g, x, w, bias, y)};
@@ -1095,7 +1080,7 @@ int srgan_conv2d_bwd_data(const srgan_conv_desc* desc, const float* gy, const fl
   if (dtype && force_kernel == 0 && use_conv3x3_mixed(g, g.C))
     return conv3x3_run(gy, g.y_bs, w, 8, 9, g.C * 9, -3, -1, bias, gx, g.x_bs, g.N, g.K, g.C, g.H, g.W, accumulate,
                        (hipStream_t)stream, nullptr, nullptr, dtype);
-  if (force_kernel == 0 && dtype == 0 && bias == nullptr && !accumulate && stem7x7_enabled() &&
+  if (force_kernel == 0 && dtype == 0 && bias == nullptr && !accumulate &&
       stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw) && (g.W & 1) == 0 && (((uintptr_t)gx) & 7) == 0)
     return stem7x7_bwd_data_run(gy, g.y_bs, w, gx, g.x_bs, g.N, g.H, g.W, g.K, g.OH, g.OW, (hipStream_t)stream);
   // k4 / s2 / p1 (the DCGAN generators' transposed convolutions, reference crowd/models.py:132-136, age/models.py:37-41,
@@ -1103,8 +1088,7 @@ int srgan_conv2d_bwd_data(const srgan_conv_desc* desc, const float* gy, const fl
   // meets the 2x2 taps kh = 3 + a - 2i, kw = 3 + b - 2j of the input pixels (q - 1 + i, r - 1 + j), i in {a, a + 1},
   // j in {b, b + 1} -- four 2x2 sub-windows of the LDS-halo 3x3 kernel with strided stores, instead of four gathered
   // GEMMs on the generic kernel (50 TF/s).
-  static const bool no_k4s2 = getenv("SRGAN_NO_K4S2") != nullptr;
-  if (force_kernel == 0 && !no_k4s2 && conv3x3_enabled() && g.R == 4 && g.S == 4 && g.sh == 2 && g.sw == 2 && g.ph == 1 &&
+  if (force_kernel == 0 && g.R == 4 && g.S == 4 && g.sh == 2 && g.sw == 2 && g.ph == 1 &&
       g.pw == 1 && g.H == 2 * g.OH && g.W == 2 * g.OW && g.OW >= 8 && (g.C >= 8 || dtype) && !accumulate) {   // (mixed: also the 3-channel image gradient)
     // small problems split the input channels over the grid and add with atomics: the output is zeroed once for all classes
     // (only when the split adds with atomics: with a workspace the slices meet in a fixed order and the sums are stored)
@@ -1142,14 +1126,14 @@ int srgan_conv2d_bwd_weight(const srgan_conv_desc* desc, const float* x, const f
   SRGAN_REQUIRE(dtype_ok(dtype), SRGAN_EINVAL, "srgan_conv2d_bwd_weight compute_dtype");
   // (mixed precision also takes 8-wide planes on the 16-wide tile: half of the columns are dead, but the alternative is
   // the gather-bound generic kernel)
-  if (dtype && force_kernel == 0 && conv3x3_wgrad_enabled() && wgrad3x3_geometry(g, 8, true) &&
+  if (dtype && force_kernel == 0 && wgrad3x3_geometry(g, 8, true) &&
       (((uintptr_t)x | (uintptr_t)gy) & 15) == 0)
     return conv3x3_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H, g.W, accumulate, (hipStream_t)stream, nullptr,
                              dtype);
   if (dtype) force_kernel = 2;
   if (use_pointwise_wgrad(g, x, gy, force_kernel))
     return pointwise_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H * g.W, accumulate, (hipStream_t)stream);
-  if (force_kernel == 0 && dtype == 0 && stem7x7_enabled() && stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw))
+  if (force_kernel == 0 && dtype == 0 && stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw))
     return stem7x7_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.H, g.W, g.K, g.OH, g.OW, accumulate, (hipStream_t)stream);
   if (use_wgrad3x3(g, x, gy, force_kernel))
     return conv3x3_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H, g.W, accumulate, (hipStream_t)stream);
@@ -1177,7 +1161,7 @@ int srgan_conv2d_bnrelu_supported(const srgan_conv_desc* desc, int pass) {
   }
   if (pass == 2) {
     if (pointwise(g)) return pointwise_wgrad_geometry(g) ? 1 : 0;
-    return (conv3x3_wgrad_enabled() && wgrad3x3_geometry(g)) ? 1 : 0;
+    return wgrad3x3_geometry(g) ? 1 : 0;
   }
   return 0;
 }

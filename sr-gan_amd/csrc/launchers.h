@@ -17,7 +17,6 @@ int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N
 // conv3x3.hip: 3x3 / stride 1 / pad 1, the LDS-halo kernel.
 // A stride-2 class of a k4 / s2 / p1 transposed convolution as a 2x2 sub-window of the 3x3 kernel (see conv3x3_run).
 struct Conv3Placement { int32_t taps, out_plane, out_sy, out_sx, out_off; };
-bool conv3x3_enabled();
 int conv3x3_splits(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W, int precision = 0);
 bool conv3x3_epilogue_supported(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
 int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
@@ -26,8 +25,11 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
                 int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
                 const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const Conv3Placement* placement = nullptr);
 
+// A grouped weight-gradient launch (conv3x3_wgrad.hip, pointwise_wgrad.hip) asks for this many times the resident
+// workgroups, shared out over its problems.
+constexpr int GROUP_OVERSUBSCRIPTION = 4;
+
 // conv3x3_wgrad.hip: the weight gradient of a 3x3 / stride 1 / pad 1 convolution, single and grouped.
-bool conv3x3_wgrad_enabled();
 int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, float* gw, int32_t N, int32_t CI,
                       int32_t CO, int32_t H, int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
                       int precision = 0);
@@ -39,7 +41,6 @@ int conv3x3_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, int
                             int64_t elements, int64_t partial_floats, hipStream_t stream);
 
 // pointwise.hip: 1x1 / stride 1, the register-streamed kernel, and the reduction of the deferred batch-norm parameter sums.
-bool pointwise_enabled();
 int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, int32_t w_si, const float* bias, float* out,
                   int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t HW, int accumulate, hipStream_t stream,
                   const float* const* bn = nullptr, const BnBackwardEpilogue* epilogue = nullptr,
@@ -77,7 +78,6 @@ int pointwise_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, i
                               int64_t elements, int64_t partial_floats, hipStream_t stream);
 
 // stem7x7.hip: the DenseNet stem's 7x7 / stride 2 convolution, all three passes.
-bool stem7x7_enabled();
 bool stem7x7_geometry(int32_t C, int32_t K, int32_t R, int32_t S, int32_t sh, int32_t sw, int32_t ph, int32_t pw);
 int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int64_t y_bs, int32_t N, int32_t H, int32_t W,
                     int32_t K, int32_t OH, int32_t OW, hipStream_t stream);

@@ -534,22 +534,16 @@ int64_t pointwise_epilogue_tiles(int32_t N, int32_t HW) {
   return (groups + 3) / 4;
 }
 
-bool pointwise_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_POINTWISE") != nullptr;
-  return !disabled;
-}
-
-template <int MI, int BK, int NI>
+// (K slices of 64 measured no faster and spill at 128 rows: the slice is 32 channels; one 32-pixel group per wave.)
+template <int MI>
 static void launch_pointwise(const PointwiseParams& p, dim3 grid, hipStream_t stream) {
   if (p.epi_x) {
-    if constexpr (NI == 1 && MI <= 2) {
-      if (p.epi_ragged) hipLaunchKernelGGL((pointwise_kernel<MI, BK, false, 1, true, true>), grid, dim3(256), 0, stream, p);
-      else hipLaunchKernelGGL((pointwise_kernel<MI, BK, false, 1, true>), grid, dim3(256), 0, stream, p);
-    }
+    if (p.epi_ragged) hipLaunchKernelGGL((pointwise_kernel<MI, 32, false, 1, true, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((pointwise_kernel<MI, 32, false, 1, true>), grid, dim3(256), 0, stream, p);
     return;
   }
-  if (p.bn_mean) hipLaunchKernelGGL((pointwise_kernel<MI, BK, true, NI>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((pointwise_kernel<MI, BK, false, NI>), grid, dim3(256), 0, stream, p);
+  if (p.bn_mean) hipLaunchKernelGGL((pointwise_kernel<MI, 32, true, 1>), grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((pointwise_kernel<MI, 32, false, 1>), grid, dim3(256), 0, stream, p);
 }
 
 // bn (4 pointers: mean, inv_std, gamma, beta; NULL = none): the input is relu(batch_norm_eval(in)) on the fly.
@@ -606,46 +600,19 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
     return status;
   }
 
-  // Two 32-pixel groups per wave (64 x 64 wave tile): a tuning variant (SRGAN_PW_NI=2).  In isolation it is up to
-  // 10 % faster on the K = 128 data gradients, inside the training step it measured 0.7 % slower: off by default.
-  static const int ni_cap = getenv("SRGAN_PW_NI") ? atoi(getenv("SRGAN_PW_NI")) : 1;
-  int ni = (HW % 64 == 0 && ni_cap >= 2 && !epilogue) ? 2 : 1;
-  int64_t groups = (int64_t)N * ((HW + 32 * ni - 1) / (32 * ni));
-  int64_t col_blocks = (groups + 3) / 4;
-  // Tallest row tile that still yields ~4 workgroups per CU; otherwise shorter tiles, then split over input channels.
-  static const int mi_cap_long = getenv("SRGAN_PW_MI") ? atoi(getenv("SRGAN_PW_MI")) : 2;
-  static const int mi_cap_short = getenv("SRGAN_PW_MI_SHORT") ? atoi(getenv("SRGAN_PW_MI_SHORT")) : mi_cap_long;
-  const int mi_cap = CI <= 128 ? mi_cap_short : mi_cap_long;
-  int mi = CO > 64 ? 4 : (CO > 32 ? 2 : 1);
-  if (mi > mi_cap) mi = mi_cap;
-  if (epilogue && mi > 2) mi = 2;
-  // NI = 2 pairs with the 64-row tile (acc 64 + 2 x 32 operand registers; 128 rows x 64 pixels would spill)
-  if (ni == 2) {
-    if (mi > 2) mi = 2;
-    if (mi < 2 || col_blocks * ((CO + 63) / 64) < 1024) {
-      ni = 1;
-      groups = (int64_t)N * ((HW + 31) / 32);
-      col_blocks = (groups + 3) / 4;
-      mi = CO > 64 ? 4 : (CO > 32 ? 2 : 1);
-      if (mi > mi_cap) mi = mi_cap;
-    }
-  }
-  static const int min_wgs = getenv("SRGAN_PW_MIN_WGS") ? atoi(getenv("SRGAN_PW_MIN_WGS")) : 768;
+  // One 32-pixel group per wave, four waves per workgroup.
+  const int64_t groups = (int64_t)N * ((HW + 31) / 32);
+  const int64_t col_blocks = (groups + 3) / 4;
+  // The 64-row tile while it still yields ~3 workgroups per CU; otherwise the 32-row tile, then split over input channels.
+  // (128-row tiles and two pixel groups per wave measured slower inside the training step.)
+  constexpr int min_wgs = 768, split_below = (min_wgs * 3) / 4;
+  int mi = CO > 32 ? 2 : 1;
   while (mi > 1 && col_blocks * ((CO + mi * 32 - 1) / (mi * 32)) < min_wgs) mi >>= 1;
-  // Rows beyond the last full 128-row tile go to a second launch with a tile just tall enough for them (the data
-  // gradients of the bottlenecks have 64 + 32*l rows: a padded 128-row tile would waste up to 3/8 of the matrix work).
-  int rest = 0, rest_mi = 0;
-  if (ni == 1 && mi == 4 && CO > 128 && CO % 128 != 0 && CO % 128 <= 64) {
-    rest = CO % 128;
-    rest_mi = rest <= 32 ? 1 : 2;
-  }
-  const int main_rows = CO - rest;
-  p.tiles_m = (main_rows + mi * 32 - 1) / (mi * 32);
+  p.tiles_m = (CO + mi * 32 - 1) / (mi * 32);
   p.m_base = 0;
   const int64_t blocks = col_blocks * p.tiles_m;
   const int slices = (CI + 63) / 64;
   int split = 1;
-  static const int split_below = getenv("SRGAN_PW_SPLIT_BELOW") ? atoi(getenv("SRGAN_PW_SPLIT_BELOW")) : (min_wgs * 3) / 4;
   if (blocks < split_below && slices >= 2 && !epilogue) {   // (the fused epilogue needs whole sums per workgroup)
     split = (int)((min_wgs + blocks - 1) / blocks);
     if (split > slices) split = slices;
@@ -664,7 +631,7 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
     // Ordered finish (split_finish.h): partial tiles through the workspace, summed in slice order by the tile's last
     // workgroup -- one launch, no zero-fill, the same bits every run.  Without a workspace: zero-fill + fp32 atomics.
     int ticket_set = -1;
-    float* ws = split_workspace(blocks, split, (int64_t)mi * ni * 16 * 256, 0, stream, &ticket_set);
+    float* ws = split_workspace(blocks, split, (int64_t)mi * 16 * 256, 0, stream, &ticket_set);
     unsigned int* tickets = ws ? device_tickets(g_pointwise_split_tickets) : nullptr;
     if (ws && tickets) {
       p.mode = accumulate == 1 ? 4 : 3;
@@ -680,7 +647,6 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
   }
   if (epilogue) {
     SRGAN_REQUIRE(!bn && !bias, SRGAN_EINVAL, "pointwise batch-norm backward epilogue: no prologue, no bias");
-    SRGAN_REQUIRE(mi <= 2 && rest == 0, SRGAN_EUNSUPPORTED, "pointwise batch-norm backward epilogue: at most 64-row tiles");
     p.epi_ragged = ((((uintptr_t)epilogue->x | (uintptr_t)out) & 15) | ((epilogue->x_bs | out_bs | HW) & 3)) != 0 ? 1 : 0;
     p.epi_x = epilogue->x; p.epi_x_bs = epilogue->x_bs;
     p.bn_mean = epilogue->bn[0]; p.bn_inv = epilogue->bn[1]; p.bn_gamma = epilogue->bn[2]; p.bn_beta = epilogue->bn[3];
@@ -693,26 +659,13 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
                     "stream first (srgan_set_workspace, >= srgan_workspace_bytes())");
     }
   }
-  static const bool narrow = getenv("SRGAN_PW_NARROW_OUT") != nullptr;
-  p.wide_out = (!narrow && (((uintptr_t)out & 15) | (out_bs & 3) | (HW & 3)) == 0) ? 1 : 0;
-  p.gpi = (HW + 32 * ni - 1) / (32 * ni);
+  p.wide_out = ((((uintptr_t)out & 15) | (out_bs & 3) | (HW & 3)) == 0) ? 1 : 0;
+  p.gpi = (HW + 31) / 32;
   const int profile_slot = profile_bracket_begin(stream);
-  // (K slices of 64 measured no faster and spill at 128 rows: the slice is 32 channels.)
-  auto launch = [&](int mi_, dim3 grid) {
-    if (ni == 2) launch_pointwise<2, 32, 2>(p, grid, stream);
-    else if (mi_ == 4) launch_pointwise<4, 32, 1>(p, grid, stream);
-    else if (mi_ == 2) launch_pointwise<2, 32, 1>(p, grid, stream);
-    else launch_pointwise<1, 32, 1>(p, grid, stream);
-  };
-  static const bool no_xcd = getenv("SRGAN_NO_XCD_ORDER") != nullptr;
-  p.xcd_remap = (!no_xcd && p.tiles_m > 1 && blocks % 8 == 0) ? 1 : 0;
-  launch(mi, dim3((unsigned)blocks, (unsigned)split, 1));
-  if (rest > 0) {
-    p.m_base = main_rows;
-    p.tiles_m = 1;
-    p.xcd_remap = 0;
-    launch(rest_mi, dim3((unsigned)col_blocks, (unsigned)split, 1));
-  }
+  p.xcd_remap = (p.tiles_m > 1 && blocks % 8 == 0) ? 1 : 0;
+  const dim3 grid((unsigned)blocks, (unsigned)split, 1);
+  if (mi == 2) launch_pointwise<2>(p, grid, stream);
+  else launch_pointwise<1>(p, grid, stream);
   if (p.epi_partial && !epilogue->partial_out)
     bn_partial_reduce_run(p.epi_partial, (int)col_blocks, CO, p.bn_inv, epilogue->g_gamma, epilogue->g_beta, stream);
   const int status = launch_status();

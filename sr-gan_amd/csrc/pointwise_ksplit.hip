@@ -143,17 +143,12 @@ __global__ __launch_bounds__(256, 2) void pointwise_ksplit_kernel(const PwKsplit
   }
 }
 
-bool pointwise_ksplit_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_PW_KSPLIT") != nullptr;
-  return !disabled;
-}
-
 // Few pixels, long K: where the streaming kernel would have to shrink its tile and split K over the grid.
 bool pointwise_ksplit_wanted(int32_t N, int32_t K, int32_t M, int32_t HW, bool fused_bn) {
   // measured (608 ... 992 -> 128 channels, batch 16): 16x16 planes 15.5 vs 26 us for the streaming kernel, 32x32 planes
   // 50 vs 46 us -- the strided weight rows of 1024 workgroups saturate the L2 -> CU path -- so only the smallest take it
-  static const int max_groups = getenv("SRGAN_PKS_GROUPS") ? atoi(getenv("SRGAN_PKS_GROUPS")) : 256;
-  if (!pointwise_ksplit_enabled() || K % 32 != 0 || K < 256 || HW % 32 != 0) return false;
+  constexpr int max_groups = 256;
+  if (K % 32 != 0 || K < 256 || HW % 32 != 0) return false;
   if (fused_bn && K > PKS_MAX_K) return false;
   const int64_t groups = (int64_t)N * HW / 32;
   return groups * ((M + 127) / 128) <= max_groups;

@@ -340,17 +340,12 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
   }
 }
 
-bool pointwise_ring_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_PW_RING") != nullptr;
-  return !disabled;
-}
-
 // Whether the LDS-DMA kernel takes the 128-row tiles of this convolution (the caller sends the remaining rows, if any,
 // to pointwise_kernel); *tile_pixels = 128, 64 or 32.  Everything the DMA addresses must be 16-byte aligned.
 bool pointwise_ring_eligible(const float* in, int64_t in_bs, const float* w, int32_t w_so, int32_t w_si, const float* bias,
                              const float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t HW, bool fused_pro,
                              const BnBackwardEpilogue* epilogue, int* tile_pixels) {
-  if (!pointwise_ring_enabled() || bias || CO < 128 || CO % 32 != 0 || CI % 32 != 0 || CI < 32 || HW % 32 != 0) return false;
+  if (bias || CO < 128 || CO % 32 != 0 || CI % 32 != 0 || CI < 32 || HW % 32 != 0) return false;
   if (!(w_si == 1 && w_so % 4 == 0) && !(w_so == 1 && w_si % 4 == 0)) return false;
   if ((((uintptr_t)in | (uintptr_t)w | (uintptr_t)out) & 15) || (in_bs & 3) || (out_bs & 3)) return false;
   // A data gradient with the batch-norm backward epilogue moves 4 * (128 + 3 * rows) bytes per pixel for 2 * 128 * rows
@@ -360,9 +355,7 @@ bool pointwise_ring_eligible(const float* in, int64_t in_bs, const float* w, int
   if (epilogue && (no_epilogue || HW % 128 != 0 || (((uintptr_t)epilogue->x) & 15) || (epilogue->x_bs & 3))) return false;
   // Few pixel blocks: narrower tiles multiply the workgroups (16 images of 32 x 32 pixels, 128 rows: 43 us on the 128-pixel
   // tile = half the CUs idle, 30 us on the 64-pixel tile); the epilogue's partial sums are per 128-pixel block.
-  static const int narrow_below = getenv("SRGAN_PW_RING_NARROW_BELOW") ? atoi(getenv("SRGAN_PW_RING_NARROW_BELOW")) : 512;
-  static const int slim_below = getenv("SRGAN_PW_RING_SLIM_BELOW") ? atoi(getenv("SRGAN_PW_RING_SLIM_BELOW")) : 384;
-  static const int min_blocks = getenv("SRGAN_PW_RING_MIN_WGS") ? atoi(getenv("SRGAN_PW_RING_MIN_WGS")) : 192;
+  constexpr int narrow_below = 512, slim_below = 384, min_blocks = 192;
   const int64_t tiles = (int64_t)N * ((CO + 127) / 128);
   int pixels = 128;
   if (epilogue) pixels = 128;
@@ -417,8 +410,7 @@ int pointwise_ring_run(const float* in, int64_t in_bs, const float* w, int32_t w
   }
   const int64_t blocks = (int64_t)N * p.bpi * p.tiles_m;
   SRGAN_REQUIRE(blocks < ((int64_t)1 << 31), SRGAN_ERANGE, "pointwise ring grid");
-  static const bool no_xcd = getenv("SRGAN_NO_XCD_ORDER") != nullptr;
-  p.xcd_remap = (!no_xcd && p.tiles_m > 1 && blocks % 8 == 0) ? 1 : 0;
+  p.xcd_remap = (p.tiles_m > 1 && blocks % 8 == 0) ? 1 : 0;
   *rows_done = CO;
   const unsigned grid = (unsigned)blocks;
   const int fuse = epilogue ? 2 : (bn ? 1 : 0);

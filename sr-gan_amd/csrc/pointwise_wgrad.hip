@@ -522,13 +522,12 @@ static int pointwise_wgrad_plan(int32_t N, int32_t CI, int32_t CO, int32_t HW, P
   SRGAN_REQUIRE(chunks < ((int64_t)1 << 30) && tiles < (1 << 30), SRGAN_ERANGE, "pointwise wgrad grid");
   p.chunks = (int)chunks;
   // Three resident workgroups per CU (166 registers per lane): 768 workgroups = 3072 wave workers over the whole grid, but at least `min_chunks` chunks per worker so the LDS reduction + atomic pass is amortised.
-  static const int resident = getenv("SRGAN_PWG_WGS") ? atoi(getenv("SRGAN_PWG_WGS")) : 768;
-  static const int min_chunks = getenv("SRGAN_PWG_DEPTH") ? atoi(getenv("SRGAN_PWG_DEPTH")) : 2;   // (8 measured equal at 512 x 512, 2.5 % slower at 224 x 224)
-  static const int oversubscription = getenv("SRGAN_GROUP_OVERSUB") ? atoi(getenv("SRGAN_GROUP_OVERSUB")) : 4;
+  constexpr int resident = 768;
+  constexpr int min_chunks = 2;   // (8 measured equal at 512 x 512, 2.5 % slower at 224 x 224)
+  constexpr int oversubscription = GROUP_OVERSUBSCRIPTION;
   int wanted = group > 1 ? (resident * oversubscription + group - 1) / group : resident;
   // (shared out by work, see pointwise_wgrad_lds_plan: 8.0 -> 6.6 ms per step on the ragged planes of 224 x 224)
-  static const bool equal_shares = getenv("SRGAN_PWG_EQUAL_SHARES") != nullptr;
-  if (!equal_shares && group > 1 && group_weights > 0)
+  if (group > 1 && group_weights > 0)
     wanted = (int)(((int64_t)resident * oversubscription * ((int64_t)CO * CI) + group_weights - 1) / group_weights);
   split = (wanted + tiles - 1) / tiles;
   const int max_split = (int)((chunks + 4 * min_chunks - 1) / (4 * min_chunks));
@@ -553,14 +552,11 @@ static int pointwise_wgrad_lds_plan(int32_t N, int32_t CI, int32_t CO, int32_t H
   p.chunks = (int)chunks;
   // Two resident workgroups per CU (72 KB of LDS each).  A worker leaves a 64 KB partial tile behind (written once, read once
   // by the finish): at least `min_chunks` chunks (32 KB of operands each) per worker.
-  static const int resident = getenv("SRGAN_PWL_WGS") ? atoi(getenv("SRGAN_PWL_WGS")) : 512;
-  static const int min_chunks = getenv("SRGAN_PWL_DEPTH") ? atoi(getenv("SRGAN_PWL_DEPTH")) : 8;
-  static const int oversubscription = getenv("SRGAN_PWL_OVERSUB") ? atoi(getenv("SRGAN_PWL_OVERSUB")) : 4;
+  constexpr int resident = 512, min_chunks = 8, oversubscription = 4;
   // a grouped launch's workgroups are shared out by WORK (the problem's weights over the group's: the same K range per
   // worker whatever the problem's width) when the caller says what the group holds, else in equal parts
   int wanted = group > 1 ? (resident * oversubscription + group - 1) / group : resident;
-  static const bool equal_shares = getenv("SRGAN_PWL_EQUAL_SHARES") != nullptr;
-  if (group > 1 && group_weights > 0 && !equal_shares)
+  if (group > 1 && group_weights > 0)
     wanted = (int)(((int64_t)resident * oversubscription * ((int64_t)CO * CI) + group_weights - 1) / group_weights);
   split = (wanted + tiles - 1) / tiles;
   const int max_split = (int)((chunks + min_chunks - 1) / min_chunks);
@@ -574,11 +570,10 @@ static int pointwise_wgrad_lds_plan(int32_t N, int32_t CI, int32_t CO, int32_t H
 }
 
 // Whole 32-pixel chunks, 16-byte aligned rows (the caller checks the pointers / offsets), byte offsets of a row inside an
-// image in 32 bits: the staged form; SRGAN_NO_PW_WGRAD_LDS=1 keeps the register-streamed kernel.
+// image in 32 bits: the staged form (tests: SRGAN_PWL_MIN_CI keeps narrower problems on the register-streamed kernel).
 static bool pointwise_wgrad_lds_shape(int32_t CI, int32_t CO, int32_t HW) {
-  static const bool disabled = getenv("SRGAN_NO_PW_WGRAD_LDS") != nullptr;
   static const int min_ci = getenv("SRGAN_PWL_MIN_CI") ? atoi(getenv("SRGAN_PWL_MIN_CI")) : 0;
-  return !disabled && CI >= min_ci && HW % 32 == 0 && (int64_t)(CI > CO ? CI : CO) * HW * 4 < ((int64_t)1 << 32);
+  return CI >= min_ci && HW % 32 == 0 && (int64_t)(CI > CO ? CI : CO) * HW * 4 < ((int64_t)1 << 32);
 }
 
 // (72 KB of dynamic LDS is beyond the 64 KB a launch gets without the attribute: set once per kernel and device, see pointwise_ring.hip)

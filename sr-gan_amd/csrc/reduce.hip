@@ -458,13 +458,12 @@ int srgan_chan_reduce(const float* a, const float* b, const float* mean, const f
   // runs of at least RED_SEG elements, doubled while the rows still yield >= 256 workgroups (one per CU): the 50 MB of the
   // gradient penalty's squared norms at 1536 / 768 / 384 workgroups: 2.4 / 3.2 / 4.2 TB/s (fewer tickets, fewer ramps)
   int64_t seg = RED_SEG;
-  static const int min_wgs = getenv("SRGAN_REDUCE_MIN_WGS") ? atoi(getenv("SRGAN_REDUCE_MIN_WGS")) : 256;
-  static const int64_t seg_cap = getenv("SRGAN_REDUCE_SEG_CAP") ? atol(getenv("SRGAN_REDUCE_SEG_CAP")) : 65536;
+  constexpr int min_wgs = 256;
+  constexpr int64_t seg_cap = 65536;
   while (seg < seg_cap && (int64_t)N * C * ((HW + 2 * seg - 1) / (2 * seg)) >= min_wgs) seg *= 2;
   const int segs = (int)((HW + seg - 1) / seg);
   SRGAN_REQUIRE((int64_t)N * segs <= 65535, SRGAN_ERANGE, "srgan_chan_reduce grid");
-  static const bool unordered = getenv("SRGAN_REDUCE_UNORDERED") != nullptr;
-  const int ticket_set = (C <= ROW_TICKETS && !unordered) ? workspace_index(s) : -1;
+  const int ticket_set = C <= ROW_TICKETS ? workspace_index(s) : -1;
   if (ticket_set >= 0 && ticket_set < TICKET_SETS) {
     float* partial = partial_workspace((size_t)C * N * segs * sizeof(float), s);
     if (partial) {

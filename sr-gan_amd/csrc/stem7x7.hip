@@ -382,11 +382,6 @@ __global__ __launch_bounds__(256, 2) void stem7x7_bwd_data_kernel(const StemPara
     }
 }
 
-bool stem7x7_enabled() {
-  static const bool disabled = getenv("SRGAN_NO_STEM") != nullptr;
-  return !disabled;
-}
-
 // 7x7 / stride 2 / pad 3 on 3 input channels with at most 64 output channels (the DenseNet stem).
 bool stem7x7_geometry(int32_t C, int32_t K, int32_t R, int32_t S, int32_t sh, int32_t sw, int32_t ph, int32_t pw) {
   return C == 3 && K >= 8 && K <= 64 && R == 7 && S == 7 && sh == 2 && sw == 2 && ph == 3 && pw == 3;
@@ -405,7 +400,7 @@ int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int6
   StemParams p;
   stem_fill(p, x, x_bs, w, y, y_bs, nullptr, N, H, W, K, OH, OW);
   SRGAN_REQUIRE((int64_t)N * p.tiles_y * p.tiles_x < ((int64_t)1 << 31), SRGAN_ERANGE, "stem grid");
-  static const int resident = getenv("SRGAN_STEM_WGS") ? atoi(getenv("SRGAN_STEM_WGS")) : 1024;
+  constexpr int resident = 1024;
   const int grid = p.tiles < resident ? p.tiles : resident;
   const int slot = profile_bracket_begin(stream);
   if (K > 32) hipLaunchKernelGGL(stem7x7_fwd_kernel<2>, dim3(grid), dim3(256), 0, stream, p);
@@ -421,7 +416,7 @@ int stem7x7_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
   stem_fill(p, x, x_bs, nullptr, const_cast<float*>(gy), gy_bs, gw, N, H, W, K, OH, OW);
   SRGAN_REQUIRE((int64_t)N * p.tiles_y * p.tiles_x < ((int64_t)1 << 31), SRGAN_ERANGE, "stem grid");
   if (!accumulate) if (const int status = zero_floats(gw, (int64_t)K * 147, stream)) return status;
-  static const int resident = getenv("SRGAN_STEM_WGRAD_WGS") ? atoi(getenv("SRGAN_STEM_WGRAD_WGS")) : 512;
+  constexpr int resident = 512;
   int grid = p.tiles < resident ? p.tiles : resident;
   const int slot = profile_bracket_begin(stream);
   const int co_blocks = (K + 31) / 32;

@@ -27,7 +27,6 @@ and no concatenation, slicing or mask tensors are materialised.  Only the input 
 recorded backward (exactly the penalty's use); parameter gradients of a recorded backward need the primitive path
 (``fused.ENABLED = False``).
 """
-import os
 
 import torch
 
@@ -41,8 +40,8 @@ ENABLED = True      # tests flip this to compare the fused block with the primit
 # DenseNet transitions evaluated as norm -> relu -> pool -> conv instead of the reference's conv -> pool (crowd/models.py
 # _Transition: a 1x1 convolution commutes with the average pooling, so the convolution, its gradients and their
 # double-backward forms run on a quarter of the pixels: 8.5 % fewer executed FLOPs per iteration, 75.5 -> 79.2 images/s).
-# SRGAN_NO_POOL_FIRST=1 (tests: fused.POOL_FIRST = False) restores the reference order.
-POOL_FIRST = not os.environ.get('SRGAN_NO_POOL_FIRST')
+# Tests set fused.POOL_FIRST = False to compare with the reference order.
+POOL_FIRST = True
 PROLOGUE = True     # batch-norm + ReLU evaluated inside the convolution kernels (tests flip this too)
 EPILOGUE = True     # batch-norm + ReLU backward evaluated in the epilogue of the data-gradient kernels
 # The weight-gradient kernels of a block's backward only feed the optimizer, so they can run on a second stream next to
@@ -50,7 +49,7 @@ EPILOGUE = True     # batch-norm + ReLU backward evaluated in the epilogue of th
 # planes cannot fill 256 CUs.  The join is deferred to the end of the backward sweep (``tape.at_sweep_end``).  Kernels then
 # overlap, so per-kernel timings no longer describe one kernel at a time: bench.py switches this on for the timed region
 # (``settings.wgrad_stream`` -> ``fused.WGRAD_STREAM``) and off for the event-bracketed step behind its roofline line.
-WGRAD_STREAM = os.environ.get('SRGAN_WGRAD_STREAM', '0') == '1'
+WGRAD_STREAM = False
 _side_streams = {}
 
 
@@ -143,11 +142,10 @@ def _reduce_plan(layers, n, c0, h, w, growth, buffer_bs, epilogue1, epilogue2, d
     return plan
 
 
-GROUPED_WGRAD = not os.environ.get('SRGAN_NO_GROUPED_WGRAD')    # all the weight gradients of a block's backward in two launches (one table per kernel size)
-IN_PLACE_GRADIENT = not os.environ.get('SRGAN_NO_IN_PLACE_GRADIENT')
+GROUPED_WGRAD = True    # all the weight gradients of a block's backward in two launches (one table per kernel size; tests flip this)
 # (round 5: 4096 MB -- with the ordered weight gradients a single-problem launch is two launches (workers + finish), so keeping
 # the masked tangents of the larger blocks for ONE grouped pair pays at 512 x 512 too: 83.7 vs 83.2 images/s; 800 MB before)
-GROUPED_TANGENT_LIMIT = int(os.environ.get('SRGAN_GROUPED_TANGENT_LIMIT_MB', '4096')) << 20   # bytes of masked tangents kept
+GROUPED_TANGENT_LIMIT = 4096 << 20   # bytes of masked tangents kept
 
 
 def _wgrad_plan(layers, n, c0, h, w, growth, buffer_bs, device, tangent=None):
@@ -362,7 +360,7 @@ def dense_block(x, layers):
                                       'gradient only; set srgan_amd.fused.ENABLED = False for parameter gradients of '
                                       'a recorded backward')
         stream = F._stream()
-        if IN_PLACE_GRADIENT and not recorded and incoming_gradient_is_exclusive() and g.data.is_contiguous():
+        if not recorded and incoming_gradient_is_exclusive() and g.data.is_contiguous():
             gbuf = g.data                         # nobody else reads it: the layers accumulate into it in place
         else:
             gbuf = _empty(g.shape, device)        # private copy: the incoming gradient may be shared

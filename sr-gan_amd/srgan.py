@@ -543,11 +543,9 @@ class Experiment(ABC):
                 getattr(self.D, '_srgan_arena', None) is None:
             return None
         if getattr(self, '_gp_stream', None) is None:
-            # (SRGAN_GP_STREAM_PRIORITY=-1: the runtime's high priority for this, the longest chain -- an experiment that is NOT the
-            # default: +0.7 % on one GPU in the eager four-stream schedule, but a high-priority stream is one more hardware queue:
-            # -25 % under data parallelism next to RCCL's stream and -18 % / -47 % when the chains are replayed as a HIP graph,
-            # profiles/r05_stream_priority.txt)
-            self._gp_stream = torch.cuda.Stream(priority=int(os.environ.get('SRGAN_GP_STREAM_PRIORITY', '0')))
+            # (default priority: a high-priority stream for this, the longest chain, is one more hardware queue and lost 18-47 %
+            # under graph replay and data parallelism, profiles/r05_stream_priority.txt)
+            self._gp_stream = torch.cuda.Stream(priority=0)
         return self._gp_stream
 
     def _gradient_penalty_on_its_own_stream(self, stream, fake_examples, unlabeled_examples):
@@ -566,7 +564,7 @@ class Experiment(ABC):
         return gradient_penalty
 
     def _apply_stream_settings(self):
-        """``settings.wgrad_stream`` (None: leave the module default / SRGAN_WGRAD_STREAM) -> ``fused.WGRAD_STREAM``."""
+        """``settings.wgrad_stream`` (None: leave the module attribute as it is) -> ``fused.WGRAD_STREAM``."""
         wanted = getattr(self.settings, 'wgrad_stream', None)
         if getattr(self, '_single_compute_stream', False):
             wanted = False
