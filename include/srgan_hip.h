@@ -56,6 +56,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_BLOCKED16 0x8u    /* ABI 1.1: the srgan_h_* entry points (16-bit storage in the blocked layout) */
 #define SRGAN_FEATURE_BATCHED_SHADOWS 0x10u /* ABI 1.1, additive: srgan_h_pack_job_matrix / _bias_rows (every shadow kind in
                                                 srgan_h_pack_batched) */
+#define SRGAN_FEATURE_CROWD_FULL_IMAGE 0x20u /* ABI 1.1, additive: srgan_crowd_extract_windows / _resize_bilinear /
+                                                 _blend_windows (full-image crowd inference on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -345,6 +347,31 @@ int srgan_crowd_extract_patches(const void* const* images_u8, const float* const
                                 const int32_t* heights, const int32_t* widths, const int32_t* ys, const int32_t* xs,
                                 const int32_t* flips, int32_t B, int32_t P, float* out_images, float* out_labels,
                                 float* out_maps, void* stream);
+
+/* ---- full-image (sliding-window) inference of the crowd application on the device (SRGAN_FEATURE_CROWD_FULL_IMAGE) ----
+ * The reference's predict_full_example (crowd/srgan.py:332-395) without its per-window NumPy work.
+ * Windows first .. first + count - 1 of ONE resident scene (image_u8: uint8 RGB [H, W, 3]): window i is the P x P patch
+ * centred on (ys[i / nx], xs[i % nx]) -- ys [ny] / xs [nx]: int32 arrays on the device, the centre lists of the reference's
+ * ImageSlidingWindowDataset (crowd/data.py:521-560) -- normalised to [-1, 1] and planar, out_images [count, 3, P, P];
+ * pixels outside the scene are 0 before normalisation (-1 after).  P even; first + count <= ny * nx; count <= 65535. */
+int srgan_crowd_extract_windows(const void* image_u8, int32_t H, int32_t W, const int32_t* ys, int32_t ny,
+                                const int32_t* xs, int32_t nx, int32_t first, int32_t count, int32_t P,
+                                float* out_images, void* stream);
+/* in [B, h, w] -> out [B, P, P], the float-mode bilinear resize the reference meant by scipy.misc.imresize(..., mode='F')
+ * (crowd/srgan.py:364): half-pixel centres, clamped edges, values not rescaled (sums are NOT preserved) -- the arithmetic of
+ * torch.nn.functional.interpolate(mode='bilinear', align_corners=False).  P >= h and P >= w (downscaling:
+ * SRGAN_EUNSUPPORTED). */
+int srgan_crowd_resize_bilinear(const float* in, int32_t B, int32_t h, int32_t w, int32_t P, float* out, void* stream);
+/* The overlap average of the windows' predictions: out_density [H, W] = (sum over the windows covering a pixel, in window
+ * order, of densities[i] at the pixel's place in window i) / (number of covering windows, 0 -> 1), bit-identical to the
+ * reference's slice-add loop; *out_count = sum over the pixels of (sum of counts[i] / (P * P) over the same windows) / the
+ * same number, reduced in a fixed order through the stream's workspace (same bits on every run; a stream without a
+ * registered workspace gets SRGAN_EUNSUPPORTED when the image has more than 1024 pixels).  densities [ny * nx, P, P] may be
+ * NULL (a network without a density: out_density is zero-filled, nothing is read); counts [ny * nx]; ys / xs as above;
+ * P even.  All pointers are device pointers. */
+int srgan_crowd_blend_windows(const float* densities, const float* counts, const int32_t* ys, int32_t ny, const int32_t* xs,
+                              int32_t nx, int32_t H, int32_t W, int32_t P, float* out_density, float* out_count,
+                              void* stream);
 
 /* Offline ikNN label of a crowd scene (reference crowd/database_preprocessor.py:93-101,266-290: generate_knn_map +
  * 1 / (map + epsilon)): out[y, x] = 1 / (mean over the k nearest heads of the Euclidean distance from (y, x), each

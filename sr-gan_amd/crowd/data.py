@@ -1,6 +1,8 @@
 """Inference-side data handling of the crowd application: the sliding-window patches of one full
 image (reference crowd/data.py:370-453,521-560) and the uint8 -> [-1, 1] normalisation (crowd/data.py:115-128).
-Host-side NumPy only; the training datasets / preprocessors stay out of scope."""
+``ImageSlidingWindowDataset`` is the host-side NumPy form and the single source of the window positions;
+``DeviceSlidingWindows`` cuts the same windows on the device from a scene resident in HBM, as ``DeviceCrowdPatchLoader``
+does for training batches.  The reference's training datasets / preprocessors stay out of scope."""
 import numpy as np
 import torch
 
@@ -174,3 +176,59 @@ class DeviceCrowdPatchLoader:
     def __iter__(self):
         while True:
             yield self.batch_for(self.draw_positions())
+
+
+class DeviceSlidingWindows:
+    """The sliding-window patches of one full example cut ON THE DEVICE: the scene is uploaded once as uint8 and every
+    batch of ``batch_size`` windows is one ``srgan_crowd_extract_windows`` launch -- no per-window NumPy padding,
+    normalisation, transposition or upload.  The centres are ``ImageSlidingWindowDataset``'s (``ys`` / ``xs``: its
+    ``y_positions`` / ``x_positions`` as int32; window ``i`` is centred on ``(ys[i // len(xs)], xs[i % len(xs)])``, the
+    dataset's own index order), so the extra edge centre and images smaller than a patch follow the one rule.
+
+    Iterating yields ``(first window index, images f32[count, 3, P, P])`` device batches in window order.  Nothing
+    touches the device before the first batch is asked for."""
+
+    def __init__(self, full_example, batch_size, image_patch_size=128, window_step_size=32, device=None):
+        if image_patch_size % 2:
+            raise ValueError('the window slices only line up for an even patch size')
+        positions = ImageSlidingWindowDataset(full_example, image_patch_size, window_step_size)
+        self.image = full_example.image
+        self.height, self.width = self.image.shape[0], self.image.shape[1]
+        self.batch_size, self.patch_size = batch_size, image_patch_size
+        self.ys = np.asarray(positions.y_positions, dtype=np.int32)
+        self.xs = np.asarray(positions.x_positions, dtype=np.int32)
+        self.length = positions.length
+        self.device = device
+        self.scene = self.device_ys = self.device_xs = None
+
+    def __len__(self):
+        return self.length
+
+    def centre(self, index):
+        """``(y, x)`` of window ``index`` -- what the kernels compute from the uploaded table."""
+        return int(self.ys[index // len(self.xs)]), int(self.xs[index % len(self.xs)])
+
+    def upload(self):
+        if self.scene is None:
+            from ..utility import current_device
+            self.device = self.device or current_device()
+            self.scene = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.uint8)).to(self.device)
+            self.device_ys = torch.from_numpy(self.ys).to(self.device)
+            self.device_xs = torch.from_numpy(self.xs).to(self.device)
+        return self
+
+    def batch(self, first, count):
+        """Windows ``first .. first + count - 1`` as one device tensor."""
+        from .. import _lib
+        self.upload()
+        size = self.patch_size
+        images = torch.empty((count, 3, size, size), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.library().srgan_crowd_extract_windows(
+            self.scene.data_ptr(), self.height, self.width, self.device_ys.data_ptr(), len(self.ys),
+            self.device_xs.data_ptr(), len(self.xs), first, count, size, images.data_ptr(), _lib.stream_handle()),
+            'srgan_crowd_extract_windows')
+        return images
+
+    def __iter__(self):
+        for first in range(0, self.length, self.batch_size):
+            yield first, self.batch(first, min(self.batch_size, self.length - first))

@@ -151,6 +151,7 @@ class KnnDenseNetCat(nn.Module):
     (B, S, S) placeholder, produced once per shape and reused (Appendix A.11)."""
 
     COUNT_OUTPUTS = 1      # 2 in the dual-goal variant: (count, real/fake score)
+    density_is_placeholder = True      # the returned density is all zero: full-image inference on the device skips it
 
     def __init__(self, growth_rate=32, block_config=(6, 12, 48, 32), num_init_features=64, bn_size=4, drop_rate=0,
                  pretrained=False, label_patch_size=224, image_size=None):

@@ -8,7 +8,7 @@ import torch
 from .. import functional as F
 from ..srgan import Experiment, as_var
 from ..tape import no_grad
-from .data import CrowdExample, ImageSlidingWindowDataset
+from .data import CrowdExample, DeviceSlidingWindows, ImageSlidingWindowDataset
 from .models import DCGenerator, KnnDenseNetCat
 from ..synthetic import SyntheticLoader
 
@@ -165,7 +165,10 @@ class CrowdExperiment(Experiment):
 
         The reference resizes every predicted density patch to the patch size with ``scipy.misc.imresize`` (removed
         from SciPy); ``KnnDenseNetCat`` already predicts at the patch size, where that resize is the identity, and
-        only that case is supported."""
+        only that case is supported here; ``predict_full_example_device`` (chosen by ``settings.full_image_inference =
+        'device'``, read with ``getattr``; the default is this host path) resizes on the device."""
+        if getattr(self.settings, 'full_image_inference', 'host') == 'device':
+            return self.predict_full_example_device(full_example, network)
         settings = self.settings
         patch_size = settings.image_patch_size
         half = patch_size // 2
@@ -184,7 +187,8 @@ class CrowdExperiment(Experiment):
             for (_, x, y), density, count in zip(items, densities, counts):
                 if density.shape != (patch_size, patch_size):
                     raise NotImplementedError('density predictions at another resolution than the patch need '
-                                              'scipy.misc.imresize, which SciPy removed')
+                                              'scipy.misc.imresize, which SciPy removed (predict_full_example_device '
+                                              'resizes them on the device)')
                 count_array = np.full(density.shape, count / density.size, dtype=np.float32)
                 y_start = half - y if y - half < 0 else 0
                 y_end = y + half - height if y + half > height else 0
@@ -199,3 +203,91 @@ class CrowdExperiment(Experiment):
         full_density = sum_density / hits.astype(np.float32)
         full_count = np.sum(sum_count / hits.astype(np.float32))
         return full_count, full_density
+
+    def predict_full_example_device(self, full_example, network):
+        """``predict_full_example`` with everything around the network on the device: the scene is uploaded once, the
+        windows are cut by ``DeviceSlidingWindows``, per-window counts and densities stay in device buffers (a density
+        predicted below the patch resolution goes through ``srgan_crowd_resize_bilinear``, the float-mode resize the
+        reference's ``imresize(..., mode='F')`` meant), one ``srgan_crowd_blend_windows`` launch averages the overlaps,
+        and count and density come back in one download.  Same return contract: ``(count, density[H, W])``.
+
+        A network whose density is the all-zero placeholder (``density_is_placeholder``: ``KnnDenseNetCat``) has none
+        stored or read; both output arities work (``(density, count, maps)`` and ``JointDCDiscriminator``'s
+        ``(density, count)``)."""
+        from .. import _lib
+        settings = self.settings
+        patch_size = settings.image_patch_size
+        height, width = full_example.label.shape[0], full_example.label.shape[1]
+        windows = DeviceSlidingWindows(full_example, settings.batch_size, patch_size, settings.test_sliding_window_size)
+        if len(windows) == 0:           # (an image of at most half a patch has no window: nothing is predicted)
+            return np.float32(0.0), np.zeros((height, width), dtype=np.float32)
+        self.join_dnn_stream()
+        lib, device = _lib.library(), windows.upload().device
+        placeholder = getattr(network, 'density_is_placeholder', False)
+        counts = torch.empty(len(windows), dtype=torch.float32, device=device)
+        densities = None if placeholder else torch.empty((len(windows), patch_size, patch_size), dtype=torch.float32,
+                                                         device=device)
+        for first, images in windows:
+            with no_grad():
+                outputs = network(as_var(images))
+            density, count = outputs[0].data, outputs[1].data
+            batch = images.shape[0]
+            counts[first:first + batch].copy_(count.reshape(-1))
+            if placeholder:
+                continue
+            if tuple(density.shape[1:]) == (patch_size, patch_size):
+                densities[first:first + batch].copy_(density)
+            else:
+                density = density.float().contiguous()
+                _lib.check(lib.srgan_crowd_resize_bilinear(
+                    density.data_ptr(), batch, density.shape[1], density.shape[2], patch_size,
+                    densities[first:first + batch].data_ptr(), _lib.stream_handle()), 'srgan_crowd_resize_bilinear')
+        result = torch.empty(height * width + 1, dtype=torch.float32, device=device)     # [density | count]: one download
+        _lib.check(lib.srgan_crowd_blend_windows(
+            0 if placeholder else densities.data_ptr(), counts.data_ptr(), windows.device_ys.data_ptr(), len(windows.ys),
+            windows.device_xs.data_ptr(), len(windows.xs), height, width, patch_size, result.data_ptr(),
+            result.data_ptr() + 4 * height * width, _lib.stream_handle()), 'srgan_crowd_blend_windows')
+        result = result.cpu().numpy()
+        return result[-1], result[:-1].reshape(height, width)
+
+    def inference(self, input_):
+        """Count and density of one uint8 image ``[H, W, 3]`` through ``inference_network`` (reference
+        crowd/srgan.py:424-436, without its timing print), on the device path."""
+        example = CrowdExample(image=input_, label=np.zeros(input_.shape[:2], dtype=np.float32))
+        return self.predict_full_example_device(example, self.inference_network)
+
+    def evaluate(self, during_training=False, step=None, number_of_examples=None):
+        """The full-image test totals of the DNN and the GAN discriminator (reference crowd/srgan.py:302-330) over
+        ``self.dataset_class(dataset='test', ...)``, printed as there and returned as ``{'DNN': {...}, 'GAN': {...}}``:
+        the reference's totals plus 'MAE count', 'MAE density', 'MSE count', 'MSE density'.  ``during_training``: the
+        networks are already set up, nothing is loaded; ``number_of_examples`` limits the walk to the first examples."""
+        if not during_training:
+            super().evaluate()
+        results = {}
+        for name, network in (('DNN', self.DNN), ('GAN', self.D)):
+            test_dataset = self.dataset_class(dataset='test', map_directory_name=self.settings.map_directory_name)
+            length = test_dataset.length if number_of_examples is None else min(number_of_examples, test_dataset.length)
+            totals = dict.fromkeys(('Count', 'Density error', 'Count error', 'Density sum error', 'Predicted count',
+                                    'Predicted density sum', 'SE count', 'SE density'), 0.0)
+            for index in range(length):
+                full_image, full_label = test_dataset[index][:2]
+                full_example = CrowdExample(image=full_image, label=full_label)
+                predicted_count, predicted_label = self.predict_full_example(full_example, network)
+                true_count = full_example.label.sum()
+                totals['Count'] += true_count
+                totals['Density error'] += np.abs(predicted_label - full_example.label).sum()
+                totals['Count error'] += np.abs(predicted_count - true_count)
+                totals['Density sum error'] += np.abs(predicted_label.sum() - true_count)
+                totals['Predicted count'] += predicted_count
+                totals['Predicted density sum'] += predicted_label.sum()
+                totals['SE count'] += (predicted_count - true_count) ** 2
+                totals['SE density'] += (predicted_label.sum() - true_count) ** 2
+            print('=== {} ==='.format(name))
+            summary = {'MAE count': totals['Count error'] / length, 'MAE density': totals['Density sum error'] / length,
+                       'MSE count': totals['SE count'] / length, 'MSE density': totals['SE density'] / length}
+            for key, value in summary.items():
+                print('{}: {}'.format(key, value))
+            for key, value in totals.items():
+                print('Total {}: {}'.format(key, value))
+            results[name] = {key: float(value) for key, value in {**totals, **summary}.items()}
+        return results

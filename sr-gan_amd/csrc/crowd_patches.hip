@@ -5,9 +5,57 @@
 // NumpyArraysToTorchTensors of the reference's 4-worker NumPy pipeline (crowd/data.py:41-128,370-453,
 // crowd/shanghai_tech_data.py:76-104) in one HBM-bound kernel: 3 bytes + 8 bytes read, 20 bytes written per pixel.
 // Pixels outside the scene are zero BEFORE normalisation (the reference pads the uint8 image), i.e. -1 afterwards.
+// The same row body cuts the sliding windows of ONE scene for full-image inference (srgan_crowd_extract_windows: centres
+// from two small tables instead of per-example pointer tables; 3 bytes read, 12 bytes written per pixel).
 #include "common.h"
 
 namespace srgan {
+
+// `VEC` consecutive floats of one output row: one 16-byte store when VEC = 4 (the caller guarantees the alignment).
+template <int VEC>
+__device__ __forceinline__ void store_run(float* p, const float (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) p[i] = v[i];
+  }
+}
+
+// Row `row` of the P x P patch centred on (cy, cx) of one scene -- the body both kernels below share.  The calling thread
+// takes the runs of VEC columns first, first + step, ...; oi / ol / om point at the row's first element in the image
+// plane 0 / the label / the map of the output (ol, om may be null).
+template <int VEC>
+__device__ __forceinline__ void patch_row(const uint8_t* __restrict__ image, const float* __restrict__ label,
+                                          const float* __restrict__ map, int H, int W, int cy, int cx, bool flip, int P,
+                                          int row, int first, int step, float* __restrict__ oi, float* __restrict__ ol,
+                                          float* __restrict__ om) {
+  const int half = P / 2;
+  const int src_row = cy - half + row;
+  const bool row_ok = (unsigned)src_row < (unsigned)H;
+  const int64_t plane = (int64_t)P * P;
+  for (int col = first * VEC; col < P; col += step * VEC) {
+    float r[VEC], g[VEC], bl[VEC], lv[VEC], mv[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const int src_col = cx - half + (flip ? P - 1 - (col + v) : col + v);
+      const bool ok = row_ok && (unsigned)src_col < (unsigned)W;
+      const int64_t at = ok ? (int64_t)src_row * W + src_col : 0;
+      float pr = 0.f, pg = 0.f, pb = 0.f;
+      if (ok) { pr = (float)image[at * 3]; pg = (float)image[at * 3 + 1]; pb = (float)image[at * 3 + 2]; }
+      r[v] = pr / 127.5f - 1.f;
+      g[v] = pg / 127.5f - 1.f;
+      bl[v] = pb / 127.5f - 1.f;
+      lv[v] = (ok && label) ? label[at] : 0.f;
+      mv[v] = (ok && map) ? map[at] : 0.f;
+    }
+    store_run<VEC>(oi + col, r);
+    store_run<VEC>(oi + plane + col, g);
+    store_run<VEC>(oi + 2 * plane + col, bl);
+    if (ol) store_run<VEC>(ol + col, lv);
+    if (om) store_run<VEC>(om + col, mv);
+  }
+}
 
 __global__ __launch_bounds__(256) void crowd_patches_kernel(const uint8_t* const* __restrict__ images,
                                                             const float* const* __restrict__ labels,
@@ -19,29 +67,26 @@ __global__ __launch_bounds__(256) void crowd_patches_kernel(const uint8_t* const
                                                             float* __restrict__ out_images, float* __restrict__ out_labels,
                                                             float* __restrict__ out_maps) {
   const int b = blockIdx.y, row = blockIdx.x;
-  const int H = heights[b], W = widths[b], half = P / 2;
-  const int src_row = ys[b] - half + row;
-  const bool row_ok = (unsigned)src_row < (unsigned)H;
-  const bool flip = flips[b] != 0;
-  const uint8_t* image = images[b];
-  const float* label = labels ? labels[b] : nullptr;
-  const float* map = maps ? maps[b] : nullptr;
   const int64_t plane = (int64_t)P * P;
-  float* oi = out_images + (int64_t)b * 3 * plane + (int64_t)row * P;
-  float* ol = out_labels ? out_labels + (int64_t)b * plane + (int64_t)row * P : nullptr;
-  float* om = out_maps ? out_maps + (int64_t)b * plane + (int64_t)row * P : nullptr;
-  for (int col = threadIdx.x; col < P; col += 256) {
-    const int src_col = xs[b] - half + (flip ? P - 1 - col : col);
-    const bool ok = row_ok && (unsigned)src_col < (unsigned)W;
-    const int64_t at = ok ? (int64_t)src_row * W + src_col : 0;
-    float r = 0.f, g = 0.f, bl = 0.f;
-    if (ok) { r = (float)image[at * 3]; g = (float)image[at * 3 + 1]; bl = (float)image[at * 3 + 2]; }
-    oi[col] = r / 127.5f - 1.f;
-    oi[plane + col] = g / 127.5f - 1.f;
-    oi[2 * plane + col] = bl / 127.5f - 1.f;
-    if (ol) ol[col] = (ok && label) ? label[at] : 0.f;
-    if (om) om[col] = (ok && map) ? map[at] : 0.f;
-  }
+  patch_row<1>(images[b], labels ? labels[b] : nullptr, maps ? maps[b] : nullptr, heights[b], widths[b], ys[b], xs[b],
+               flips[b] != 0, P, row, (int)threadIdx.x, 256, out_images + (int64_t)b * 3 * plane + (int64_t)row * P,
+               out_labels ? out_labels + (int64_t)b * plane + (int64_t)row * P : nullptr,
+               out_maps ? out_maps + (int64_t)b * plane + (int64_t)row * P : nullptr);
+}
+
+// Full-image inference: windows first, first + 1, ... of ONE scene, window i centred on (ys[i / nx], xs[i % nx]) -- the
+// sliding-window order of the reference's ImageSlidingWindowDataset (crowd/data.py:521-560).  One wave per patch row, four
+// rows per workgroup; with VEC = 4 a lane stores 16 bytes per plane and a wave 1 KiB of one row.
+constexpr int WINDOW_ROWS = 4;
+template <int VEC>
+__global__ __launch_bounds__(256) void crowd_windows_kernel(const uint8_t* __restrict__ image, int H, int W,
+                                                            const int32_t* __restrict__ ys, const int32_t* __restrict__ xs,
+                                                            int nx, int first, int P, float* __restrict__ out_images) {
+  const int row = (int)blockIdx.x * WINDOW_ROWS + ((int)threadIdx.x >> 6);
+  if (row >= P) return;
+  const int window = first + (int)blockIdx.y;
+  patch_row<VEC>(image, nullptr, nullptr, H, W, ys[window / nx], xs[window % nx], false, P, row, (int)threadIdx.x & 63, 64,
+                 out_images + (int64_t)blockIdx.y * 3 * P * P + (int64_t)row * P, nullptr, nullptr);
 }
 
 }  // namespace srgan
@@ -57,5 +102,24 @@ extern "C" int srgan_crowd_extract_patches(const void* const* images_u8, const f
   hipLaunchKernelGGL(crowd_patches_kernel, dim3(P, B), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const uint8_t* const*>(images_u8), labels, maps, heights, widths, ys, xs, flips, P,
                      out_images, out_labels, out_maps);
+  return launch_status();
+}
+
+extern "C" int srgan_crowd_extract_windows(const void* image_u8, int32_t H, int32_t W, const int32_t* ys, int32_t ny,
+                                           const int32_t* xs, int32_t nx, int32_t first, int32_t count, int32_t P,
+                                           float* out_images, void* stream) {
+  SRGAN_REQUIRE(image_u8 && ys && xs && out_images && H > 0 && W > 0 && ny > 0 && nx > 0 && first >= 0 && count > 0 &&
+                P > 0 && P % 2 == 0, SRGAN_EINVAL, "srgan_crowd_extract_windows arguments");
+  SRGAN_REQUIRE((int64_t)first + count <= (int64_t)ny * nx, SRGAN_EINVAL, "srgan_crowd_extract_windows window range");
+  SRGAN_REQUIRE(count <= 65535 && (int64_t)H * W * 3 <= INT32_MAX && (int64_t)count * 3 * P * P <= INT32_MAX, SRGAN_ERANGE,
+                "srgan_crowd_extract_windows: a tensor exceeds 2^31 - 1 elements (or more than 65535 windows per call)");
+  const dim3 grid((P + WINDOW_ROWS - 1) / WINDOW_ROWS, count);
+  const uint8_t* image = static_cast<const uint8_t*>(image_u8);
+  if (P % 4 == 0 && reinterpret_cast<uintptr_t>(out_images) % 16 == 0)
+    hipLaunchKernelGGL(crowd_windows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, image, H, W, ys, xs, nx, first, P,
+                       out_images);
+  else
+    hipLaunchKernelGGL(crowd_windows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, image, H, W, ys, xs, nx, first, P,
+                       out_images);
   return launch_status();
 }
