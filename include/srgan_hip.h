@@ -58,6 +58,8 @@ const char* srgan_last_error(void);
                                                 srgan_h_pack_batched) */
 #define SRGAN_FEATURE_CROWD_FULL_IMAGE 0x20u /* ABI 1.1, additive: srgan_crowd_extract_windows / _resize_bilinear /
                                                  _blend_windows (full-image crowd inference on the device) */
+#define SRGAN_FEATURE_IMAGE_BATCHES 0x40u /* ABI 1.1, additive: srgan_image_batch_gather (training batches gathered on the
+                                             device from a resident database of frames) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -347,6 +349,21 @@ int srgan_crowd_extract_patches(const void* const* images_u8, const float* const
                                 const int32_t* heights, const int32_t* widths, const int32_t* ys, const int32_t* xs,
                                 const int32_t* flips, int32_t B, int32_t P, float* out_images, float* out_labels,
                                 float* out_maps, void* stream);
+
+/* Training-batch assembly from a database of equally sized frames resident on the device (SRGAN_FEATURE_IMAGE_BATCHES):
+ * the reference's AgeDataset / SteeringAngleDataset items (age/data.py:52-60, driving/data.py:44-51) collated by its
+ * DataLoader, as one launch and no host-to-device copy.  store: count frames [C, h, w], planar and contiguous, values in the
+ * 0..255 range; store_dtype 0 = uint8, 1 = float.  labels [count] float; order: int32 index list (an epoch's permutation);
+ * all device pointers.  Example b of the batch is frame order[first + b] -- an entry outside [0, count) is clamped, it cannot
+ * be checked here -- written to out_images [B, C, H, W] fp32 and out_labels [B] (labels and out_labels: both or neither).
+ * (H, W) == (h, w): out = (float(v) / 127.5f) - 1.0f, an IEEE division and a separate subtraction: the bits of the
+ * reference's to_normalized_range on a CPU tensor (utility.py:129-132).  Any other (H, W), larger or smaller, per axis: the
+ * normalised frame resampled with the arithmetic of torch.nn.functional.interpolate(mode='bilinear', align_corners=False,
+ * antialias=False) -- half-pixel centres, clamped edges.  A frame and the batch hold at most max_tensor_elements elements
+ * each (SRGAN_EINVAL, like every other argument error); the store as a whole may be larger, frames are addressed in 64 bits. */
+int srgan_image_batch_gather(const void* store, int store_dtype, int32_t count, int32_t C, int32_t h, int32_t w,
+                             const float* labels, const int32_t* order, int64_t first, int32_t B, int32_t H, int32_t W,
+                             float* out_images, float* out_labels, void* stream);
 
 /* ---- full-image (sliding-window) inference of the crowd application on the device (SRGAN_FEATURE_CROWD_FULL_IMAGE) ----
  * The reference's predict_full_example (crowd/srgan.py:332-395) without its per-window NumPy work.

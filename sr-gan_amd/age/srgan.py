@@ -1,6 +1,9 @@
-"""Age application (surface of reference age/srgan.py:17-51).  The IMDB-WIKI loaders need downloads and are out
-of scope; ``dataset_setup`` yields synthetic faces of the same batch contract (image f32[3,S,S] in [-1,1],
-age in [10, 95])."""
+"""Age application (surface of reference age/srgan.py:17-51).  Without a database ``dataset_setup`` yields synthetic
+faces of the reference's batch contract (image f32[3,S,S] in [-1,1], age in [10, 95]); with ``SRGAN_AGE_DATABASE`` it
+trains on a preprocessed IMDB-WIKI / LAP directory resident on the device (``age/data.py``; the downloads are out of
+scope)."""
+import os
+
 from ..srgan import Experiment
 from ..synthetic import SyntheticLoader
 from .models import Generator, Discriminator
@@ -18,8 +21,16 @@ class AgeExperiment(Experiment):
             return self.image_size
         return 224 if model_architecture == 'vgg' else 128
 
+    DATABASE_ENV = 'SRGAN_AGE_DATABASE'          # a directory with meta.json and the preprocessed images
+
     def dataset_setup(self):
         settings = self.settings
+        directory = os.environ.get(self.DATABASE_ENV)
+        if directory:
+            from ..data import database_loaders
+            from .data import age_datasets
+            database_loaders(self, age_datasets(directory, settings), self._size())
+            return
         self.train_dataset_loader = SyntheticLoader.images(settings.batch_size, self._size(), (10.0, 95.0),
                                                            seed=settings.labeled_dataset_seed, dp=self.dp)
         self.unlabeled_dataset_loader = SyntheticLoader.images(settings.batch_size, self._size(), (10.0, 95.0),

@@ -80,6 +80,18 @@ struct BnBackwardEpilogue {
   float* partial_out;
 };
 
+// Source taps of one output coordinate of a bilinear resize with half-pixel centres and clamped edges -- the sampling rule
+// of torch.nn.functional.interpolate(mode='bilinear', align_corners=False, antialias=False), up or down: scale = in / out
+// in fp32, source = fma(scale, destination + 0.5, -0.5) clamped at 0 (one rounding, as torch's CPU kernel evaluates it:
+// at 128 -> 192 a separately rounded product moves a tap weight by 1e-6); taps lo and hi (= lo at the far edge), weight w_hi.
+__device__ __forceinline__ void bilinear_source(float scale, int destination, int extent, int& lo, int& hi, float& w_hi) {
+  float source = __fmaf_rn(scale, (float)destination + 0.5f, -0.5f);
+  source = source < 0.f ? 0.f : source;
+  lo = min((int)source, extent - 1);
+  hi = lo + (lo < extent - 1 ? 1 : 0);
+  w_hi = source - (float)lo;
+}
+
 // Grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs x 8, never more than the work.
 inline unsigned stream_grid(int64_t work_items, int per_block) {
   int64_t blocks = (work_items + per_block - 1) / per_block;

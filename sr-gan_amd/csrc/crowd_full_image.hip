@@ -8,16 +8,8 @@
 namespace srgan {
 
 // out[b, oy, ox] of a [B, h, w] -> [B, P, P] upscale with half-pixel centres and clamped edges: the arithmetic of
-// torch.nn.functional.interpolate(mode='bilinear', align_corners=False) (scale = in / out in fp32, source = scale *
-// (destination + 0.5) - 0.5 clamped at 0, the two horizontal lerps first).  Values are not rescaled: sums change.
-__device__ __forceinline__ void bilinear_source(float scale, int destination, int extent, int& lo, int& hi, float& w_hi) {
-  float source = scale * ((float)destination + 0.5f) - 0.5f;
-  source = source < 0.f ? 0.f : source;
-  lo = min((int)source, extent - 1);
-  hi = lo + (lo < extent - 1 ? 1 : 0);
-  w_hi = source - (float)lo;
-}
-
+// torch.nn.functional.interpolate(mode='bilinear', align_corners=False) (bilinear_source, common.h; the two horizontal
+// lerps first).  Values are not rescaled: sums change.
 template <int VEC>
 __global__ __launch_bounds__(256) void crowd_resize_bilinear_kernel(const float* __restrict__ in, int h, int w, int P,
                                                                     int64_t runs, float* __restrict__ out) {

@@ -971,8 +971,10 @@ class Experiment(ABC):
 
     def regression_validation_summaries(self, normalized=False):
         """DNN and D on the train and validation batches, D's validation MAE relative to the DNN's (reference
-        age/srgan.py:52-71, driving/srgan.py:48-67; the image grids are out of scope)."""
-        train, validation = self.train_dataset_loader, self.validation_dataset_loader
+        age/srgan.py:52-71, driving/srgan.py:48-67; the image grids are out of scope).  A loader over a database
+        (``in_order``) is walked once in stored order, every example of the split as upstream; any other loader is iterated."""
+        train, validation = (loader.in_order() if hasattr(loader, 'in_order') else loader
+                             for loader in (self.train_dataset_loader, self.validation_dataset_loader))
         self.regression_evaluation_epoch(self.DNN, train, self.dnn_summary_writer, '2 Train Error', normalized=normalized)
         dnn_mae = self.regression_evaluation_epoch(self.DNN, validation, self.dnn_summary_writer, '1 Validation Error',
                                                    normalized=normalized)
