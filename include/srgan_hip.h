@@ -60,6 +60,7 @@ const char* srgan_last_error(void);
                                                  _blend_windows (full-image crowd inference on the device) */
 #define SRGAN_FEATURE_IMAGE_BATCHES 0x40u /* ABI 1.1, additive: srgan_image_batch_gather (training batches gathered on the
                                              device from a resident database of frames) */
+#define SRGAN_FEATURE_BATCH_NORM_TRAIN 0x80u /* ABI 1.1, additive: srgan_batch_norm_train_* (batch statistics, fp32 NCHW) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -274,6 +275,32 @@ int srgan_bn_act_bwd(const float* g, const float* x, const float* mean, const fl
                      const float* beta, int relu, float* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C,
                      int64_t HW, int64_t g_batch_stride, int64_t x_batch_stride, int64_t gx_batch_stride,
                      int accumulate_gx, int unscaled, void* stream);
+
+/* Training-mode batch normalisation (batch statistics) of an fp32 NCHW tensor, M = N * HW values per channel: the
+ * norm layers of the DCGAN generators, which the reference never freezes (srgan.py:171, age/models.py:16-21).
+ * _stats: ONE read of x -> mean[c], inv_std[c] = 1 / sqrt(biased variance + eps); the variance is summed from
+ *   deviations about the mean ((count, mean, M2) partials merged by Chan's formula), and the channel's workgroups meet
+ *   in the stream's workspace in a fixed order: bit-reproducible.  running_mean / running_var (each may be NULL)
+ *   become (1 - momentum) * running + momentum * statistic, with the UNBIASED variance M2 / (M - 1) as
+ *   torch.nn.BatchNorm2d; *num_batches_tracked (may be NULL) is incremented on the device.  2 <= M <= 2^24
+ *   (the partial counts are carried as fp32; more values per channel: SRGAN_ERANGE).
+ * _fwd: y = leaky((x - mean) * inv_std * gamma + beta, slope) in one pass (slope = 1: no activation).
+ * _bwd_reduce: g' = g * (pre-activation > 0 ? 1 : slope), the mask recomputed from x with the forward's arithmetic;
+ *   sums[c] = sum g', sums[C + c] = sum g' * xhat (xhat = (x - mean) * inv_std), in a fixed order; g_beta[c] += sums[c]
+ *   and g_gamma[c] += sums[C + c] when given (each may be NULL).
+ * _bwd_apply: gx = gamma * inv_std * (g' - sums[c] / M - xhat * sums[C + c] / M).
+ * Nothing but x, mean and inv_std is kept between the passes. */
+int srgan_batch_norm_train_stats(const float* x, float* mean, float* inv_std, float* running_mean, float* running_var,
+                                 int64_t* num_batches_tracked, float momentum, float eps, int32_t N, int32_t C, int64_t HW,
+                                 void* stream);
+int srgan_batch_norm_train_fwd(const float* x, const float* mean, const float* inv_std, const float* gamma, const float* beta,
+                               float slope, float* y, int32_t N, int32_t C, int64_t HW, void* stream);
+int srgan_batch_norm_train_bwd_reduce(const float* g, const float* x, const float* mean, const float* inv_std, const float* gamma,
+                                      const float* beta, float slope, float* sums, float* g_gamma, float* g_beta, int32_t N,
+                                      int32_t C, int64_t HW, void* stream);
+int srgan_batch_norm_train_bwd_apply(const float* g, const float* x, const float* mean, const float* inv_std, const float* gamma,
+                                     const float* beta, float slope, const float* sums, float* gx, int32_t N, int32_t C, int64_t HW,
+                                     void* stream);
 
 /* out[c] (=,+=) scale[c] * sum_{n,i} a[n,c,i] * ((b ? b[n,c,i] : 1) - mean[c])  (b, mean, scale optional).
  * Bias / batch-norm parameter gradients; with N = 1, C = batch it is the per-example dot product over C*H*W of

@@ -67,6 +67,10 @@ SIGNATURES = {
     'srgan_bn_act_bwd': ([vp, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, i32, i32, i64, i64, i64, i64, ctypes.c_int,
                           ctypes.c_int, vp],
                          ctypes.c_int),
+    'srgan_batch_norm_train_stats': ([vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, i64, vp], ctypes.c_int),
+    'srgan_batch_norm_train_fwd': ([vp, vp, vp, vp, vp, f32, vp, i32, i32, i64, vp], ctypes.c_int),
+    'srgan_batch_norm_train_bwd_reduce': ([vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i64, vp], ctypes.c_int),
+    'srgan_batch_norm_train_bwd_apply': ([vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i64, vp], ctypes.c_int),
     'srgan_chan_reduce': ([vp, vp, vp, vp, vp, i32, i32, i64, ctypes.c_int, vp], ctypes.c_int),
     'srgan_row_max': ([vp, vp, i32, i32, vp], ctypes.c_int),
     'srgan_nearest_bin_onehot': ([vp, vp, vp, i32, i32, vp], ctypes.c_int),

@@ -6,7 +6,10 @@ from .. import functional as F
 from .. import nn
 from ..utility import seed_all
 
-batch_norm = False            # the reference's module-level switch (age/models.py:13): no batch-norm anywhere
+# The reference's module-level switch (age/models.py:13).  Read when a stage is BUILT (``bn=None``), so setting it takes
+# effect; ``Generator(batch_norm=...)`` / ``Discriminator(batch_norm=...)`` override it per instance
+# (``settings.generator_batch_norm`` / ``settings.discriminator_batch_norm``).
+batch_norm = False
 LEAK = 0.05
 
 
@@ -19,17 +22,21 @@ def _pair(value):
     return (value, value) if isinstance(value, int) else tuple(value)
 
 
-def _stage(layer_class, c_in, c_out, k_size, stride, pad, bn):
-    """``Sequential(layer[, BatchNorm2d])`` -- the reference wraps every layer like this, so keys read ``layerN.0.weight``."""
-    return nn.Sequential(*([layer_class(c_in, c_out, k_size, stride, pad)] + ([nn.BatchNorm2d(c_out)] if bn else [])))
+def _stage(layer_class, norm_class, c_in, c_out, k_size, stride, pad, bn):
+    """``Sequential(layer[, norm])`` -- the reference wraps every layer like this, so keys read ``layerN.0.weight``."""
+    if bn is None:
+        bn = batch_norm
+    return nn.Sequential(*([layer_class(c_in, c_out, k_size, stride, pad)] + ([norm_class(c_out)] if bn else [])))
 
 
-def transpose_convolution(c_in, c_out, k_size, stride=2, pad=1, bn=batch_norm):
-    return _stage(nn.ConvTranspose2d, c_in, c_out, k_size, stride, pad, bn)
+def transpose_convolution(c_in, c_out, k_size, stride=2, pad=1, bn=None):
+    """The generator's stage: its norm uses batch statistics in training mode (the reference never freezes G, srgan.py:171)."""
+    return _stage(nn.ConvTranspose2d, nn.BatchStatNorm2d, c_in, c_out, k_size, stride, pad, bn)
 
 
-def convolution(c_in, c_out, k_size, stride=2, pad=1, bn=batch_norm):
-    return _stage(nn.Conv2d, c_in, c_out, k_size, stride, pad, bn)
+def convolution(c_in, c_out, k_size, stride=2, pad=1, bn=None):
+    """The discriminator's stage: its norm is frozen (the reference freezes D and DNN at every step, srgan.py:261,276)."""
+    return _stage(nn.Conv2d, nn.BatchNorm2d, c_in, c_out, k_size, stride, pad, bn)
 
 
 def _seed_kernel(image_size):
@@ -40,14 +47,14 @@ def _seed_kernel(image_size):
 class Generator(nn.Module):
     """z -> ``fc``: convT(k = S/16) -> ``layer1..3``: convT k4 s2 p1 + leaky 0.05 -> ``layer4``: convT k4 s2 p1 -> tanh."""
 
-    def __init__(self, z_dim=256, image_size=128, conv_dim=64):
+    def __init__(self, z_dim=256, image_size=128, conv_dim=64, batch_norm=None):
         seed_all(0)
         super().__init__()
         widths = (conv_dim * 8, conv_dim * 4, conv_dim * 2, conv_dim, 3)
         self.fc = transpose_convolution(z_dim, widths[0], _seed_kernel(image_size), 1, 0, bn=False)
         for index in range(1, 5):
             setattr(self, f'layer{index}', transpose_convolution(widths[index - 1], widths[index], 4,
-                                                                 **({'bn': False} if index == 4 else {})))
+                                                                 bn=False if index == 4 else batch_norm))
         self.input_size = z_dim
 
     def forward(self, z):
@@ -56,7 +63,10 @@ class Generator(nn.Module):
             return self._forward_blocked(z, active_code())
         out = self.fc(F.view(z, (z.shape[0], z.shape[1], 1, 1)))
         for stage in (self.layer1, self.layer2, self.layer3):
-            out = F.leaky_relu(stage(out), LEAK)
+            if len(stage) == 2:       # convT -> norm with the leaky-ReLU fused into the norm's pass
+                out = stage[1](stage[0](out), slope=LEAK)
+            else:
+                out = F.leaky_relu(stage(out), LEAK)
         return F.tanh(self.layer4(out))
 
     def _forward_blocked(self, z, code):
@@ -75,14 +85,14 @@ class Generator(nn.Module):
 class Discriminator(nn.Module):
     """``layer1..4``: conv k4 s2 p1 + leaky 0.05; ``features`` = the flattened result; ``layer5``: conv k = S/16 -> outputs."""
 
-    def __init__(self, image_size=128, conv_dim=64, number_of_outputs=1):
+    def __init__(self, image_size=128, conv_dim=64, number_of_outputs=1, batch_norm=None):
         seed_all(0)
         super().__init__()
         self.number_of_outputs = number_of_outputs
         widths = (3, conv_dim, conv_dim * 2, conv_dim * 4, conv_dim * 8)
         for index in range(1, 5):
             setattr(self, f'layer{index}', convolution(widths[index - 1], widths[index], 4,
-                                                       **({'bn': False} if index == 1 else {})))
+                                                       bn=False if index == 1 else batch_norm))
         self.layer5 = convolution(widths[4], number_of_outputs, _seed_kernel(image_size), 1, 0, False)
         self.features = None
 

@@ -41,14 +41,16 @@ class AgeExperiment(Experiment):
     def model_setup(self):
         """reference age/srgan.py:42-51 (``pretrained=True`` VGG weights need a download: load a checkpoint)."""
         size = self._size()
+        g_norm = getattr(self.settings, 'generator_batch_norm', False)
+        d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
         if model_architecture == 'vgg':
-            self.G = Generator(image_size=size)
+            self.G = Generator(image_size=size, batch_norm=g_norm)
             self.D = vgg16(num_classes=1, image_size=size)
             self.DNN = vgg16(num_classes=1, image_size=size)
         else:
-            self.G = Generator(image_size=size)
-            self.D = Discriminator(image_size=size)
-            self.DNN = Discriminator(image_size=size)
+            self.G = Generator(image_size=size, batch_norm=g_norm)
+            self.D = Discriminator(image_size=size, batch_norm=d_norm)
+            self.DNN = Discriminator(image_size=size, batch_norm=d_norm)
 
     def validation_summaries(self, step):
         """MAE / MSE of DNN and D on the train and validation batches (reference age/srgan.py:52-71,92-107)."""

@@ -77,6 +77,19 @@ int pointwise_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, i
                               const float* x_base, const float* gy_base, float* gw_base, int64_t flops_mn, int64_t pixels,
                               int64_t elements, int64_t partial_floats, hipStream_t stream);
 
+// batch_norm_train.hip: training-mode batch normalisation (batch statistics), fp32 NCHW.  `sums` = [2][C]: sum g', sum g' * xhat.
+int bn_train_stats_run(const float* x, float* mean, float* inv_std, float* running_mean, float* running_var,
+                       int64_t* num_batches_tracked, float momentum, float eps, int32_t N, int32_t C, int64_t HW,
+                       hipStream_t stream);
+int bn_train_fwd_run(const float* x, const float* mean, const float* inv_std, const float* gamma, const float* beta, float slope,
+                     float* y, int32_t N, int32_t C, int64_t HW, hipStream_t stream);
+int bn_train_bwd_reduce_run(const float* g, const float* x, const float* mean, const float* inv_std, const float* gamma,
+                            const float* beta, float slope, float* sums, float* g_gamma, float* g_beta, int32_t N, int32_t C,
+                            int64_t HW, hipStream_t stream);
+int bn_train_bwd_apply_run(const float* g, const float* x, const float* mean, const float* inv_std, const float* gamma,
+                           const float* beta, float slope, const float* sums, float* gx, int32_t N, int32_t C, int64_t HW,
+                           hipStream_t stream);
+
 // stem7x7.hip: the DenseNet stem's 7x7 / stride 2 convolution, all three passes.
 bool stem7x7_geometry(int32_t C, int32_t K, int32_t R, int32_t S, int32_t sh, int32_t sw, int32_t ph, int32_t pw);
 int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int64_t y_bs, int32_t N, int32_t H, int32_t W,

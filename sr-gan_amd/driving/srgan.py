@@ -33,9 +33,11 @@ class DrivingExperiment(Experiment):
                                                                 seed=101, dp=self.dp, pool=1)
 
     def model_setup(self):
-        self.G = Generator(image_size=self.image_size)
-        self.D = Discriminator(image_size=self.image_size)
-        self.DNN = Discriminator(image_size=self.image_size)
+        g_norm = getattr(self.settings, 'generator_batch_norm', False)
+        d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
+        self.G = Generator(image_size=self.image_size, batch_norm=g_norm)
+        self.D = Discriminator(image_size=self.image_size, batch_norm=d_norm)
+        self.DNN = Discriminator(image_size=self.image_size, batch_norm=d_norm)
 
     def validation_summaries(self, step):
         """MAE / NMAE / MSE of DNN and D on the train and validation batches (reference driving/srgan.py:48-67,87-104)."""

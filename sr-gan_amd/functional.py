@@ -383,6 +383,53 @@ def batch_norm_eval(x, mean, inv_std, gamma, beta, relu=False):
     return out
 
 
+def batch_norm_train(x, gamma, beta, running_mean, running_var, momentum, eps, slope=1.0, num_batches_tracked=None):
+    """Training-mode batch-norm fused with the leaky-ReLU that follows it (``slope`` 1: none):
+    y = leaky((x - mean_B) * rsqrt(var_B + eps) * gamma + beta, slope) with the statistics of THIS batch, two launches
+    (statistics: one read of x; apply: one read, one write).  ``running_mean`` / ``running_var`` (torch tensors or None)
+    are updated on the device as ``torch.nn.BatchNorm2d`` does (unbiased variance), ``num_batches_tracked`` incremented.
+    The backward is two launches (the per-channel sums = gamma / beta gradients; the input gradient) and keeps nothing
+    but x, the batch mean and inv_std; the activation mask is recomputed from x.  FIRST ORDER ONLY: the generator is
+    never differentiated twice (the penalty chain differentiates D w.r.t. detached interpolates, reference
+    srgan.py:365-370), so a recorded backward through this op raises instead of dropping the statistics' terms."""
+    n, c, hw = _dims_nchw(x.shape)
+    if n * hw < 2:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {list(x.shape)}')
+    if momentum is None:
+        raise NotImplementedError('batch_norm_train: momentum=None (cumulative moving average) is not implemented')
+    stats = _empty((2, c), x.data)               # batch mean, inv_std
+    data = _empty(x.shape, x.data)
+    slope = float(slope)
+    _call('srgan_batch_norm_train_stats', _ptr(x), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(running_mean),
+          _ptr(running_var), _ptr(num_batches_tracked), float(momentum), float(eps), n, c, hw, _stream())
+    _call('srgan_batch_norm_train_fwd', _ptr(x), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(gamma), _ptr(beta), slope,
+          data.data_ptr(), n, c, hw, _stream())
+    out = _out(data, (x, gamma, beta), None, 'batch_norm_train')
+    if out.node is None:
+        return out                               # (no_grad: the statistics are dropped with this frame)
+
+    def backward(g, needs):
+        if grad_enabled():
+            raise NotImplementedError('batch_norm_train has a first-order backward only: differentiating a gradient through '
+                                      'batch statistics (create_graph=True) is not implemented')
+        # both parameter sums are ADDED by the kernel: straight into the gradient arena when the sweep accumulates there
+        direct_gamma, direct_beta = needs[1] and accumulates_into(gamma), needs[2] and accumulates_into(beta)
+        sums = _empty((2, c), x.data)            # sum g' (= g_beta), sum g' * xhat (= g_gamma)
+        _call('srgan_batch_norm_train_bwd_reduce', _ptr(g), _ptr(x), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(gamma),
+              _ptr(beta), slope, sums.data_ptr(), gamma.grad_buffer.data_ptr() if direct_gamma else None,
+              beta.grad_buffer.data_ptr() if direct_beta else None, n, c, hw, _stream())
+        gx = None
+        if needs[0]:
+            gx = Var(_empty(x.shape, x.data))
+            _call('srgan_batch_norm_train_bwd_apply', _ptr(g), _ptr(x), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(gamma),
+                  _ptr(beta), slope, sums.data_ptr(), gx.data.data_ptr(), n, c, hw, _stream())
+        ggamma = Var(sums[1].view(gamma.shape)) if needs[1] and not direct_gamma else None
+        gbeta = Var(sums[0].view(beta.shape)) if needs[2] and not direct_beta else None
+        return gx, ggamma, gbeta
+    out.node.backward = backward
+    return out
+
+
 def chan_reduce(a, b=None, mean=None, scale=None, dims=None, like=None):
     """out[c] = scale[c] * sum_{n,i} a[n,c,i] * ((b or 1) - mean[c]) -> shape of ``like`` (default [C])."""
     if dims is None:

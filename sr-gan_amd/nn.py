@@ -69,6 +69,39 @@ class BatchNorm2d(nn.BatchNorm2d):
         return F.batch_norm_eval(x, mean, inv_std, P(self.weight), P(self.bias), relu=relu)
 
 
+class BatchStatNorm2d(BatchNorm2d):
+    """Batch-norm that is NOT frozen: in training mode it normalises with the statistics of the batch and updates the
+    running statistics, as ``torch.nn.BatchNorm2d`` does -- the norm layers of the DCGAN generators, which the reference
+    leaves in training mode (srgan.py:171; only D and DNN are frozen, :261,276).  Same parameters, buffers and
+    ``state_dict`` keys as ``BatchNorm2d``; in eval mode it IS ``BatchNorm2d``.  ``slope`` fuses the leaky-ReLU that
+    follows the layer into the pass (1: none)."""
+
+    def _statistics_changed(self):
+        """The running buffers are written by a kernel through raw pointers, which torch's version counters do not see:
+        bump them, so that ``_inverse_std`` refreshes its cached tensors (in place) at the next eval-mode forward."""
+        for buffer in (self.running_mean, self.running_var, self.num_batches_tracked):
+            if buffer is not None:
+                torch.autograd.graph.increment_version(buffer)
+
+    def train(self, mode=True):
+        if self.training and not mode:      # (a replayed HIP graph trains without passing through ``forward``)
+            self._statistics_changed()
+        return super().train(mode)
+
+    def forward(self, x, relu=False, slope=1.0):
+        if not self.training:
+            out = super().forward(x, relu=relu)
+            return out if relu or slope == 1.0 else F.leaky_relu(out, slope)
+        if relu:
+            slope = 0.0
+        if not self.track_running_stats or self.running_mean is None:
+            raise NotImplementedError('BatchStatNorm2d needs track_running_stats=True')
+        out = F.batch_norm_train(x, P(self.weight), P(self.bias), self.running_mean, self.running_var, self.momentum, self.eps,
+                                 slope=slope, num_batches_tracked=self.num_batches_tracked)
+        self._statistics_changed()
+        return out
+
+
 class ReLU(nn.Module):
     def __init__(self, inplace=False):
         super().__init__()

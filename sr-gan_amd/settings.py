@@ -33,6 +33,9 @@ DEFAULTS = (
     ('map_multiplier', 1e-6), ('map_directory_name', 'i1nn_maps'),
     # SGAN models
     ('number_of_bins', 10),
+    # DCGAN networks: the ``batch_norm`` switch of the reference's age / driving / crowd models.py, per network.  G's norm
+    # layers use batch statistics in training mode, D's and DNN's are frozen (reference srgan.py:171,261,276).
+    ('generator_batch_norm', False), ('discriminator_batch_norm', False),
 )
 
 # what ``local_setup`` shrinks on the reference author's laptop (settings.py:69-79)

@@ -382,6 +382,11 @@ class Experiment(ABC):
 
     def gpu_mode(self):
         """Moves each network into its flat parameter / gradient arena on this rank's device."""
+        if self.dp is not None and self.dp.world_size > 1 and self.G is not None and \
+                any(isinstance(module, nn.BatchStatNorm2d) for module in self.G.modules()):
+            # per-rank statistics and unsynchronised running buffers would silently differ from one device on the global batch
+            raise NotImplementedError('a generator with batch-statistics normalisation (settings.generator_batch_norm) runs on '
+                                      'one device only: statistics synchronised across the data-parallel ranks are future work')
         device = current_device()
         for module in (self.D, self.DNN, self.G):
             if getattr(module, '_srgan_arena', None) is None:
