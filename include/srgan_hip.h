@@ -61,6 +61,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_IMAGE_BATCHES 0x40u /* ABI 1.1, additive: srgan_image_batch_gather (training batches gathered on the
                                              device from a resident database of frames) */
 #define SRGAN_FEATURE_BATCH_NORM_TRAIN 0x80u /* ABI 1.1, additive: srgan_batch_norm_train_* (batch statistics, fp32 NCHW) */
+#define SRGAN_FEATURE_BLOCKED_BATCH_NORM 0x100u /* ABI 1.1, additive: srgan_h_batch_norm_* (batch statistics on blocked
+                                                  tensors, dtype 0 / 1 / 2) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -555,6 +557,35 @@ int srgan_h_conv_transpose4x4s2(const void* x, const void* packed, const float* 
 /* gw (fp32 [A][B][4][4]) += weight gradient from `small` [N, A, H/2, W/2] and `big` [N, B, H, W] (small_is_rows must be 1) */
 int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N, int32_t C_big, int32_t C_small, int32_t H, int32_t W,
                        int small_is_rows, int dtype, void* stream);
+
+/* Training-mode batch normalisation (batch statistics) of a BLOCKED tensor (SRGAN_FEATURE_BLOCKED_BATCH_NORM): logical
+ * shape [N, C, HW], dtype 0 (fp32, 4 channels per slot) / 1 (bf16) / 2 (fp16, 8 per slot), M = N * HW values per channel --
+ * the norm layers of a DCGAN generator that stays on the blocked data path.  mean / inv_std / gamma / beta / sums and the
+ * running buffers are fp32 [C] ([2][C] for sums); all arithmetic is fp32 on the stored elements converted exactly, and y / gx
+ * are rounded to nearest even once.  Channels beyond C in the last group are written as zeros.
+ * _stats: as srgan_batch_norm_train_stats -- ONE read of x, (count, mean, M2) partials merged by Chan's formula, the
+ *   workgroups of a channel group meeting in the stream's workspace in a fixed order (bit-reproducible; without a workspace
+ *   one workgroup per group); running_mean / running_var / num_batches_tracked (each may be NULL) updated on the device
+ *   with the unbiased variance and `momentum`.
+ * _fwd: y = leaky((x - mean) * inv_std * gamma + beta, slope) (slope = 1: no activation); eval mode passes the running
+ *   mean and its inverse standard deviation.
+ * _bwd_reduce: `s` is the PRE-MASKED gradient (already multiplied by the activation's derivative, the convention of the
+ *   blocked path): sums[c] = sum s, sums[C + c] = sum s * xhat (xhat = (x - mean) * inv_std), in a fixed order;
+ *   g_beta[c] += sums[c] and g_gamma[c] += sums[C + c] when given (each may be NULL).
+ * _bwd_apply: gx = gamma * inv_std * (s - sums[c] / M - xhat * sums[C + c] / M), times (ref > 0 ? 1 : slope) when `ref`
+ *   (the blocked tensor whose sign pattern masks x; may be NULL) is given.
+ * All four: unknown dtype, a NULL required pointer or M < 2: SRGAN_EINVAL; M > 2^24: SRGAN_ERANGE (before any device
+ * work).  Nothing but x, mean and inv_std is kept between the passes. */
+int srgan_h_batch_norm_stats(const void* x, float* mean, float* inv_std, float* running_mean, float* running_var,
+                             int64_t* num_batches_tracked, float momentum, float eps, int32_t N, int32_t C, int64_t HW,
+                             int32_t dtype, void* stream);
+int srgan_h_batch_norm_fwd(const void* x, const float* mean, const float* inv_std, const float* gamma, const float* beta,
+                           float slope, void* y, int32_t N, int32_t C, int64_t HW, int32_t dtype, void* stream);
+int srgan_h_batch_norm_bwd_reduce(const void* s, const void* x, const float* mean, const float* inv_std, float* sums,
+                                  float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW, int32_t dtype, void* stream);
+int srgan_h_batch_norm_bwd_apply(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma,
+                                 const float* sums, const void* ref, float slope, void* gx, int32_t N, int32_t C, int64_t HW,
+                                 int32_t dtype, void* stream);
 
 /* ---- measurement ---------------------------------------------------------------------------------------------
  * Between begin and end every contraction launch (conv / gemm passes) is bracketed by a pair of HIP events on

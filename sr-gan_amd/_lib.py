@@ -141,6 +141,10 @@ SIGNATURES = {
     'srgan_h_conv4x4s2': ([vp, vp, vp, vp, f32, ctypes.c_int, vp, i32, i32, i32, i32, i32, ctypes.c_int, vp], ctypes.c_int),
     'srgan_h_conv_transpose4x4s2': ([vp, vp, vp, vp, f32, ctypes.c_int, vp, i32, i32, i32, i32, i32, ctypes.c_int, vp], ctypes.c_int),
     'srgan_h_k4s2_wgrad': ([vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_int, ctypes.c_int, vp], ctypes.c_int),
+    'srgan_h_batch_norm_stats': ([vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, i64, i32, vp], ctypes.c_int),
+    'srgan_h_batch_norm_fwd': ([vp, vp, vp, vp, vp, f32, vp, i32, i32, i64, i32, vp], ctypes.c_int),
+    'srgan_h_batch_norm_bwd_reduce': ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp], ctypes.c_int),
+    'srgan_h_batch_norm_bwd_apply': ([vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i64, i32, vp], ctypes.c_int),
     'srgan_comm_available': ([], ctypes.c_int),
     'srgan_comm_unique_id': ([vp], ctypes.c_int),
     'srgan_comm_init': ([ctypes.POINTER(vp), i32, i32, vp], ctypes.c_int),

@@ -14,8 +14,13 @@ LEAK = 0.05
 
 
 def _blocked_stack_ok(network):
-    """The 16-bit path has the reference configuration: no batch-norm inside the stages (age/models.py:13)."""
-    return all(len(stage) == 1 for name, stage in network.named_children())
+    """The blocked path has the reference configuration -- no batch-norm inside the stages (age/models.py:13) -- or, for a
+    network built with ``blocked_batch_norm`` (the generator), stages ``[ConvTranspose2d, BatchStatNorm2d]``: the norm
+    with batch statistics has kernels on blocked tensors (``blocked16.batch_norm_train``), the frozen one has not."""
+    norms = getattr(network, 'blocked_batch_norm', False)
+    return all(len(stage) == 1 or (norms and len(stage) == 2 and isinstance(stage[0], nn.ConvTranspose2d) and
+                                   isinstance(stage[1], nn.BatchStatNorm2d))
+               for name, stage in network.named_children())
 
 
 def _pair(value):
@@ -47,9 +52,11 @@ def _seed_kernel(image_size):
 class Generator(nn.Module):
     """z -> ``fc``: convT(k = S/16) -> ``layer1..3``: convT k4 s2 p1 + leaky 0.05 -> ``layer4``: convT k4 s2 p1 -> tanh."""
 
-    def __init__(self, z_dim=256, image_size=128, conv_dim=64, batch_norm=None):
+    def __init__(self, z_dim=256, image_size=128, conv_dim=64, batch_norm=None, blocked_batch_norm=False):
         seed_all(0)
         super().__init__()
+        # with norm layers, stay on the blocked data path under F.storage_dtype (settings.blocked_batch_norm; off: the fp32 graph)
+        self.blocked_batch_norm = bool(blocked_batch_norm)
         widths = (conv_dim * 8, conv_dim * 4, conv_dim * 2, conv_dim, 3)
         self.fc = transpose_convolution(z_dim, widths[0], _seed_kernel(image_size), 1, 0, bn=False)
         for index in range(1, 5):
@@ -78,7 +85,10 @@ class Generator(nn.Module):
         else:
             h = B.seed_conv_transpose(B.pack(F.view(z, (z.shape[0], z.shape[1])), code), self.fc[0])
         for stage in (self.layer1, self.layer2, self.layer3):
-            h = B.conv_transpose4x4s2(h, stage[0], slope=LEAK)
+            if len(stage) == 2:       # convT -> norm with the leaky-ReLU fused into the norm's pass, all on blocked tensors
+                h = stage[1](B.conv_transpose4x4s2(h, stage[0]), slope=LEAK)
+            else:
+                h = B.conv_transpose4x4s2(h, stage[0], slope=LEAK)
         return F.tanh(B.unpack(B.conv_transpose4x4s2(h, self.layer4[0])))
 
 

@@ -17,6 +17,6 @@ class AgeSganExperiment(SganExperiment, AgeExperiment):
 
     def model_setup(self):
         size = self._size()
-        self.G = Generator(image_size=size, batch_norm=getattr(self.settings, 'generator_batch_norm', False))
+        self.G = Generator(image_size=size, **self.generator_norm_arguments())
         d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
         self.D, self.DNN = (Discriminator(image_size=size, number_of_outputs=BIN_LOGITS, batch_norm=d_norm) for _ in range(2))

@@ -41,14 +41,13 @@ class AgeExperiment(Experiment):
     def model_setup(self):
         """reference age/srgan.py:42-51 (``pretrained=True`` VGG weights need a download: load a checkpoint)."""
         size = self._size()
-        g_norm = getattr(self.settings, 'generator_batch_norm', False)
         d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
         if model_architecture == 'vgg':
-            self.G = Generator(image_size=size, batch_norm=g_norm)
+            self.G = Generator(image_size=size, **self.generator_norm_arguments())
             self.D = vgg16(num_classes=1, image_size=size)
             self.DNN = vgg16(num_classes=1, image_size=size)
         else:
-            self.G = Generator(image_size=size, batch_norm=g_norm)
+            self.G = Generator(image_size=size, **self.generator_norm_arguments())
             self.D = Discriminator(image_size=size, batch_norm=d_norm)
             self.DNN = Discriminator(image_size=size, batch_norm=d_norm)
 

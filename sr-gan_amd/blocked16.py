@@ -617,3 +617,85 @@ def _weight_gradient(shadow, module, x_side, y_side, into):
         outputs, inputs = module.weight.shape[0], module.weight.numel() // module.weight.shape[0]
         _call('srgan_h_linear_wgrad', y_side.data.data_ptr(), x_side.data.data_ptr(), into.data_ptr(), xm.n, outputs, xm.c,
               outputs, inputs, inputs, 1, 1, shadow.plane, xm.code, stream)
+
+
+# ------------------------------------------------------------------------------------------------ batch statistics
+def _norm_tensors(x, gamma, beta):
+    meta = x.meta
+    if meta is None or meta.plane != 1:
+        raise ValueError('blocked16 batch norm takes a blocked [N, C, H, W] tensor')
+    if gamma.data.numel() != meta.c or beta.data.numel() != meta.c:
+        raise ValueError(f'blocked16 batch norm: input has {meta.c} channels, the layer has {gamma.data.numel()}')
+    return meta
+
+
+def _activated(meta, data, slope):
+    """The ``Blocked`` of ``leaky(..., slope)`` written into ``data``: an activated tensor is its own mask."""
+    out_meta = Blocked(meta.n, meta.c, meta.h, meta.w, meta.code)
+    if slope != 1.0:
+        out_meta.mask_ref, out_meta.slope = data, slope
+    return out_meta
+
+
+def batch_norm_train(x, gamma, beta, running_mean, running_var, momentum, eps, slope=1.0, num_batches_tracked=None):
+    """``F.batch_norm_train`` on a blocked tensor of any code (csrc/blocked16_batch_norm.hip): y = leaky((x - mean_B) *
+    rsqrt(var_B + eps) * gamma + beta, slope) with the statistics of THIS batch, the running buffers updated on the device;
+    two launches forward, two backward, nothing kept but x, the batch mean and inv_std.  The output is its own mask
+    (``slope`` != 1), so the gradient arrives pre-masked and the backward applies only the mask of ``x`` itself.  gamma / beta
+    gradients go straight into the fp32 arena.  FIRST ORDER ONLY, as the NCHW op."""
+    meta = _norm_tensors(x, gamma, beta)
+    n, c, hw, code = meta.n, meta.c, meta.h * meta.w, meta.code
+    if n * hw < 2:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {[n, c, meta.h, meta.w]}')
+    if momentum is None:
+        raise NotImplementedError('batch_norm_train: momentum=None (cumulative moving average) is not implemented')
+    stats = F._empty((2, c), x.data)               # batch mean, inv_std
+    data = _new(n, c, meta.h, meta.w, code, x.data.device)
+    slope = float(slope)
+    _call('srgan_h_batch_norm_stats', x.data.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(running_mean),
+          _ptr(running_var), _ptr(num_batches_tracked), float(momentum), float(eps), n, c, hw, code, F._stream())
+    _call('srgan_h_batch_norm_fwd', x.data.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), gamma.data.data_ptr(),
+          beta.data.data_ptr(), slope, data.data_ptr(), n, c, hw, code, F._stream())
+    out = F._out(data, (x, gamma, beta), None, 'h_batch_norm_train')
+    out.meta = _activated(meta, data, slope)
+    if out.node is None:
+        return out                                 # (no_grad: the statistics are dropped with this frame)
+
+    def backward(s, needs):
+        if F.grad_enabled():
+            raise NotImplementedError('batch_norm_train has a first-order backward only: differentiating a gradient through '
+                                      'batch statistics (create_graph=True) is not implemented')
+        for need, parameter in ((needs[1], gamma), (needs[2], beta)):
+            if need and not accumulates_into(parameter):
+                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
+                                          'only (straight into the fp32 gradient arena)')
+        sums = F._empty((2, c), x.data)            # sum s (= g_beta), sum s * xhat (= g_gamma)
+        _call('srgan_h_batch_norm_bwd_reduce', s.data.data_ptr(), x.data.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+              sums.data_ptr(), gamma.grad_buffer.data_ptr() if needs[1] else None, beta.grad_buffer.data_ptr() if needs[2] else None,
+              n, c, hw, code, F._stream())
+        gx = None
+        if needs[0]:
+            gx = Var(_new(n, c, meta.h, meta.w, code, x.data.device))
+            _call('srgan_h_batch_norm_bwd_apply', s.data.data_ptr(), x.data.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+                  gamma.data.data_ptr(), sums.data_ptr(), _ptr(meta.mask_ref), float(meta.slope), gx.data.data_ptr(), n, c, hw, code,
+                  F._stream())
+            gx.meta = meta                          # a pre-masked gradient of x
+        return gx, None, None
+    out.node.backward = backward
+    return out
+
+
+def batch_norm_eval(x, mean, inv_std, gamma, beta, slope=1.0):
+    """The forward kernel with given statistics (``nn.BatchStatNorm2d`` in eval mode on a blocked tensor): forward only."""
+    meta = _norm_tensors(x, gamma, beta)
+    data = _new(meta.n, meta.c, meta.h, meta.w, meta.code, x.data.device)
+    slope = float(slope)
+    _call('srgan_h_batch_norm_fwd', x.data.data_ptr(), mean.data.data_ptr(), inv_std.data.data_ptr(), gamma.data.data_ptr(),
+          beta.data.data_ptr(), slope, data.data_ptr(), meta.n, meta.c, meta.h * meta.w, meta.code, F._stream())
+
+    def backward(s, needs):
+        raise NotImplementedError('blocked16.batch_norm_eval is forward only: a BatchStatNorm2d on blocked tensors is '
+                                  'differentiated in training mode')
+    out = F._out(data, (x, gamma, beta), backward, 'h_batch_norm_eval')
+    out.meta = _activated(meta, data, slope)
+    return out

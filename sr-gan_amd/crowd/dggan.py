@@ -15,7 +15,7 @@ class CrowdDgganExperiment(CrowdExperiment):
 
     def model_setup(self):
         size = self.settings.image_patch_size
-        self.G = DCGenerator(image_size=size, batch_norm=getattr(self.settings, 'generator_batch_norm', False))
+        self.G = DCGenerator(image_size=size, **self.generator_norm_arguments())
         self.D = KnnDenseNetCatDggan(image_size=size)
         self.DNN = KnnDenseNetCatDggan(image_size=size)
 

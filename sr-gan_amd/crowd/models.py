@@ -21,8 +21,9 @@ FUSED_STEM_POOL = True     # norm0 -> relu0 -> pool0 of the DenseNet stem as one
 class DCGenerator(_DCGANGenerator):
     """reference crowd/models.py:127-147 (defaults to 224x224)."""
 
-    def __init__(self, z_dim=256, image_size=224, conv_dim=64, batch_norm=None):
-        super().__init__(z_dim=z_dim, image_size=image_size, conv_dim=conv_dim, batch_norm=batch_norm)
+    def __init__(self, z_dim=256, image_size=224, conv_dim=64, batch_norm=None, blocked_batch_norm=False):
+        super().__init__(z_dim=z_dim, image_size=image_size, conv_dim=conv_dim, batch_norm=batch_norm,
+                         blocked_batch_norm=blocked_batch_norm)
 
 
 class JointDCDiscriminator(nn.Module):

@@ -26,7 +26,7 @@ class CrowdSganExperiment(SganExperiment, CrowdExperiment):
     def model_setup(self):
         size = self.settings.image_patch_size
         bins = self.settings.number_of_bins
-        self.G = DCGenerator(image_size=size, batch_norm=getattr(self.settings, 'generator_batch_norm', False))
+        self.G = DCGenerator(image_size=size, **self.generator_norm_arguments())
         self.D = JointDCDiscriminator(image_size=size, number_of_outputs=bins)
         self.DNN = JointDCDiscriminator(image_size=size, number_of_outputs=bins)
 

@@ -51,7 +51,7 @@ class CrowdExperiment(Experiment):
         """reference crowd/srgan.py:92-96 (``pretrained=True`` there downloads torchvision weights; offline the
         networks are freshly initialised and a checkpoint can be loaded instead)."""
         size = self.settings.image_patch_size
-        self.G = DCGenerator(image_size=size, batch_norm=getattr(self.settings, 'generator_batch_norm', False))
+        self.G = DCGenerator(image_size=size, **self.generator_norm_arguments())
         self.D = KnnDenseNetCat(image_size=size)
         self.DNN = KnnDenseNetCat(image_size=size)
 

@@ -1,6 +1,8 @@
 // batch_norm_train.hip -- training-mode batch normalisation (batch statistics) for fp32 NCHW tensors: the DCGAN
 // generators' norm layers, which the reference never freezes (srgan.py:171; age/models.py:16-21 with batch_norm on).
 //
+// (The same four passes on blocked bf16 / fp16 / fp32 tensors: blocked16_batch_norm.hip; what the two share: bn_train.h.)
+//
 // Four HBM-bound kernels, all on one decomposition: a workgroup owns channel c of a group of images [n0, n1), lanes
 // along the plane (float4 when HW % 4 == 0 and the tensors are 16-byte aligned, scalars otherwise):
 //   stats       one read of x  -> mean, inv_std (+ the running buffers and num_batches_tracked)
@@ -15,6 +17,7 @@
 // workspace in part order (split_finish.h: no fp32 atomics on data, the same bits on every run).
 // Roofline: HBM; algorithmic bytes = 4 * elements per tensor read or written.
 #include <initializer_list>
+#include "bn_train.h"
 #include "common.h"
 #include "launchers.h"
 #include "split_finish.h"
@@ -22,35 +25,6 @@
 namespace srgan {
 
 __device__ unsigned int g_bn_train_tickets[SPLIT_TICKET_SETS * ROW_FINISH_ROWS];
-
-// The pre-activation, shared by the forward and both backward kernels: the leaky mask is bit-consistent.
-__device__ __forceinline__ float bn_train_pre(float x, float mean, float a, float beta) { return fmaf(x - mean, a, beta); }
-__device__ __forceinline__ float bn_train_scale(float inv_std, float gamma) { return __fmul_rn(inv_std, gamma); }
-
-struct Moments { float n, mean, m2; };      // count (a float: exact up to 2^24, the entry point's limit), mean, sum of squared deviations about it
-
-// Chan et al.: the moments of the union of two disjoint sets.
-__device__ __forceinline__ Moments merge_moments(const Moments& a, const Moments& b) {
-  if (b.n == 0.f) return a;
-  if (a.n == 0.f) return b;
-  const float n = a.n + b.n, delta = b.mean - a.mean, w = b.n / n;
-  return Moments{n, fmaf(delta, w, a.mean), a.m2 + b.m2 + delta * delta * a.n * w};
-}
-
-// The 256 threads' moments in a fixed tree (shuffle-down inside each wave, then the four waves in order): thread 0.
-__device__ __forceinline__ Moments block_moments_256(Moments v, Moments* scratch4) {
-#pragma unroll
-  for (int offset = 32; offset > 0; offset >>= 1) {
-    const Moments other{__shfl_down(v.n, offset, 64), __shfl_down(v.mean, offset, 64), __shfl_down(v.m2, offset, 64)};
-    v = merge_moments(v, other);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) scratch4[wave] = v;
-  __syncthreads();
-  Moments total{0.f, 0.f, 0.f};
-  if (threadIdx.x == 0) total = merge_moments(merge_moments(scratch4[0], scratch4[1]), merge_moments(scratch4[2], scratch4[3]));
-  return total;
-}
 
 // Offset of element `idx` (in units of W floats) of the workgroup's chunk: channel c of images n0, n0 + 1, ...
 template <int W>
@@ -247,15 +221,6 @@ __global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __
     }
     store_run<W>(gx + at, gv);
   });
-}
-
-// Images per workgroup: ~2048 workgroups of at least 4096 elements where the shape allows it (as srgan_bn_act_bwd).
-static int images_per_workgroup(int N, int C, int64_t HW) {
-  int per = 1;
-  while (per < N && ((int64_t)C * ((N + per - 1) / per) > 2048 || (int64_t)per * HW < 4096) &&
-         (int64_t)C * ((N + 2 * per - 1) / (2 * per)) >= 1024)
-    per *= 2;
-  return per;
 }
 
 static bool vectorisable(int64_t HW, std::initializer_list<const void*> tensors) {

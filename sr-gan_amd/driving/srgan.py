@@ -33,9 +33,8 @@ class DrivingExperiment(Experiment):
                                                                 seed=101, dp=self.dp, pool=1)
 
     def model_setup(self):
-        g_norm = getattr(self.settings, 'generator_batch_norm', False)
         d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
-        self.G = Generator(image_size=self.image_size, batch_norm=g_norm)
+        self.G = Generator(image_size=self.image_size, **self.generator_norm_arguments())
         self.D = Discriminator(image_size=self.image_size, batch_norm=d_norm)
         self.DNN = Discriminator(image_size=self.image_size, batch_norm=d_norm)
 

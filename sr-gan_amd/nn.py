@@ -89,6 +89,8 @@ class BatchStatNorm2d(BatchNorm2d):
         return super().train(mode)
 
     def forward(self, x, relu=False, slope=1.0):
+        if x.meta is not None:
+            return self._forward_blocked(x, 0.0 if relu else slope)
         if not self.training:
             out = super().forward(x, relu=relu)
             return out if relu or slope == 1.0 else F.leaky_relu(out, slope)
@@ -97,6 +99,20 @@ class BatchStatNorm2d(BatchNorm2d):
         if not self.track_running_stats or self.running_mean is None:
             raise NotImplementedError('BatchStatNorm2d needs track_running_stats=True')
         out = F.batch_norm_train(x, P(self.weight), P(self.bias), self.running_mean, self.running_var, self.momentum, self.eps,
+                                 slope=slope, num_batches_tracked=self.num_batches_tracked)
+        self._statistics_changed()
+        return out
+
+    def _forward_blocked(self, x, slope):
+        """The same layer on a tensor in the blocked layout (``blocked16``, any code): training mode differentiable to first
+        order, eval mode -- the forward kernel with the cached tensors of ``_inverse_std`` -- forward only."""
+        from . import blocked16 as B
+        if not self.training:
+            inv_std, mean = self._inverse_std()
+            return B.batch_norm_eval(x, mean, inv_std, P(self.weight), P(self.bias), slope=slope)
+        if not self.track_running_stats or self.running_mean is None:
+            raise NotImplementedError('BatchStatNorm2d needs track_running_stats=True')
+        out = B.batch_norm_train(x, P(self.weight), P(self.bias), self.running_mean, self.running_var, self.momentum, self.eps,
                                  slope=slope, num_batches_tracked=self.num_batches_tracked)
         self._statistics_changed()
         return out

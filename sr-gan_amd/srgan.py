@@ -380,6 +380,15 @@ class Experiment(ABC):
         for module in (self.D, self.DNN, self.G):
             module.eval()
 
+    def generator_norm_arguments(self):
+        """The norm-layer arguments of a DCGAN generator, for every ``model_setup`` that builds one:
+        ``settings.generator_batch_norm`` (norm layers with batch statistics) and ``settings.blocked_batch_norm`` (such a
+        generator stays on the blocked data path that ``settings.storage_dtype`` / ``settings.blocked_fp32`` select; without
+        either of them it changes nothing).  The latter is read with ``getattr`` and defaults to off: with it off the
+        generator with norm layers keeps the fp32 graph, which the 16-bit storage test of the batch-norm step pins."""
+        return dict(batch_norm=getattr(self.settings, 'generator_batch_norm', False),
+                    blocked_batch_norm=getattr(self.settings, 'blocked_batch_norm', False))
+
     def gpu_mode(self):
         """Moves each network into its flat parameter / gradient arena on this rank's device."""
         if self.dp is not None and self.dp.world_size > 1 and self.G is not None and \
