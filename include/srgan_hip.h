@@ -63,6 +63,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_BATCH_NORM_TRAIN 0x80u /* ABI 1.1, additive: srgan_batch_norm_train_* (batch statistics, fp32 NCHW) */
 #define SRGAN_FEATURE_BLOCKED_BATCH_NORM 0x100u /* ABI 1.1, additive: srgan_h_batch_norm_* (batch statistics on blocked
                                                   tensors, dtype 0 / 1 / 2) */
+#define SRGAN_FEATURE_BLOCKED_FROZEN_NORM 0x200u /* ABI 1.1, additive: srgan_h_frozen_norm_bwd (the backward, to first and
+                                                   second order, of a norm with given statistics on blocked tensors) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -586,6 +588,24 @@ int srgan_h_batch_norm_bwd_reduce(const void* s, const void* x, const float* mea
 int srgan_h_batch_norm_bwd_apply(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma,
                                  const float* sums, const void* ref, float slope, void* gx, int32_t N, int32_t C, int64_t HW,
                                  int32_t dtype, void* stream);
+/* The backward of a norm with GIVEN statistics -- the frozen norm layers of the DCGAN discriminators, y = (x - mean) * inv_std *
+ * gamma + beta, whose forward is srgan_h_batch_norm_fwd with the running statistics -- on BLOCKED tensors
+ * (SRGAN_FEATURE_BLOCKED_FROZEN_NORM): a per-channel affine map, so ONE pass reads `s` once (and `x`, `ref` once when needed)
+ * and writes gx once:
+ *   gx = s * gamma[c] * inv_std[c], times (ref > 0 ? 1 : slope) when `ref` is given;
+ *   g_gamma[c] += inv_std[c] * sum_{n,i} s * (x - mean[c]);     g_beta[c] += sum_{n,i} s.
+ * Each of gx, g_gamma, g_beta may be NULL (not all three); mean may be NULL (= zero); x is needed only with g_gamma.  `s` is
+ * used as it arrives (PRE-MASKED by the layer's own activation, as everywhere on the blocked path); `ref` / `slope` are the
+ * mask of the tensor x itself, as in srgan_h_batch_norm_bwd_apply.  The same call is the recorded backward (gx alone) and the
+ * double backward (s = the incoming cotangent, x = the first sweep's gradient, mean = NULL: gx and g_gamma in one pass).
+ * fp32 arithmetic on the stored elements, gx rounded to nearest even once, channels beyond C in the last group written as
+ * zeros; the per-channel sums of several workgroups meet in the stream's workspace in a fixed order (bit-reproducible; without
+ * a workspace one workgroup per channel group).  Before any device work: unknown dtype, NULL s / inv_std / gamma, all three
+ * outputs NULL, or g_gamma without x: SRGAN_EINVAL; more than max_tensor_elements (N * C * HW): SRGAN_ERANGE.  M = N * HW = 1
+ * is legal (nothing is divided by a count). */
+int srgan_h_frozen_norm_bwd(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma,
+                            const void* ref, float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW,
+                            int32_t dtype, void* stream);
 
 /* ---- measurement ---------------------------------------------------------------------------------------------
  * Between begin and end every contraction launch (conv / gemm passes) is bracketed by a pair of HIP events on

@@ -145,6 +145,7 @@ SIGNATURES = {
     'srgan_h_batch_norm_fwd': ([vp, vp, vp, vp, vp, f32, vp, i32, i32, i64, i32, vp], ctypes.c_int),
     'srgan_h_batch_norm_bwd_reduce': ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp], ctypes.c_int),
     'srgan_h_batch_norm_bwd_apply': ([vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i64, i32, vp], ctypes.c_int),
+    'srgan_h_frozen_norm_bwd': ([vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i64, i32, vp], ctypes.c_int),
     'srgan_comm_available': ([], ctypes.c_int),
     'srgan_comm_unique_id': ([vp], ctypes.c_int),
     'srgan_comm_init': ([ctypes.POINTER(vp), i32, i32, vp], ctypes.c_int),

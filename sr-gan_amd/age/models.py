@@ -15,11 +15,14 @@ LEAK = 0.05
 
 def _blocked_stack_ok(network):
     """The blocked path has the reference configuration -- no batch-norm inside the stages (age/models.py:13) -- or, for a
-    network built with ``blocked_batch_norm`` (the generator), stages ``[ConvTranspose2d, BatchStatNorm2d]``: the norm
-    with batch statistics has kernels on blocked tensors (``blocked16.batch_norm_train``), the frozen one has not."""
+    network built with ``blocked_batch_norm`` (the generator), stages ``[ConvTranspose2d, BatchStatNorm2d]`` (the norm with
+    batch statistics on blocked tensors, ``blocked16.batch_norm_train``), or, for one built with ``blocked_frozen_norm`` (the
+    discriminator), stages ``[Conv2d, BatchNorm2d]`` with exactly the frozen class (``blocked16.batch_norm_frozen``)."""
     norms = getattr(network, 'blocked_batch_norm', False)
-    return all(len(stage) == 1 or (norms and len(stage) == 2 and isinstance(stage[0], nn.ConvTranspose2d) and
-                                   isinstance(stage[1], nn.BatchStatNorm2d))
+    frozen = getattr(network, 'blocked_frozen_norm', False)
+    return all(len(stage) == 1 or
+               (norms and len(stage) == 2 and isinstance(stage[0], nn.ConvTranspose2d) and isinstance(stage[1], nn.BatchStatNorm2d)) or
+               (frozen and len(stage) == 2 and isinstance(stage[0], nn.Conv2d) and type(stage[1]) is nn.BatchNorm2d)
                for name, stage in network.named_children())
 
 
@@ -95,9 +98,12 @@ class Generator(nn.Module):
 class Discriminator(nn.Module):
     """``layer1..4``: conv k4 s2 p1 + leaky 0.05; ``features`` = the flattened result; ``layer5``: conv k = S/16 -> outputs."""
 
-    def __init__(self, image_size=128, conv_dim=64, number_of_outputs=1, batch_norm=None):
+    def __init__(self, image_size=128, conv_dim=64, number_of_outputs=1, batch_norm=None, blocked_frozen_norm=False):
         seed_all(0)
         super().__init__()
+        # with (frozen) norm layers, stay on the blocked data path under F.storage_dtype (settings.blocked_frozen_norm; off: the
+        # fp32 graph)
+        self.blocked_frozen_norm = bool(blocked_frozen_norm)
         self.number_of_outputs = number_of_outputs
         widths = (3, conv_dim, conv_dim * 2, conv_dim * 4, conv_dim * 8)
         for index in range(1, 5):
@@ -119,11 +125,15 @@ class Discriminator(nn.Module):
 
     def _forward_blocked(self, x, code):
         """The same graph on the 16-bit data path (``blocked16``): every ``leaky_relu(conv(x))`` stage one kernel on bf16 / fp16
-        tensors in the blocked layout; ``features`` (reference order: the NCHW flattening) and the scores leave as fp32."""
+        tensors in the blocked layout -- with a frozen norm the convolution, then the norm's pass with the leaky-ReLU fused into
+        it; ``features`` (reference order: the NCHW flattening) and the scores leave as fp32."""
         from .. import blocked16 as B
         h = B.pack(x, code)
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
-            h = B.conv4x4s2(h, stage[0], slope=LEAK)
+            if len(stage) == 2:       # (called as a module, so that forward hooks see the blocked tensors)
+                h = stage[1](B.conv4x4s2(h, stage[0]), slope=LEAK)
+            else:
+                h = B.conv4x4s2(h, stage[0], slope=LEAK)
         trunk = B.unpack(h)
         self.features = F.flatten2d(trunk)
         # the full-plane convolution = a linear map over the flattened trunk: 16-bit through the blocked order's shadow, fp32

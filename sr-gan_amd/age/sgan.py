@@ -18,5 +18,5 @@ class AgeSganExperiment(SganExperiment, AgeExperiment):
     def model_setup(self):
         size = self._size()
         self.G = Generator(image_size=size, **self.generator_norm_arguments())
-        d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
-        self.D, self.DNN = (Discriminator(image_size=size, number_of_outputs=BIN_LOGITS, batch_norm=d_norm) for _ in range(2))
+        d_norm = self.discriminator_norm_arguments()
+        self.D, self.DNN = (Discriminator(image_size=size, number_of_outputs=BIN_LOGITS, **d_norm) for _ in range(2))

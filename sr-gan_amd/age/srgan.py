@@ -41,15 +41,15 @@ class AgeExperiment(Experiment):
     def model_setup(self):
         """reference age/srgan.py:42-51 (``pretrained=True`` VGG weights need a download: load a checkpoint)."""
         size = self._size()
-        d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
+        d_norm = self.discriminator_norm_arguments()
         if model_architecture == 'vgg':
             self.G = Generator(image_size=size, **self.generator_norm_arguments())
             self.D = vgg16(num_classes=1, image_size=size)
             self.DNN = vgg16(num_classes=1, image_size=size)
         else:
             self.G = Generator(image_size=size, **self.generator_norm_arguments())
-            self.D = Discriminator(image_size=size, batch_norm=d_norm)
-            self.DNN = Discriminator(image_size=size, batch_norm=d_norm)
+            self.D = Discriminator(image_size=size, **d_norm)
+            self.DNN = Discriminator(image_size=size, **d_norm)
 
     def validation_summaries(self, step):
         """MAE / MSE of DNN and D on the train and validation batches (reference age/srgan.py:52-71,92-107)."""

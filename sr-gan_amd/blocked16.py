@@ -699,3 +699,85 @@ def batch_norm_eval(x, mean, inv_std, gamma, beta, slope=1.0):
     out = F._out(data, (x, gamma, beta), backward, 'h_batch_norm_eval')
     out.meta = _activated(meta, data, slope)
     return out
+
+
+def _frozen_backward(s, x_data, mean, inv_std, gamma, ref, slope, want_gx, gamma_grad, beta_grad):
+    """One ``srgan_h_frozen_norm_bwd`` launch on the (pre-masked) blocked ``s``: returns the raw gx = s * gamma * inv_std *
+    mask(ref, slope) (None unless ``want_gx``); ``gamma_grad`` += inv_std * sum s (x - mean) and ``beta_grad`` += sum s where
+    those fp32 buffers are given."""
+    meta = s.meta
+    data = _new(meta.n, meta.c, meta.h, meta.w, meta.code, s.data.device) if want_gx else None
+    _call('srgan_h_frozen_norm_bwd', s.data.data_ptr(), _ptr(x_data), _ptr(mean), inv_std.data_ptr(), gamma.data.data_ptr(), _ptr(ref),
+          float(slope), _ptr(data), _ptr(gamma_grad), _ptr(beta_grad), meta.n, meta.c, meta.h * meta.w, meta.code, F._stream())
+    return data
+
+
+def _frozen_scale(s, gamma, inv_std, ref, slope):
+    """``s * gamma * inv_std * mask(ref, slope)`` per channel, recorded: the backward of ``batch_norm_frozen`` inside a recorded
+    sweep (the gradient penalty).  Like epi 2 of ``_layer`` the result carries (ref, slope) as its mask: cotangents arrive
+    masked alike, so its own backward never applies that mask again (slope ** 2 != slope) -- the gradient for ``s`` is the
+    linearised forward, this scale with the mask ``s`` itself carries, and the gradient for gamma is inv_std * sum(u * s),
+    straight into the arena; both from one launch.  Differentiating that once more (third order) is refused."""
+    data = _frozen_backward(s, None, None, inv_std, gamma, ref, slope, True, None, None)
+    s_meta = s.meta
+
+    def backward(u, needs):
+        if F.grad_enabled():
+            raise NotImplementedError('blocked16.batch_norm_frozen is differentiable twice: a third-order use (a recorded sweep '
+                                      'through the backward of its recorded backward) is not implemented')
+        if needs[1] and not accumulates_into(gamma):
+            raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps only '
+                                      '(straight into the fp32 gradient arena)')
+        if not (needs[0] or needs[1]):
+            return None, None
+        back = _frozen_backward(u, s.data if needs[1] else None, None, inv_std, gamma, s_meta.mask_ref, s_meta.slope, needs[0],
+                                gamma.grad_buffer if needs[1] else None, None)
+        gs = None
+        if needs[0]:
+            gs = Var(back)
+            gs.meta = s_meta
+        return gs, None
+    out = F._out(data, (s, gamma), backward, 'h_frozen_norm_scale')
+    out.meta = s_meta.like(mask_ref=ref, slope=slope)
+    return out
+
+
+def batch_norm_frozen(x, mean, inv_std, gamma, beta, slope=1.0):
+    """The norm with GIVEN statistics (``nn.BatchNorm2d``, which the reference freezes at every step: the norm layers of D /
+    DNN) on a blocked tensor of any code: y = leaky((x - mean) * inv_std * gamma + beta, slope) -- the forward kernel of
+    ``batch_norm_eval`` -- DIFFERENTIABLE TWICE.  A frozen norm is a per-channel affine map, so every derivative is "scale per
+    channel, then mask" (``srgan_h_frozen_norm_bwd``): a plain sweep is ONE launch (gx and the gamma / beta gradients, the
+    latter straight into the fp32 arena), a recorded sweep (the gradient penalty) records ``_frozen_scale``, whose own backward
+    is again one launch; a third-order use raises.  The output is its own mask (``slope`` != 1), so the gradient arrives
+    pre-masked.  The forward entry point refuses fewer than two values per channel: N * H * W == 1 raises ``ValueError``."""
+    meta = _norm_tensors(x, gamma, beta)
+    if meta.n * meta.h * meta.w < 2:
+        raise ValueError(f'blocked16.batch_norm_frozen needs more than 1 value per channel (the forward entry point refuses '
+                         f'M < 2), got input size {[meta.n, meta.c, meta.h, meta.w]}')
+    data = _new(meta.n, meta.c, meta.h, meta.w, meta.code, x.data.device)
+    slope = float(slope)
+    _call('srgan_h_batch_norm_fwd', x.data.data_ptr(), mean.data.data_ptr(), inv_std.data.data_ptr(), gamma.data.data_ptr(),
+          beta.data.data_ptr(), slope, data.data_ptr(), meta.n, meta.c, meta.h * meta.w, meta.code, F._stream())
+
+    def backward(s, needs):
+        if F.grad_enabled():                       # a recorded sweep: the gradient of x only, as a differentiable operation
+            if needs[1] or needs[2]:
+                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
+                                          'only (straight into the fp32 gradient arena)')
+            return (_frozen_scale(s, gamma, inv_std.data, meta.mask_ref, meta.slope) if needs[0] else None), None, None
+        for need, parameter in ((needs[1], gamma), (needs[2], beta)):
+            if need and not accumulates_into(parameter):
+                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
+                                          'only (straight into the fp32 gradient arena)')
+        if not any(needs):
+            return None, None, None
+        back = _frozen_backward(s, x.data if needs[1] else None, mean.data, inv_std.data, gamma, meta.mask_ref, meta.slope, needs[0],
+                                gamma.grad_buffer if needs[1] else None, beta.grad_buffer if needs[2] else None)
+        gx = None
+        if needs[0]:
+            gx = Var(back)
+            gx.meta = meta                          # a pre-masked gradient of x
+        return gx, None, None
+    out = F._out(data, (x, gamma, beta), backward, 'h_batch_norm_frozen')
+    out.meta = _activated(meta, data, slope)
+    return out

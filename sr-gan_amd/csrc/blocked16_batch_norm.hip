@@ -3,13 +3,15 @@
 // so that a DCGAN generator with norm layers stays on the blocked kernels end to end (batch_norm_train.hip is the fp32 NCHW
 // twin; bn_train.h holds what the two share).
 //
-// Four HBM-bound kernels on one decomposition: a workgroup owns channel GROUP g of a run of images [n0, n1), lanes along
+// Five HBM-bound kernels on one decomposition: a workgroup owns channel GROUP g of a run of images [n0, n1), lanes along
 // the pixels of the (image, group) planes, every access one whole slot (16 bytes); all arithmetic fp32 between h_unpack and
 // h_pack (one rounding to nearest even at the store):
 //   stats       one read of x  -> mean, inv_std (+ the running buffers and num_batches_tracked)
 //   forward     one read, one write: y = leaky((x - mean) * inv_std * gamma + beta, slope); eval mode passes running statistics
 //   bwd reduce  reads s, x     -> sum s, sum s * xhat per channel (= g_beta, g_gamma; accumulated when asked)
 //   bwd apply   reads s, x (and the mask reference of x), writes gx = gamma * inv_std * (s - sum s / M - xhat * sum s xhat / M)
+//   frozen bwd  the norm with GIVEN statistics (the frozen layers of D / DNN): a per-channel affine map, so ONE pass reads s
+//               (and x for the gamma sums, the mask reference for gx) -> gx = s * gamma * inv_std, g_gamma, g_beta
 // `s` follows the blocked path's pre-masked convention (blocked16.py): it arrives multiplied by the derivative of this layer's
 // activation, so the backward kernels know no slope of their own; `ref` / `slope` of the apply kernel are the mask of the
 // tensor x itself (epi 2 of the contraction kernels).
@@ -266,7 +268,135 @@ __global__ __launch_bounds__(256) void h_bn_bwd_apply_kernel(const Slot* __restr
   });
 }
 
-// What the four entry points check before any device work.
+// The backward of the norm with GIVEN statistics, y = (x - mean) * inv_std * gamma + beta: every derivative of a per-channel
+// affine map is "scale per channel, then mask", so one pass serves the plain backward (gx and both parameter sums), the
+// recorded backward (gx alone) and the double backward (s = the cotangent, x = the first sweep's gradient, mean = nullptr).
+// GX: write gx = s * gamma * inv_std (times the mask of `ref`).  SUMS: 0 none, 1 sum s, 2 sum s and sum s * (x - mean); the
+// sums leave as g_beta[c] += sum s, g_gamma[c] += inv_std[c] * sum s (x - mean), where the pointers are given.
+// REF: `ref` is given.  A thread takes a TILE of four slots at a time: all their loads are issued before the first is used
+// (the lambda loop of h_bn_for_chunk compiles to one load in flight per thread, which leaves a workgroup of a few slots per
+// thread waiting for HBM latency four times in a row); a slot beyond the chunk re-reads the chunk's last slot and counts as zero.
+template <int PREC, bool GX, int SUMS, bool REF>
+__global__ __launch_bounds__(256) void h_frozen_norm_bwd_kernel(const Slot* __restrict__ s, const Slot* __restrict__ x,
+                                                                const float* __restrict__ mean, const float* __restrict__ inv_std,
+                                                                const float* __restrict__ gamma, const Slot* __restrict__ ref,
+                                                                float slope, Slot* __restrict__ gx, float* g_gamma, float* g_beta,
+                                                                int N, int C, int HW, int images_per_block, float* partial,
+                                                                unsigned int* tickets) {
+  constexpr int G = HGroup<PREC>::N;
+  constexpr int V = SUMS == 2 ? 2 * G : G;
+  const int g = (int)blockIdx.x, CG = (int)gridDim.x, first = g * G, live = min(G, C - first);
+  float mu[G], a[G], plain[G], weighted[G];
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    const bool real = j < live;
+    mu[j] = (real && mean) ? mean[first + j] : 0.f;
+    a[j] = real ? bn_train_scale(inv_std[first + j], gamma[first + j]) : 0.f;
+    plain[j] = weighted[j] = 0.f;
+  }
+  const int n0 = (int)blockIdx.y * images_per_block, n1 = min(N, n0 + images_per_block);
+  const int total = (n1 - n0) * HW;                          // >= 1: every workgroup of the grid owns an image
+  for (int base = 0; base < total; base += 1024) {
+    int64_t at[4];
+    bool ok[4];
+    Slot sq[4], xq[4], rq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = base + q * 256 + (int)threadIdx.x;
+      ok[q] = idx < total;
+      at[q] = h_bn_slot(min(idx, total - 1), HW, n0, CG, g);
+      sq[q] = s[at[q]];
+      if constexpr (SUMS == 2) xq[q] = x[at[q]];
+      if constexpr (GX && REF) rq[q] = ref[at[q]];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float sv[G];
+      h_unpack<PREC>(sq[q], sv);
+      if constexpr (SUMS >= 1) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) sv[j] = ok[q] ? sv[j] : 0.f;
+      }
+      if constexpr (SUMS == 2) {
+        float xv[G];
+        h_unpack<PREC>(xq[q], xv);
+#pragma unroll
+        for (int j = 0; j < G; ++j) weighted[j] = fmaf(sv[j], xv[j] - mu[j], weighted[j]);
+      }
+      if constexpr (SUMS >= 1) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) plain[j] += sv[j];
+      }
+      if constexpr (GX) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) sv[j] = j < live ? sv[j] * a[j] : 0.f;
+        if constexpr (REF) {
+#pragma unroll
+          for (int j = 0; j < G; ++j) sv[j] *= h_slot_positive<PREC>(rq[q], j) ? 1.f : slope;
+        }
+        if (ok[q]) gx[at[q]] = h_pack<PREC>(sv);
+      }
+    }
+  }
+  if constexpr (SUMS >= 1) {
+    // the workgroup's V sums with ONE barrier (every wave's butterfly first, then the four waves in a fixed order: thread i holds
+    // sum i), then the workgroups of the group in part order through the workspace -- the ticket protocol of split_finish.h as
+    // h_bn_stats_kernel walks it, all V values side by side: V barriers in a row in the last workgroup cost more than its loads
+    __shared__ float waves[4][V];
+    __shared__ int last;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int part = (int)blockIdx.y, parts = (int)gridDim.y;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const float p = wave_sum(plain[j]);
+      if (lane == 0) waves[wave][j] = p;
+      if constexpr (SUMS == 2) {
+        const float w = wave_sum(weighted[j]);
+        if (lane == 0) waves[wave][G + j] = w;
+      }
+    }
+    __syncthreads();
+    float mine = 0.f;                                        // thread i < V: sum i of this workgroup's images
+    if (tid < V) mine = (waves[0][tid] + waves[1][tid]) + (waves[2][tid] + waves[3][tid]);
+    if (parts > 1) {
+      float* row = partial + (int64_t)g * parts * V;
+      unsigned int* ticket = tickets + g;
+      if (tid < V) __hip_atomic_store(row + part * V + tid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store acknowledged, the barrier, then thread 0 takes the ticket
+      __syncthreads();
+      if (tid == 0) last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
+      __syncthreads();
+      if (!last) return;
+      // thread t adds the parts t, t + 256, ... of all V sums (their loads in flight together), then the same tree
+      float sum[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) sum[i] = 0.f;
+      for (int p = tid; p < parts; p += 256) {
+        float theirs[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) theirs[i] = __hip_atomic_load(row + p * V + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < V; ++i) sum[i] += theirs[i];
+      }
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const float w = wave_sum(sum[i]);
+        if (lane == 0) waves[wave][i] = w;                   // (its readers above passed two barriers since)
+      }
+      __syncthreads();
+      if (tid < V) mine = (waves[0][tid] + waves[1][tid]) + (waves[2][tid] + waves[3][tid]);
+      if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // thread j adds sum s of channel j to g_beta, thread G + j the weighted sum to g_gamma
+    const int j = tid < G ? tid : tid - G;
+    if (tid >= V || j >= live) return;
+    const int c = first + j;
+    if (tid < G) { if (g_beta) g_beta[c] += mine; }
+    else if (g_gamma) g_gamma[c] += inv_std[c] * mine;
+  }
+}
+
+// What the four batch-statistics entry points check before any device work.
 static int h_bn_arguments(int32_t N, int32_t C, int64_t HW, int32_t dtype, bool pointers, const char* what) {
   SRGAN_REQUIRE(dtype == 0 || dtype == 1 || dtype == 2, SRGAN_EINVAL, what);
   SRGAN_REQUIRE(pointers && N > 0 && C > 0 && HW > 0, SRGAN_EINVAL, what);
@@ -289,7 +419,8 @@ static HBnGrid h_bn_grid(int32_t N, int32_t C, int64_t HW, int32_t dtype) {
   return grid;
 }
 
-// Records of the live profile: kinds 20 .. 23 as batch_norm_train.hip, the algorithmic bytes from the element size.
+// Records of the live profile: kinds 20 .. 23 as batch_norm_train.hip, 24 the frozen backward; the algorithmic bytes from the
+// element size.
 static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int64_t HW, int32_t dtype, int kind, const HBnGrid& grid,
                         double tensors) {
   const double element = dtype == 0 ? 4.0 : 2.0;
@@ -303,6 +434,59 @@ static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int6
     else if ((dtype) == 1) hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);               \
     else hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, stream, __VA_ARGS__);                                 \
   } while (0)
+
+// The modes of h_frozen_norm_bwd_kernel that a call can ask for (gx alone; sums alone, with or without the gamma sums; both; gx
+// with or without the mask reference).
+#define H_FROZEN_LAUNCH(GX, SUMS)                                                                                     \
+  do {                                                                                                                \
+    if (ref && (GX)) H_FROZEN_LAUNCH_MODE(GX, SUMS, true);                                                            \
+    else H_FROZEN_LAUNCH_MODE(GX, SUMS, false);                                                                       \
+  } while (0)
+#define H_FROZEN_LAUNCH_MODE(GX, SUMS, REF)                                                                           \
+  do {                                                                                                                \
+    const dim3 blocks(grid.CG, grid.parts);                                                                           \
+    if (dtype == 0) hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<0, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS);      \
+    else if (dtype == 1) hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<1, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS); \
+    else hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<2, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS);                 \
+  } while (0)
+#define H_FROZEN_ARGUMENTS                                                                                                        \
+  (const Slot*)s, (const Slot*)x, mean, inv_std, gamma, (const Slot*)ref, slope, (Slot*)gx, g_gamma, g_beta, N, C, (int)HW, grid.per, \
+      partial, tickets
+
+int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma, const void* ref,
+                          float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW, int32_t dtype,
+                          hipStream_t stream) {
+  const char* what = "srgan_h_frozen_norm_bwd arguments";
+  SRGAN_REQUIRE(dtype == 0 || dtype == 1 || dtype == 2, SRGAN_EINVAL, what);
+  SRGAN_REQUIRE(s && inv_std && gamma && N > 0 && C > 0 && HW > 0, SRGAN_EINVAL, what);
+  SRGAN_REQUIRE(gx || g_gamma || g_beta, SRGAN_EINVAL, what);
+  SRGAN_REQUIRE(x || !g_gamma, SRGAN_EINVAL, what);
+  // max_tensor_elements; this also keeps a workgroup's chunk (at most N * HW slots) inside 32-bit indices
+  SRGAN_REQUIRE(HW <= (((int64_t)1 << 31) - 1) / ((int64_t)N * C), SRGAN_ERANGE, "srgan_h_frozen_norm_bwd tensor size (2^31 - 1 elements)");
+  HBnGrid grid = h_bn_grid(N, C, HW, dtype);
+  const int sums = g_gamma ? 2 : (g_beta ? 1 : 0);
+  // a workgroup that reduces pays for its g (2 g) trees, its partials and its ticket whatever it read: at least 4096 slots each
+  // while that leaves 256 workgroups
+  while (sums && grid.per < N && (int64_t)grid.per * HW < 4096 && (int64_t)grid.CG * ((N + 2 * grid.per - 1) / (2 * grid.per)) >= 256)
+    grid.per *= 2;
+  grid.parts = (N + grid.per - 1) / grid.per;
+  unsigned int* tickets = nullptr;
+  float* partial = nullptr;
+  if (sums) {
+    if (grid.parts > 1) partial = row_finish_workspace(grid.CG, grid.parts, sums * grid.group, g_h_bn_tickets, stream, &tickets);
+    if (!partial) { grid.per = N; grid.parts = 1; }        // no workspace for this stream: one workgroup per group
+  }
+  SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_frozen_norm_bwd grid");
+  const int slot = profile_bracket_begin(stream);
+  if (gx && sums == 2) H_FROZEN_LAUNCH(true, 2);
+  else if (gx && sums == 1) H_FROZEN_LAUNCH(true, 1);
+  else if (gx) H_FROZEN_LAUNCH(true, 0);
+  else if (sums == 2) H_FROZEN_LAUNCH(false, 2);
+  else H_FROZEN_LAUNCH(false, 1);
+  const int status = launch_status();
+  h_bn_bracket(slot, stream, N, C, HW, dtype, 24, grid, 1.0 + (sums == 2) + (gx != nullptr) + (gx && ref));
+  return status;
+}
 
 }  // namespace srgan
 
@@ -378,6 +562,12 @@ int srgan_h_batch_norm_bwd_apply(const void* s, const void* x, const float* mean
   const int status = launch_status();
   h_bn_bracket(slot, st, N, C, HW, dtype, 23, grid, 3.0);
   return status;
+}
+
+int srgan_h_frozen_norm_bwd(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma,
+                            const void* ref, float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW,
+                            int32_t dtype, void* stream) {
+  return h_frozen_norm_bwd_run(s, x, mean, inv_std, gamma, ref, slope, gx, g_gamma, g_beta, N, C, HW, dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

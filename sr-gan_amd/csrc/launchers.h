@@ -90,6 +90,11 @@ int bn_train_bwd_apply_run(const float* g, const float* x, const float* mean, co
                            const float* beta, float slope, const float* sums, float* gx, int32_t N, int32_t C, int64_t HW,
                            hipStream_t stream);
 
+// blocked16_batch_norm.hip: the backward of a norm with given statistics on blocked tensors (contract: srgan_h_frozen_norm_bwd).
+int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma, const void* ref,
+                          float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW, int32_t dtype,
+                          hipStream_t stream);
+
 // stem7x7.hip: the DenseNet stem's 7x7 / stride 2 convolution, all three passes.
 bool stem7x7_geometry(int32_t C, int32_t K, int32_t R, int32_t S, int32_t sh, int32_t sw, int32_t ph, int32_t pw);
 int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int64_t y_bs, int32_t N, int32_t H, int32_t W,

@@ -33,10 +33,10 @@ class DrivingExperiment(Experiment):
                                                                 seed=101, dp=self.dp, pool=1)
 
     def model_setup(self):
-        d_norm = getattr(self.settings, 'discriminator_batch_norm', False)
+        d_norm = self.discriminator_norm_arguments()
         self.G = Generator(image_size=self.image_size, **self.generator_norm_arguments())
-        self.D = Discriminator(image_size=self.image_size, batch_norm=d_norm)
-        self.DNN = Discriminator(image_size=self.image_size, batch_norm=d_norm)
+        self.D = Discriminator(image_size=self.image_size, **d_norm)
+        self.DNN = Discriminator(image_size=self.image_size, **d_norm)
 
     def validation_summaries(self, step):
         """MAE / NMAE / MSE of DNN and D on the train and validation batches (reference driving/srgan.py:48-67,87-104)."""

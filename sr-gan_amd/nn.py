@@ -44,7 +44,8 @@ class Linear(nn.Linear):
 class BatchNorm2d(nn.BatchNorm2d):
     """Always evaluated with the running statistics: the reference freezes every batch-norm layer at each
     step (srgan.py:261,276,538-542), so training mode never updates or uses batch statistics.  gamma / beta
-    are still trained.  One fused kernel: y = (x - mean) * rsqrt(var + eps) * gamma + beta."""
+    are still trained.  One fused kernel: y = (x - mean) * rsqrt(var + eps) * gamma + beta.  A tensor in the blocked layout
+    (``blocked16``, any code) takes ``_forward_blocked``: differentiable twice, ``slope`` fuses a following leaky-ReLU."""
 
     def _inverse_std(self):
         key = (id(self.running_var), self.running_var._version, id(self.running_mean), self.running_mean._version)
@@ -64,9 +65,20 @@ class BatchNorm2d(nn.BatchNorm2d):
             self._inv_std_cache = cached
         return cached[1], cached[2]
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, slope=1.0):
+        if x.meta is not None:
+            return self._forward_blocked(x, 0.0 if relu else slope)
         inv_std, mean = self._inverse_std()
-        return F.batch_norm_eval(x, mean, inv_std, P(self.weight), P(self.bias), relu=relu)
+        out = F.batch_norm_eval(x, mean, inv_std, P(self.weight), P(self.bias), relu=relu)
+        return out if relu or slope == 1.0 else F.leaky_relu(out, slope)
+
+    def _forward_blocked(self, x, slope):
+        """The frozen layer on a tensor in the blocked layout: the running statistics whatever the mode, the buffers untouched;
+        the cached tensors of ``_inverse_std`` keep their addresses when the statistics are reloaded (a captured graph stays
+        valid)."""
+        from . import blocked16 as B
+        inv_std, mean = self._inverse_std()
+        return B.batch_norm_frozen(x, mean, inv_std, P(self.weight), P(self.bias), slope=slope)
 
 
 class BatchStatNorm2d(BatchNorm2d):

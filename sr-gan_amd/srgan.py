@@ -389,6 +389,14 @@ class Experiment(ABC):
         return dict(batch_norm=getattr(self.settings, 'generator_batch_norm', False),
                     blocked_batch_norm=getattr(self.settings, 'blocked_batch_norm', False))
 
+    def discriminator_norm_arguments(self):
+        """The norm-layer arguments of a DCGAN discriminator (D and DNN), for every ``model_setup`` that builds one:
+        ``settings.discriminator_batch_norm`` (frozen norm layers) and ``settings.blocked_frozen_norm`` (such a discriminator
+        stays on the blocked data path that ``settings.storage_dtype`` / ``settings.blocked_fp32`` select; without either of
+        them it changes nothing).  The latter is read with ``getattr`` and defaults to off: the fp32 NCHW graph."""
+        return dict(batch_norm=getattr(self.settings, 'discriminator_batch_norm', False),
+                    blocked_frozen_norm=getattr(self.settings, 'blocked_frozen_norm', False))
+
     def gpu_mode(self):
         """Moves each network into its flat parameter / gradient arena on this rank's device."""
         if self.dp is not None and self.dp.world_size > 1 and self.G is not None and \
