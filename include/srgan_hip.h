@@ -65,6 +65,8 @@ const char* srgan_last_error(void);
                                                   tensors, dtype 0 / 1 / 2) */
 #define SRGAN_FEATURE_BLOCKED_FROZEN_NORM 0x200u /* ABI 1.1, additive: srgan_h_frozen_norm_bwd (the backward, to first and
                                                    second order, of a norm with given statistics on blocked tensors) */
+#define SRGAN_FEATURE_DEVICE_DRAWS 0x400u /* ABI 1.1, additive: srgan_random_fill / srgan_random_advance (an iteration's random
+                                             tensors from a counter-based generator on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -365,6 +367,29 @@ int srgan_avgpool2d_bwd(const float* g, float* gx, int32_t planes, int32_t H, in
  * out = alpha[b]*u + (1 - alpha[b])*fake (reference srgan.py:365-366). */
 int srgan_gp_interpolate(const float* unlabeled, const float* fake, const float* alpha, float* out, int32_t B,
                          int64_t F, void* stream);
+/* The random tensors of an iteration drawn ON THE DEVICE (SRGAN_FEATURE_DEVICE_DRAWS): the two-Gaussian mixture z of the
+ * discriminator step, alpha and the generator step's z (reference srgan.py:286-289, 364, 301; the reference draws them on
+ * the host from NumPy's / torch's streams -- this stream is a different one, with the same distributions).
+ *   out[i] = element (first + i) of draw `draw` of the iteration held in state, i in [0, n).
+ *   state: device uint32[4] = {seed_lo, seed_hi, iteration, 0}, owned by the caller.
+ * Element e is a pure function of (seed, iteration, draw, e): Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+ * constants 0x9E3779B9 / 0xBB67AE85) with key (seed_lo, seed_hi) and counter (block & 0xffffffff, block >> 32, draw,
+ * iteration), block = e >> 2; the four output words w0..w3 belong to elements 4 * block + 0..3, element e owns w[e & 3].
+ * A window [first, first + n) of a draw therefore holds the same bits whoever fills it: a data-parallel rank fills its rows
+ * of the global tensor with first = rank * local_rows * columns.  first and n need not be multiples of 4.
+ *   kind 0: U[0, 1) = float(w_own >> 8) * 2^-24 (exact).
+ *   kind 1: N(0, 1) + (+/-)offset.  Box-Muller per word pair ((w0, w1) -> elements 0, 1; (w2, w3) -> elements 2, 3):
+ *     u1 = 1 - float(w_even >> 8) * 2^-24 in (0, 1], u2 = float(w_odd >> 8) * 2^-24, r = sqrt(-2 ln u1); the even element
+ *     is r cos(2 pi u2), the odd one r sin(2 pi u2) (precise logf / sqrtf / sincospif); then + offset when bit 0 of the
+ *     element's OWN word is 1, - offset when it is 0 (offset == 0: nothing is added).  Bit 0 lies below the 24 bits the normal
+ *     uses, so this is the equal-weight mixture of norm(-offset, 1) and norm(offset, 1).
+ * Before any device work: NULL out / state, n < 0, first < 0 (or first + n beyond 2^63 - 1), kind outside {0, 1}, draw < 0,
+ * a non-finite offset, n above max_tensor_elements: SRGAN_EINVAL.  n == 0 is a successful no-op.
+ * srgan_random_advance: state[2] += 1 on the stream (one thread), so a HIP graph that captured the fills and the advance
+ * replays as the next iteration each time. */
+int srgan_random_fill(float* out, int64_t n, int64_t first, int32_t kind, float offset, int32_t draw, const uint32_t* state,
+                      void* stream);
+int srgan_random_advance(uint32_t* state, void* stream);
 /* rows[b] = sum_{hw} mean_c |maps[b,c,hw] - target[b,hw]| and its backward (reference crowd/srgan.py:252). */
 int srgan_crowd_map_l1_fwd(const float* maps, const float* target, float* rows, int32_t B, int32_t Cm, int64_t HW,
                            void* stream);

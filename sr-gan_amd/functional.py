@@ -889,6 +889,21 @@ def gp_interpolate(unlabeled, fake, alpha):
     return Var(data, requires_grad=True)
 
 
+def random_fill(shape, kind, offset, draw, state, first=0):
+    """Constant tensor of ``shape`` holding elements ``first ..`` of draw ``draw`` of the iteration in ``state`` (device
+    int32 x 4: seed_lo, seed_hi, iteration, 0): ``kind`` 0 = U[0, 1), 1 = N(0, 1) -/+ ``offset`` with equal weights.  The
+    stream is defined at ``srgan_random_fill`` (include/srgan_hip.h); nothing is copied from the host."""
+    data = _empty(tuple(shape), state)
+    _call('srgan_random_fill', data.data_ptr(), data.numel(), int(first), int(kind), float(offset), int(draw),
+          state.data_ptr(), _stream())
+    return Var(data)
+
+
+def random_advance(state):
+    """The draws' iteration count (``state[2]``) + 1, on the stream: the next fills are the next iteration's."""
+    _call('srgan_random_advance', state.data_ptr(), _stream())
+
+
 def crowd_map_l1(maps, target):
     """rows[b] = sum_{h,w} mean_c |maps[b,c,h,w] - target[b,h,w]| (reference crowd/srgan.py:252).
     First-order differentiable in ``maps`` (it is never inside the gradient-penalty graph)."""

@@ -10,7 +10,9 @@ which is the capturing one) and replaying the instantiated graph removes the hos
 What changes between iterations enters through fixed device buffers that are refreshed before each replay:
 * the labeled / unlabeled batches (device-to-device copies into the captured input tensors);
 * the three random draws, made on the HOST from the same streams and in the same order as the eager step (z for the
-  discriminator step, alpha, z for the generator step), so a replayed run consumes the generators exactly as an eager one;
+  discriminator step, alpha, z for the generator step), so a replayed run consumes the generators exactly as an eager one
+  (with ``settings.device_random_draws`` they are filled on the device by launches captured with the step, from a device
+  state the step advances: nothing is drawn on the host or copied, and only an injected draw enters through a buffer);
 * Adam's update count, kept on the device (``Adam.count_on_device`` / ``srgan_adam_step_counted``).
 
 The side streams of the eager schedule (``settings.overlap_dnn_step`` / ``overlap_gradient_penalty`` /
@@ -114,19 +116,27 @@ class CapturedIteration:
         flat = _flatten(inputs, [])
         generator_phase = step % settings.generator_training_step_period == 0
         # (the 16-bit path bakes its storage type into every launch and the static loss scale into the scaled backward)
-        key = (tuple(tuple(v.shape) for v in flat), generator_phase, F.COMPUTE_DTYPE,
-               tuple(o.param_groups[0]['lr'] for o in self.optimizers()), getattr(settings, 'storage_dtype', None),
-               float(getattr(settings, 'loss_scale', 1.0)))
         batch = inputs[2].shape[0]
         # host draws of THIS iteration, in the order the eager step makes them (srgan.py:286, :364, :301)
         # (a draw injected by a test is used once, exactly as the eager step would use it)
+        # settings.device_random_draws: no host draw is made and none is copied -- the fills and the advance of the draws'
+        # iteration count are launches captured with the step, and a replay consumes the next iteration of the device state
+        # (eager iterations in between advance the same state); only an injected draw still enters through a buffer
+        device_draws = e.device_random_draws()
         def drawn(name, draw):
             injected = e._take_draw(name)
-            return draw() if injected is None else injected
+            if injected is None:
+                return None if device_draws else draw()
+            return injected
         host = {'z_d': drawn('z_d', lambda: e.draw_discriminator_noise(batch)),
-                'alpha': drawn('alpha', lambda: e.draw_interpolation_alpha(settings.batch_size)).reshape(-1)}
+                'alpha': drawn('alpha', lambda: e.draw_interpolation_alpha(settings.batch_size))}
         if generator_phase:
             host['z_g'] = drawn('z_g', lambda: e.draw_generator_noise(batch))
+        host = {name: value.reshape(-1) if name == 'alpha' else value for name, value in host.items() if value is not None}
+        # (which draws enter through a buffer is baked in too: with device draws, only the injected ones)
+        key = (tuple(tuple(v.shape) for v in flat), generator_phase, F.COMPUTE_DTYPE,
+               tuple(o.param_groups[0]['lr'] for o in self.optimizers()), getattr(settings, 'storage_dtype', None),
+               float(getattr(settings, 'loss_scale', 1.0)), tuple(sorted(host)))
         record = self.records.get(key)
         if record is not None and record['shadows'] != self.shadow_counts():
             # a weight shadow appeared since this capture (an eager summary step, a new phase): the captured refreshes do not
@@ -178,6 +188,8 @@ class CapturedIteration:
         for optimizer in optimizers:
             optimizer.count_on_device()
         before = [optimizer.step_count for optimizer in optimizers]
+        if e.device_random_draws():
+            e.device_draw_state()                             # exists before the capture: made inside it, it would be a host copy
         static_inputs = _rebuild(inputs, iter(static))
         injected, e.injected_draws = e.injected_draws, dict(draws)
         graph = torch.cuda.CUDAGraph()

@@ -94,6 +94,22 @@ def examples_on_gpu():
     return torch.cuda.is_available()
 
 
+DRAW_Z_D, DRAW_ALPHA, DRAW_Z_G = 0, 1, 2      # the draw ids of an iteration's three device draws (settings.device_random_draws)
+
+
+def device_draw_window(global_rows, columns, world_size=1, rank=0):
+    """(rows, first) of the window of a ``[global_rows, columns]`` device draw that rank ``rank`` of ``world_size`` fills:
+    its contiguous rows of the global tensor, starting at element ``first`` of the draw.  The ranks' windows tile the
+    global tensor, and an element's value depends on its index in the draw alone (``srgan_random_fill``), so together the
+    ranks hold exactly what one device draws at the global batch size."""
+    if not 0 <= rank < world_size:
+        raise ValueError(f'rank {rank} outside a world of {world_size}')
+    if global_rows % world_size:
+        raise ValueError(f'{global_rows} rows are not divisible by {world_size} ranks')
+    rows = global_rows // world_size
+    return rows, rank * rows * columns
+
+
 class Experiment(ABC):
     """Manages one experimental trial (reference srgan.py:24-469)."""
 
@@ -127,6 +143,7 @@ class Experiment(ABC):
         self._pending_updates = {}     # network name -> (gradient exchange in flight, optimizer to step after it)
         self.injected_draws = None     # tests: dict with 'z_d', 'z_g', 'alpha' device/CPU tensors, used once
         self.last_losses = {}          # device scalars of the latest step (no host sync)
+        self._draw_state = None        # settings.device_random_draws: device int32 x 4 {seed_lo, seed_hi, iteration, 0}
 
     @property
     def parallel(self):
@@ -481,16 +498,47 @@ class Experiment(ABC):
         reproducible across devices; here it comes from torch's CPU stream and is copied over."""
         return self._global_draw(batch_size, lambda count: torch.rand(count))
 
+    # ``settings.device_random_draws`` (read with getattr, default off; seed: ``settings.device_random_seed``, default 0): the
+    # three draws come from the counter-based generator of csrc/random_draws.hip instead of the host streams -- kernel
+    # launches on the stream that uses them, nothing staged, and a HIP graph captures them with the step.  Element e of draw d
+    # of iteration t is a pure function of (seed, t, d, e); t lives in a device state that ``gan_training_step`` advances once
+    # per iteration.  The stream is NOT the reference's (host draws stay the default and the only stream pinned against it);
+    # an injected draw still wins.
+    def device_random_draws(self):
+        return bool(getattr(self.settings, 'device_random_draws', False))
+
+    def device_draw_state(self):
+        """The draws' device state, created at first use with ``iteration = starting_step`` (a resumed run continues its
+        stream; checkpoints keep the reference's keys, the seed comes from the settings)."""
+        if getattr(self, '_draw_state', None) is None:
+            seed = int(getattr(self.settings, 'device_random_seed', 0)) & (2 ** 64 - 1)
+            words = np.array([seed & 0xffffffff, seed >> 32, int(self.starting_step) & 0xffffffff, 0], dtype=np.uint32)
+            self._draw_state = torch.from_numpy(words.view(np.int32)).to(current_device())
+        return self._draw_state
+
+    def _device_draw(self, draw, local_rows, columns, kind, offset=0.0):
+        """This rank's ``[local_rows, columns]`` window of a draw of the global batch (no global draw, no shard); one value
+        per example (``columns`` None) is a vector."""
+        world_size, rank = (self.dp.world_size, self.dp.rank) if self.dp is not None else (1, 0)
+        rows, first = device_draw_window(local_rows * world_size, columns or 1, world_size, rank)
+        return F.random_fill((rows,) if columns is None else (rows, columns), kind, offset, draw, self.device_draw_state(), first)
+
     def sample_discriminator_noise(self, batch_size):
         z = self._take_draw('z_d')
+        if z is None and self.device_random_draws():
+            return self._device_draw(DRAW_Z_D, batch_size, self.G.input_size, 1, self.settings.mean_offset)
         return as_var(self.draw_discriminator_noise(batch_size) if z is None else z, staged=True)
 
     def sample_generator_noise(self, batch_size):
         z = self._take_draw('z_g')
+        if z is None and self.device_random_draws():
+            return self._device_draw(DRAW_Z_G, batch_size, self.G.input_size, 1)
         return as_var(self.draw_generator_noise(batch_size) if z is None else z, staged=True)
 
     def sample_interpolation_alpha(self, batch_size):
         alpha = self._take_draw('alpha')
+        if alpha is None and self.device_random_draws():
+            return self._device_draw(DRAW_ALPHA, batch_size, None, 0)
         return as_var((self.draw_interpolation_alpha(batch_size) if alpha is None else alpha).reshape(-1), staged=True)
 
     # ------------------------------------------------------------------------------------------ batch reductions
@@ -762,6 +810,13 @@ class Experiment(ABC):
                 exchange = self.gradient_exchange(self.G)
                 self.scaled_backward(generator_loss, grad_ready=exchange)
             self.start_update('G', self.g_optimizer, exchange)      # finished when G is next used (next iteration)
+        if self.device_random_draws():
+            # ONE advance of the draws' iteration count per iteration (also when the generator does not train), on the main
+            # stream.  Every fill of iteration t lies between the advances of t - 1 and t: z_D and z_G are filled on this
+            # stream, in front of this line; alpha is filled on the penalty stream, which waited for this stream (behind the
+            # previous advance) before its chain started and which this stream waited for above, before the arenas were
+            # added; the DNN chain and the auxiliary forward draw nothing.  A captured step holds the same edges.
+            F.random_advance(self.device_draw_state())
         self.finish_update('D', 'DNN')
         self.last_losses.update(labeled_loss=labeled_loss, unlabeled_loss=unlabeled_loss, fake_loss=fake_loss,
                                 gradient_penalty=gradient_penalty, generator_loss=generator_loss)
