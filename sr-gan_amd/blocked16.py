@@ -19,6 +19,8 @@ piecewise linear, so every backward operation is again "a linear map, then a mas
 backward is the same kind of call with the roles swapped (the LINEARISED forward: ``conv(s, W) * mask(ref')``) plus a
 weight gradient from (tangent, first-backward gradient), so the recorded backward and its double backward reuse the
 forward kernels; masks and arg-max positions are constants."""
+import collections
+import ctypes
 import os
 
 import torch
@@ -205,17 +207,38 @@ def _refuse_under_capture(what):
                            'of the step (and run the step once eagerly) before capturing it')
 
 
+def _contract(name, a, b, bias, ref, slope, epi, out_meta, *extents):
+    """One launch of a contraction entry point -- they all take (two operands, bias, mask reference, slope, epilogue, output,
+    extents ..., code, stream) -- into a fresh tensor of ``out_meta``'s shape: returns (that tensor, ``out_meta``)."""
+    data = _new(out_meta.n, out_meta.c, out_meta.h, out_meta.w, out_meta.code, a.device)
+    _call(name, a.data_ptr(), b.data_ptr(), bias, _ptr(ref), float(slope), epi, data.data_ptr(), *extents, out_meta.code, F._stream())
+    return data, out_meta
+
+
+class Form(collections.namedtuple('Form', 'name slots source packer tail dtype', defaults=(torch.int32,))):
+    """One operand form of a shadow: the buffer ``name`` of ``slots`` 16-byte slots (``dtype`` elements), written from the fp32
+    ``source`` by ``srgan_h_pack_<packer>(source, buffer, *tail, stream)``, or in the batched refresh by the job that
+    ``srgan_h_pack_job_<packer>(job, first_block, source, buffer, *tail)`` fills in."""
+    __slots__ = ()
+
+
 class Shadow:
     """The 16-bit operand forms of one layer's fp32 master weights: ``forward`` (rows = outputs) and ``transposed`` (the
     data gradient's operand), re-rounded whenever the masters changed -- by ``refresh(arena)`` right behind the optimizer
     update (same stream as the update), or lazily when the version key below moved (checkpoint load, tests).  Every buffer
-    (the ``linear_t`` bias rows included) is allocated once and then written in place, so a refresh can be captured."""
+    (the ``linear_t`` bias rows included) is allocated once and then written in place, so a refresh can be captured.
 
-    def __init__(self, module, kind, code, in_blocked=0, plane=1):
-        _refuse_under_capture(f'a new {kind} weight shadow')
-        self.module, self.kind, self.code, self.in_blocked, self.plane = module, kind, code, in_blocked, plane
+    A kind of layer is a subclass (``SHADOW_KINDS``): it measures the layer once (``_measure``), enumerates its operand
+    forms (``forms``: read by ``repack`` and by the batched refresh only, never on the layer path), and knows the layer's
+    contraction launch and weight gradient."""
+    kind = None
+
+    def __init__(self, module, code, in_blocked=0, plane=1):
+        _refuse_under_capture(f'a new {self.kind} weight shadow')
+        self.module, self.code, self.in_blocked, self.plane = module, code, in_blocked, plane
         self.forward = self.transposed = self.down = self.up = self.bias_rows = None
         self.key = None
+        self._measure()
         arena = getattr(module.weight, '_srgan_arena', None)
         if arena is not None:
             arena.shadows.append(self)
@@ -229,66 +252,22 @@ class Shadow:
             torch.cuda.current_stream().synchronize()
         return self
 
-    def matrix_forms(self):
-        """The matrix shadows of a ``linear`` / ``linear_t`` layer: (buffer name, 16-byte slots, the (rows, cols, rows_real,
-        cols_real, row_stride, col_stride, row_plane, col_plane) of ``srgan_h_pack_matrix``)."""
-        weight = self.module.weight
-        if self.kind == 'linear':
-            outputs, inputs = weight.shape[0], weight.numel() // weight.shape[0]
-            blocked = self.in_blocked or (inputs + 7) // 8 * 8
-            outputs_padded = (outputs + 7) // 8 * 8
-            # forward operand A[o][f'] = W[o][map(f')]; transposed operand A[f'][o] = W[o][map(f')]
-            return (('forward', outputs * blocked // 8, (outputs, blocked, outputs, inputs, inputs, 1, 1, self.plane)),
-                    ('transposed', blocked * outputs_padded // 8, (blocked, outputs_padded, inputs, outputs, 1, inputs, self.plane, 1)))
-        # 'linear_t': conv_transpose2d weights [Cin][Cout][R][S] applied to a 1 x 1 input: a linear map Cin -> (Cout, R x S); its
-        # outputs in the blocked order of a [Cout, R, S] tensor (plane = R * S)
-        c_in, c_out = weight.shape[0], weight.shape[1]
-        plane = weight.shape[2] * weight.shape[3]
-        blocked, c_in_padded = (c_out + 7) // 8 * 8 * plane, (c_in + 7) // 8 * 8
-        return (('forward', blocked * c_in_padded // 8, (blocked, c_in_padded, c_out * plane, c_in, 1, c_out * plane, plane, 1)),
-                ('transposed', c_in * blocked // 8, (c_in, blocked, c_in, c_out * plane, c_out * plane, 1, 1, plane)))
-
-    def bias_rows_form(self):
-        """``linear_t`` with a bias: (channels, plane) of its fp32 bias rows -- bias[co] of every output row (co, pixel) in the
-        blocked order, ceil(channels / 8) * plane * 8 floats -- else None."""
-        if self.kind != 'linear_t' or self.module.bias is None:
-            return None
-        weight = self.module.weight
-        return weight.shape[1], weight.shape[2] * weight.shape[3]
-
     def repack(self):
-        weight = self.module.weight
-        lib, stream = _lib.library(), F._stream()
-
-        buffer = self._buffer
-        if self.kind == 'conv3x3':
-            k, c, r, s = weight.shape
-            for name, transposed, rows, reduced in (('forward', 0, k, c), ('transposed', 1, c, k)):
-                _call('srgan_h_pack_conv_weights', weight.data_ptr(), buffer(name, lib.srgan_h_conv_weight_slots(rows, reduced, r, s)),
-                      k, c, r, s, transposed, self.code, stream)
-        elif self.kind in ('linear', 'linear_t'):
-            for name, slots, arguments in self.matrix_forms():
-                _call('srgan_h_pack_matrix', weight.data_ptr(), buffer(name, slots), *arguments, self.code, stream)
-            form = self.bias_rows_form()
-            if form is not None:                  # (a copy, no arithmetic: written in place, the buffer keeps its address)
-                channels, plane = form
-                full = channels // 8
-                self._buffer('bias_rows', (channels + 7) // 8 * plane * 2, torch.float32)
-                rows, bias = self.bias_rows.view(-1, plane, 8), self.module.bias.data
-                if full:
-                    rows[:full].copy_(bias[:full * 8].view(full, 1, 8).expand(full, plane, 8))
-                if channels % 8:
-                    rows[full].zero_()
-                    rows[full, :, :channels % 8].copy_(bias[full * 8:].view(1, -1).expand(plane, channels % 8))
-        elif self.kind == 'k4s2':
-            # [A][B][4][4], A = the channels on the small plane: conv2d weights [K][C], conv_transpose2d weights [Cin][Cout]
-            a, b = weight.shape[0], weight.shape[1]
-            for name, direction in (('down', 0), ('up', 1)):
-                _call('srgan_h_pack_k4s2_weights', weight.data_ptr(), buffer(name, lib.srgan_h_k4s2_weight_slots(a, b, direction, self.code)),
-                      a, b, direction, self.code, stream)
-        else:
-            raise ValueError(self.kind)
+        """Every form by its single-layer packer, one launch per operand."""
+        stream = F._stream()
+        for form in self.forms():
+            self._pack(form, self._buffer(form.name, form.slots, form.dtype), stream)
         self.key = self._version()
+
+    def _pack(self, form, target, stream):
+        _call('srgan_h_pack_' + form.packer, form.source.data_ptr(), target, *form.tail, stream)
+
+    def _fill(self, job, first_block, form, target):
+        """``form`` as job(s) of the batched refresh, written to host memory at ``job``: (jobs written, workgroups taken)."""
+        name = 'srgan_h_pack_job_' + form.packer
+        taken = getattr(_lib.library(), name)(job, first_block, form.source.data_ptr(), target, *form.tail)
+        _lib.check(min(taken, 0), name)
+        return 1, taken
 
     def _buffer(self, name, slots, dtype=torch.int32):
         """The device buffer of one operand form (``slots`` 16-byte slots), allocated on first use and then kept."""
@@ -305,12 +284,176 @@ class Shadow:
                 None if arena is None else (arena.version, arena.data._version))
 
 
+class Conv3x3Shadow(Shadow):
+    """A 3x3 / stride 1 / padding 1 ``nn.Conv2d``, weights [K][C][3][3]."""
+    kind = 'conv3x3'
+
+    def _measure(self):
+        self.k, self.c, self.r, self.s = self.module.weight.shape
+
+    def forms(self):
+        k, c, r, s = self.k, self.c, self.r, self.s
+        slots = _lib.library().srgan_h_conv_weight_slots
+        for name, transposed, rows, reduced in (('forward', 0, k, c), ('transposed', 1, c, k)):
+            yield Form(name, slots(rows, reduced, r, s), self.module.weight, 'conv_weights', (k, c, r, s, transposed, self.code))
+
+    def launch(self, x, transposed, epi, slope, ref, bias):
+        meta = x.meta
+        c_in, c_out = (self.k, self.c) if transposed else (self.c, self.k)
+        if meta.c != c_in:
+            raise ValueError(f'blocked16 conv: input has {meta.c} channels, the layer expects {c_in}')
+        operand = self.transposed if transposed else self.forward
+        return _contract('srgan_h_conv3x3', x.data, operand, F._ptr(bias), ref, slope, epi,
+                         Blocked(meta.n, c_out, meta.h, meta.w, meta.code), meta.n, c_in, c_out, c_out, meta.h, meta.w)
+
+    def weight_gradient(self, x_side, y_side, into):
+        xm = x_side.meta
+        _call('srgan_h_conv3x3_wgrad', x_side.data.data_ptr(), y_side.data.data_ptr(), into.data_ptr(), xm.n, xm.c, y_side.meta.c,
+              xm.h, xm.w, xm.code, F._stream())
+
+
+class K4s2Shadow(Shadow):
+    """The 4x4 / stride 2 / padding 1 family, weights [A][B][4][4] with A = the channels on the small plane: conv2d weights
+    [K][C], conv_transpose2d weights [Cin][Cout].  ``down`` is the operand big -> small plane, ``up`` small -> big."""
+    kind = 'k4s2'
+
+    def _measure(self):
+        self.a, self.b = self.module.weight.shape[:2]
+        self.transpose = isinstance(self.module, torch.nn.ConvTranspose2d)
+
+    def forms(self):
+        slots = _lib.library().srgan_h_k4s2_weight_slots
+        for name, direction in (('down', 0), ('up', 1)):
+            yield Form(name, slots(self.a, self.b, direction, self.code), self.module.weight, 'k4s2_weights',
+                       (self.a, self.b, direction, self.code))
+
+    def _fill(self, job, first_block, form, target):
+        written = ctypes.c_int32()              # a form of this kind may take several jobs: the filler says how many
+        _, taken = super()._fill(job, first_block, form._replace(tail=form.tail + (ctypes.byref(written),)), target)
+        return written.value, taken
+
+    def launch(self, x, transposed, epi, slope, ref, bias):
+        meta, a, b = x.meta, self.a, self.b
+        if self.transpose != transposed:                       # small -> big plane
+            if meta.c != a:
+                raise ValueError(f'blocked16 transposed 4x4 / s2: input has {meta.c} channels, expected {a}')
+            return _contract('srgan_h_conv_transpose4x4s2', x.data, self.up, F._ptr(bias), ref, slope, epi,
+                             Blocked(meta.n, b, 2 * meta.h, 2 * meta.w, meta.code), meta.n, a, b, meta.h, meta.w)
+        if meta.c != b or meta.h % 2 or meta.w % 2:
+            raise ValueError(f'blocked16 4x4 / s2: input [{meta.c}, {meta.h}, {meta.w}], expected {b} channels on an even plane')
+        return _contract('srgan_h_conv4x4s2', x.data, self.down, F._ptr(bias), ref, slope, epi,
+                         Blocked(meta.n, a, meta.h // 2, meta.w // 2, meta.code), meta.n, b, a, meta.h, meta.w)
+
+    def weight_gradient(self, x_side, y_side, into):
+        # conv2d: input side = the big plane; conv_transpose2d: input side = the small plane
+        big, small = (y_side, x_side) if self.transpose else (x_side, y_side)
+        _call('srgan_h_k4s2_wgrad', big.data.data_ptr(), small.data.data_ptr(), into.data_ptr(), big.meta.n, big.meta.c, small.meta.c,
+              big.meta.h, big.meta.w, 1, x_side.meta.code, F._stream())
+
+
+class LinearShadow(Shadow):
+    """An ``nn.Linear`` on a [N, F] blocked matrix of ``in_blocked`` columns (0: the inputs padded to whole groups), which may
+    be the flattened view of a [N, C, H, W] tensor (``plane`` = H * W): the shadow's columns follow the blocked order."""
+    kind = 'linear'
+
+    def _measure(self):
+        weight = self.module.weight
+        self.outputs, self.inputs = weight.shape[0], weight.numel() // weight.shape[0]
+        self.blocked = self.in_blocked or (self.inputs + 7) // 8 * 8
+        self.outputs_padded = (self.outputs + 7) // 8 * 8
+
+    def forms(self):
+        """The (rows, cols, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane) of ``srgan_h_pack_matrix``:
+        forward operand A[o][f'] = W[o][map(f')]; transposed operand A[f'][o] = W[o][map(f')]."""
+        outputs, inputs, blocked, padded = self.outputs, self.inputs, self.blocked, self.outputs_padded
+        weight, plane, code = self.module.weight, self.plane, self.code
+        yield Form('forward', outputs * blocked // 8, weight, 'matrix', (outputs, blocked, outputs, inputs, inputs, 1, 1, plane, code))
+        yield Form('transposed', blocked * padded // 8, weight, 'matrix', (blocked, padded, inputs, outputs, 1, inputs, plane, 1, code))
+
+    def launch(self, x, transposed, epi, slope, ref, bias):
+        meta, outputs, blocked = x.meta, self.outputs, self.blocked
+        if transposed:
+            if meta.c != outputs:
+                raise ValueError(f'blocked16 linear (data gradient): input has {meta.c} features, expected {outputs}')
+            return _contract('srgan_h_gemm', self.transposed, x.data, None, ref, slope, epi,
+                             Blocked(meta.n, blocked, 1, 1, meta.code, plane=self.plane, real=self.inputs),
+                             blocked, meta.n, outputs, blocked, 0)
+        if meta.c != blocked:
+            raise ValueError(f'blocked16 linear: input has {meta.c} (blocked) features, the shadow was built for {blocked}')
+        return _contract('srgan_h_gemm', self.forward, x.data, F._ptr(bias), ref, slope, epi, Blocked(meta.n, outputs, 1, 1, meta.code),
+                         outputs, meta.n, blocked, outputs, outputs)
+
+    def weight_gradient(self, x_side, y_side, into):
+        xm = x_side.meta
+        _call('srgan_h_linear_wgrad', y_side.data.data_ptr(), x_side.data.data_ptr(), into.data_ptr(), xm.n, self.outputs, xm.c,
+              self.outputs, self.inputs, self.inputs, 1, 1, self.plane, xm.code, F._stream())
+
+
+class SeedShadow(Shadow):
+    """``nn.ConvTranspose2d`` weights [Cin][Cout][R][S] applied to a 1 x 1 input: a linear map Cin -> (Cout, R x S), its
+    outputs in the blocked order of a [Cout, R, S] tensor (``plane`` = R * S, ``blocked`` rows).  With a bias, ``bias_rows``
+    holds bias[co] of every output row (co, pixel) in that order, as fp32."""
+    kind = 'linear_t'
+
+    def _measure(self):
+        self.c_in, self.c_out, self.r, self.s = self.module.weight.shape
+        self.plane = self.r * self.s
+        self.features = self.c_out * self.plane
+        self.blocked = (self.c_out + 7) // 8 * 8 * self.plane
+        self.c_in_padded = (self.c_in + 7) // 8 * 8
+
+    def forms(self):
+        c_in, features, blocked, padded, plane = self.c_in, self.features, self.blocked, self.c_in_padded, self.plane
+        weight, code = self.module.weight, self.code
+        yield Form('forward', blocked * padded // 8, weight, 'matrix', (blocked, padded, features, c_in, 1, features, plane, 1, code))
+        yield Form('transposed', c_in * blocked // 8, weight, 'matrix', (c_in, blocked, c_in, features, features, 1, 1, plane, code))
+        if self.module.bias is not None:              # ``blocked`` floats, four to a slot
+            yield Form('bias_rows', blocked // 4, self.module.bias, 'bias_rows', (self.c_out, plane), torch.float32)
+
+    def _pack(self, form, target, stream):
+        if form.name != 'bias_rows':
+            return super()._pack(form, target, stream)
+        # the bias rows have no single-layer entry point (a copy, no arithmetic: written in place, the buffer keeps its address)
+        channels, plane = form.tail
+        full = channels // 8
+        rows, bias = self.bias_rows.view(-1, plane, 8), form.source.data
+        if full:
+            rows[:full].copy_(bias[:full * 8].view(full, 1, 8).expand(full, plane, 8))
+        if channels % 8:
+            rows[full].zero_()
+            rows[full, :, :channels % 8].copy_(bias[full * 8:].view(1, -1).expand(plane, channels % 8))
+
+    def launch(self, x, transposed, epi, slope, ref, bias):
+        meta, c_in, c_out, blocked = x.meta, self.c_in, self.c_out, self.blocked
+        if transposed:                                         # [N, Cout, R, S] -> [N, Cin]
+            if (meta.c, meta.h, meta.w) != (c_out, self.r, self.s):
+                raise ValueError('blocked16 seed transposed convolution (data gradient): unexpected input shape')
+            return _contract('srgan_h_gemm', self.transposed, x.data, None, ref, slope, epi, Blocked(meta.n, c_in, 1, 1, meta.code),
+                             c_in, meta.n, blocked, c_in, 0)
+        if meta.c != c_in:
+            raise ValueError(f'blocked16 seed transposed convolution: input has {meta.c} features, expected {c_in}')
+        rows = None if bias is None else _ptr(self.bias_rows)
+        return _contract('srgan_h_gemm', self.forward, x.data, rows, ref, slope, epi, Blocked(meta.n, c_out, self.r, self.s, meta.code),
+                         blocked, meta.n, self.c_in_padded, blocked, blocked)
+
+    def weight_gradient(self, x_side, y_side, into):
+        xm = x_side.meta
+        _call('srgan_h_linear_wgrad', y_side.data.data_ptr(), x_side.data.data_ptr(), into.data_ptr(), xm.n, self.blocked, xm.c,
+              self.features, self.c_in, 1, self.features, self.plane, 1, xm.code, F._stream())
+
+
+SHADOW_KINDS = {cls.kind: cls for cls in (Conv3x3Shadow, K4s2Shadow, LinearShadow, SeedShadow)}
+# the shadow kinds of the batched refresh: all of them (the matrix shadows and the seed layer's bias rows since ABI 1.1's
+# SRGAN_FEATURE_BATCHED_SHADOWS)
+BATCHED_KINDS = tuple(SHADOW_KINDS)
+
+
 def shadow_of(module, kind, code, in_blocked=0, plane=1):
     table = module.__dict__.setdefault('_srgan_shadows', {})
     key = (kind, code, in_blocked, plane)
     found = table.get(key)
     if found is None:
-        found = table[key] = Shadow(module, kind, code, in_blocked, plane)
+        found = table[key] = SHADOW_KINDS[kind](module, code, in_blocked, plane)
     return found.fresh()
 
 
@@ -320,50 +463,19 @@ class _PackPlan:
     buffers, so the table stays valid until the set of shadows changes (and a replayed refresh writes the same addresses)."""
 
     def __init__(self, shadows):
-        import ctypes
         _refuse_under_capture('building the batched shadow refresh')
-        lib = _lib.library()
-        size = lib.srgan_h_pack_job_bytes()
+        size = _lib.library().srgan_h_pack_job_bytes()
         self.shadows = list(shadows)
         self.signature = _signature(self.shadows)
         host = ctypes.create_string_buffer(size * 5 * max(1, len(self.shadows)))
         count = blocks = 0
-        written = ctypes.c_int32()
         device = None
         for shadow in self.shadows:
-            weight = shadow.module.weight
-            device = weight.device
-            if shadow.kind == 'conv3x3':
-                k, c, r, s = weight.shape
-                for name, transposed, rows, reduced in (('forward', 0, k, c), ('transposed', 1, c, k)):
-                    target = shadow._buffer(name, lib.srgan_h_conv_weight_slots(rows, reduced, r, s))
-                    taken = lib.srgan_h_pack_job_conv_weights(ctypes.byref(host, count * size), blocks, weight.data_ptr(), target,
-                                                              k, c, r, s, transposed, shadow.code)
-                    _lib.check(min(taken, 0), 'srgan_h_pack_job_conv_weights')
-                    count, blocks = count + 1, blocks + taken
-            elif shadow.kind == 'k4s2':
-                a, b = weight.shape[0], weight.shape[1]
-                for name, direction in (('down', 0), ('up', 1)):
-                    target = shadow._buffer(name, lib.srgan_h_k4s2_weight_slots(a, b, direction, shadow.code))
-                    taken = lib.srgan_h_pack_job_k4s2_weights(ctypes.byref(host, count * size), blocks, weight.data_ptr(), target,
-                                                              a, b, direction, shadow.code, ctypes.byref(written))
-                    _lib.check(min(taken, 0), 'srgan_h_pack_job_k4s2_weights')
-                    count, blocks = count + written.value, blocks + taken
-            else:                                           # 'linear', 'linear_t'
-                for name, slots, arguments in shadow.matrix_forms():
-                    target = shadow._buffer(name, slots)
-                    taken = lib.srgan_h_pack_job_matrix(ctypes.byref(host, count * size), blocks, weight.data_ptr(), target,
-                                                        *arguments, shadow.code)
-                    _lib.check(min(taken, 0), 'srgan_h_pack_job_matrix')
-                    count, blocks = count + 1, blocks + taken
-                form = shadow.bias_rows_form()
-                if form is not None:
-                    channels, plane = form
-                    target = shadow._buffer('bias_rows', (channels + 7) // 8 * plane * 2, torch.float32)
-                    taken = lib.srgan_h_pack_job_bias_rows(ctypes.byref(host, count * size), blocks, shadow.module.bias.data_ptr(),
-                                                           target, channels, plane)
-                    _lib.check(min(taken, 0), 'srgan_h_pack_job_bias_rows')
-                    count, blocks = count + 1, blocks + taken
+            device = shadow.module.weight.device
+            for form in shadow.forms():
+                target = shadow._buffer(form.name, form.slots, form.dtype)
+                written, taken = shadow._fill(ctypes.byref(host, count * size), blocks, form, target)
+                count, blocks = count + written, blocks + taken
         self.count, self.blocks = count, blocks
         self.table = None
         if count:
@@ -374,11 +486,6 @@ class _PackPlan:
             _call('srgan_h_pack_batched', self.table.data_ptr(), self.count, self.blocks, F._stream())
         for shadow in self.shadows:
             shadow.key = shadow._version()
-
-
-# the shadow kinds of the batched refresh: all of them (the matrix shadows and the seed layer's bias rows since ABI 1.1's
-# SRGAN_FEATURE_BATCHED_SHADOWS)
-BATCHED_KINDS = ('conv3x3', 'k4s2', 'linear', 'linear_t')
 
 
 def _signature(shadows):
@@ -448,9 +555,7 @@ def conv3x3(x, module, slope=None):
     age/vgg.py:78-82), other = leaky_relu."""
     if tuple(module.kernel_size) != (3, 3) or tuple(module.stride) != (1, 1) or tuple(module.padding) != (1, 1):
         raise ValueError('blocked16.conv3x3: 3x3 / stride 1 / padding 1 convolutions')
-    shadow = shadow_of(module, 'conv3x3', x.meta.code)
-    epi, slope_value = (1, 1.0 if slope is None else float(slope))
-    return _layer(x, module, shadow, False, epi, slope_value, None, True)
+    return _activated_layer(x, module, shadow_of(module, 'conv3x3', x.meta.code), slope)
 
 
 def linear(x, module, slope=None):
@@ -459,8 +564,7 @@ def linear(x, module, slope=None):
     meta = x.meta
     if meta.h != 1 or meta.w != 1:
         raise ValueError('blocked16.linear takes [N, F] (flatten first)')
-    shadow = shadow_of(module, 'linear', meta.code, in_blocked=meta.groups * 8, plane=meta.plane)
-    return _layer(x, module, shadow, False, 1, 1.0 if slope is None else float(slope), None, True)
+    return _activated_layer(x, module, shadow_of(module, 'linear', meta.code, in_blocked=meta.groups * 8, plane=meta.plane), slope)
 
 
 def conv4x4s2(x, module, slope=None):
@@ -468,7 +572,7 @@ def conv4x4s2(x, module, slope=None):
     age/models.py:61-73: ``leaky_relu(layer(x), 0.05)``)."""
     if tuple(module.kernel_size) != (4, 4) or tuple(module.stride) != (2, 2) or tuple(module.padding) != (1, 1):
         raise ValueError('blocked16.conv4x4s2: 4x4 / stride 2 / padding 1 convolutions')
-    return _layer(x, module, shadow_of(module, 'k4s2', x.meta.code), False, 1, 1.0 if slope is None else float(slope), None, True)
+    return _activated_layer(x, module, shadow_of(module, 'k4s2', x.meta.code), slope)
 
 
 def conv_transpose4x4s2(x, module, slope=None):
@@ -477,7 +581,7 @@ def conv_transpose4x4s2(x, module, slope=None):
     if tuple(module.kernel_size) != (4, 4) or tuple(module.stride) != (2, 2) or tuple(module.padding) != (1, 1) or \
             tuple(module.output_padding) != (0, 0):
         raise ValueError('blocked16.conv_transpose4x4s2: 4x4 / stride 2 / padding 1 transposed convolutions')
-    return _layer(x, module, shadow_of(module, 'k4s2', x.meta.code), False, 1, 1.0 if slope is None else float(slope), None, True)
+    return _activated_layer(x, module, shadow_of(module, 'k4s2', x.meta.code), slope)
 
 
 def seed_conv_transpose(x, module, slope=None):
@@ -485,76 +589,18 @@ def seed_conv_transpose(x, module, slope=None):
     ``fc``, reference age/models.py:37,47): a linear map onto a [N, Cout, R, S] tensor."""
     if tuple(module.stride) != (1, 1) or tuple(module.padding) != (0, 0) or x.meta.h != 1 or x.meta.w != 1 or x.meta.plane != 1:
         raise ValueError('blocked16.seed_conv_transpose: a stride-1 unpadded transposed convolution of a 1 x 1 plane')
-    return _layer(x, module, shadow_of(module, 'linear_t', x.meta.code), False, 1, 1.0 if slope is None else float(slope), None, True)
+    return _activated_layer(x, module, shadow_of(module, 'linear_t', x.meta.code), slope)
 
 
-def _is_transpose(module):
-    return isinstance(module, torch.nn.ConvTranspose2d)
+def _activated_layer(x, module, shadow, slope):
+    """The tail of the public layer functions: bias and leaky(slope) in the layer's kernel (slope None: no activation)."""
+    return _layer(x, module, shadow, False, 1, 1.0 if slope is None else float(slope), None, True)
 
 
-def _launch(x, module, shadow, transposed, epi, slope, ref, bias):
-    """The contraction launch of ``_layer``: returns (output tensor, its Blocked)."""
-    meta, code, stream, device = x.meta, x.meta.code, F._stream(), x.data.device
-    bias_ptr = None if bias is None else bias.data.data_ptr()
-    if shadow.kind == 'conv3x3':
-        k, c = module.weight.shape[0], module.weight.shape[1]
-        c_in, c_out = (k, c) if transposed else (c, k)
-        if meta.c != c_in:
-            raise ValueError(f'blocked16 conv: input has {meta.c} channels, the layer expects {c_in}')
-        data = _new(meta.n, c_out, meta.h, meta.w, code, device)
-        operand = shadow.transposed if transposed else shadow.forward
-        _call('srgan_h_conv3x3', x.data.data_ptr(), operand.data_ptr(), bias_ptr, _ptr(ref), float(slope), epi, data.data_ptr(),
-              meta.n, c_in, c_out, c_out, meta.h, meta.w, code, stream)
-        return data, Blocked(meta.n, c_out, meta.h, meta.w, code)
-    if shadow.kind == 'k4s2':
-        a, b = module.weight.shape[0], module.weight.shape[1]
-        up = _is_transpose(module) != transposed              # small -> big plane
-        if up:
-            if meta.c != a:
-                raise ValueError(f'blocked16 transposed 4x4 / s2: input has {meta.c} channels, expected {a}')
-            data = _new(meta.n, b, 2 * meta.h, 2 * meta.w, code, device)
-            _call('srgan_h_conv_transpose4x4s2', x.data.data_ptr(), shadow.up.data_ptr(), bias_ptr, _ptr(ref), float(slope), epi,
-                  data.data_ptr(), meta.n, a, b, meta.h, meta.w, code, stream)
-            return data, Blocked(meta.n, b, 2 * meta.h, 2 * meta.w, code)
-        if meta.c != b or meta.h % 2 or meta.w % 2:
-            raise ValueError(f'blocked16 4x4 / s2: input [{meta.c}, {meta.h}, {meta.w}], expected {b} channels on an even plane')
-        data = _new(meta.n, a, meta.h // 2, meta.w // 2, code, device)
-        _call('srgan_h_conv4x4s2', x.data.data_ptr(), shadow.down.data_ptr(), bias_ptr, _ptr(ref), float(slope), epi,
-              data.data_ptr(), meta.n, b, a, meta.h, meta.w, code, stream)
-        return data, Blocked(meta.n, a, meta.h // 2, meta.w // 2, code)
-    if shadow.kind == 'linear_t':
-        c_in, c_out, r, s_ = module.weight.shape
-        plane = r * s_
-        blocked = (c_out + 7) // 8 * 8 * plane
-        if transposed:                                         # [N, Cout, R, S] -> [N, Cin]
-            if (meta.c, meta.h, meta.w) != (c_out, r, s_):
-                raise ValueError('blocked16 seed transposed convolution (data gradient): unexpected input shape')
-            data = _new(meta.n, c_in, 1, 1, code, device)
-            _call('srgan_h_gemm', shadow.transposed.data_ptr(), x.data.data_ptr(), None, _ptr(ref), float(slope), epi, data.data_ptr(),
-                  c_in, meta.n, blocked, c_in, 0, code, stream)
-            return data, Blocked(meta.n, c_in, 1, 1, code)
-        if meta.c != c_in:
-            raise ValueError(f'blocked16 seed transposed convolution: input has {meta.c} features, expected {c_in}')
-        data = _new(meta.n, c_out, r, s_, code, device)
-        rows = None if (bias is None or shadow.bias_rows is None) else shadow.bias_rows.data_ptr()
-        _call('srgan_h_gemm', shadow.forward.data_ptr(), x.data.data_ptr(), rows, _ptr(ref), float(slope), epi, data.data_ptr(),
-              blocked, meta.n, (c_in + 7) // 8 * 8, blocked, blocked, code, stream)
-        return data, Blocked(meta.n, c_out, r, s_, code)
-    outputs, inputs = module.weight.shape[0], module.weight.numel() // module.weight.shape[0]
-    blocked = shadow.in_blocked or (inputs + 7) // 8 * 8
-    if transposed:
-        if meta.c != outputs:
-            raise ValueError(f'blocked16 linear (data gradient): input has {meta.c} features, expected {outputs}')
-        data = _new(meta.n, blocked, 1, 1, code, device)
-        _call('srgan_h_gemm', shadow.transposed.data_ptr(), x.data.data_ptr(), None, _ptr(ref), float(slope), epi, data.data_ptr(),
-              blocked, meta.n, outputs, blocked, 0, code, stream)
-        return data, Blocked(meta.n, blocked, 1, 1, code, plane=shadow.plane, real=inputs)
-    if meta.c != blocked:
-        raise ValueError(f'blocked16 linear: input has {meta.c} (blocked) features, the shadow was built for {blocked}')
-    data = _new(meta.n, outputs, 1, 1, code, device)
-    _call('srgan_h_gemm', shadow.forward.data_ptr(), x.data.data_ptr(), bias_ptr, _ptr(ref), float(slope), epi, data.data_ptr(),
-          outputs, meta.n, blocked, outputs, outputs, code, stream)
-    return data, Blocked(meta.n, outputs, 1, 1, code)
+def _into_arena(parameter, what, where=' (straight into the fp32 gradient arena)'):
+    """Parameter gradients of this path exist only as sums into the fp32 arena, which a plain backward sweep offers."""
+    if not accumulates_into(parameter):
+        raise NotImplementedError(f'the 16-bit path computes {what} gradients in plain backward sweeps only{where}')
 
 
 def _layer(x, module, shadow, transposed, epi, slope, ref, use_bias):
@@ -563,7 +609,7 @@ def _layer(x, module, shadow, transposed, epi, slope, ref, use_bias):
     meta = x.meta
     weight = _parameter(module.weight)
     bias = _parameter(module.bias) if (use_bias and module.bias is not None) else None
-    data, out_meta = _launch(x, module, shadow, transposed, epi, slope, ref, bias)
+    data, out_meta = shadow.launch(x, transposed, epi, slope, ref, bias)
     if epi == 1 and slope != 1.0:
         out_meta.mask_ref, out_meta.slope = data, slope            # an activated tensor is its own mask
     elif epi == 2:
@@ -577,14 +623,11 @@ def _layer(x, module, shadow, transposed, epi, slope, ref, use_bias):
             else:
                 gx = _layer(s, module, shadow, not transposed, 0, 1.0, None, False)
         if needs[1]:
-            if not accumulates_into(weight):
-                raise NotImplementedError('the 16-bit path computes weight gradients in plain backward sweeps only '
-                                          '(straight into the fp32 gradient arena)')
+            _into_arena(weight, 'weight')
             x_side, y_side = (s, x) if transposed else (x, s)
-            _weight_gradient(shadow, module, x_side, y_side, weight.grad_buffer)
+            shadow.weight_gradient(x_side, y_side, weight.grad_buffer)
         if needs[2]:
-            if not accumulates_into(bias):
-                raise NotImplementedError('the 16-bit path computes bias gradients in plain backward sweeps only')
+            _into_arena(bias, 'bias', '')
             sm = s.meta
             _call('srgan_h_channel_sums', s.data.data_ptr(), bias.grad_buffer.data_ptr(), sm.n, sm.c, sm.h * sm.w, sm.code,
                   F._stream())
@@ -597,26 +640,7 @@ def _layer(x, module, shadow, transposed, epi, slope, ref, use_bias):
 def _weight_gradient(shadow, module, x_side, y_side, into):
     """into (fp32, the arena's gradient view of the layer's weight) += d loss / d W from the tensor at the layer's input side
     and the (pre-masked) gradient at its output side."""
-    xm, ym = x_side.meta, y_side.meta
-    stream = F._stream()
-    if shadow.kind == 'conv3x3':
-        _call('srgan_h_conv3x3_wgrad', x_side.data.data_ptr(), y_side.data.data_ptr(), into.data_ptr(), xm.n, xm.c, ym.c, xm.h,
-              xm.w, xm.code, stream)
-    elif shadow.kind == 'k4s2':
-        # conv2d: input side = the big plane; conv_transpose2d: input side = the small plane
-        big, small = (y_side, x_side) if _is_transpose(module) else (x_side, y_side)
-        _call('srgan_h_k4s2_wgrad', big.data.data_ptr(), small.data.data_ptr(), into.data_ptr(), big.meta.n, big.meta.c, small.meta.c,
-              big.meta.h, big.meta.w, 1, xm.code, stream)
-    elif shadow.kind == 'linear_t':
-        c_in, c_out, r, s_ = module.weight.shape
-        plane = r * s_
-        blocked = (c_out + 7) // 8 * 8 * plane
-        _call('srgan_h_linear_wgrad', y_side.data.data_ptr(), x_side.data.data_ptr(), into.data_ptr(), xm.n, blocked, xm.c,
-              c_out * plane, c_in, 1, c_out * plane, plane, 1, xm.code, stream)
-    else:
-        outputs, inputs = module.weight.shape[0], module.weight.numel() // module.weight.shape[0]
-        _call('srgan_h_linear_wgrad', y_side.data.data_ptr(), x_side.data.data_ptr(), into.data_ptr(), xm.n, outputs, xm.c,
-              outputs, inputs, inputs, 1, 1, shadow.plane, xm.code, stream)
+    shadow.weight_gradient(x_side, y_side, into)
 
 
 # ------------------------------------------------------------------------------------------------ batch statistics
@@ -666,9 +690,8 @@ def batch_norm_train(x, gamma, beta, running_mean, running_var, momentum, eps, s
             raise NotImplementedError('batch_norm_train has a first-order backward only: differentiating a gradient through '
                                       'batch statistics (create_graph=True) is not implemented')
         for need, parameter in ((needs[1], gamma), (needs[2], beta)):
-            if need and not accumulates_into(parameter):
-                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
-                                          'only (straight into the fp32 gradient arena)')
+            if need:
+                _into_arena(parameter, 'batch-norm parameter')
         sums = F._empty((2, c), x.data)            # sum s (= g_beta), sum s * xhat (= g_gamma)
         _call('srgan_h_batch_norm_bwd_reduce', s.data.data_ptr(), x.data.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
               sums.data_ptr(), gamma.grad_buffer.data_ptr() if needs[1] else None, beta.grad_buffer.data_ptr() if needs[2] else None,
@@ -725,9 +748,8 @@ def _frozen_scale(s, gamma, inv_std, ref, slope):
         if F.grad_enabled():
             raise NotImplementedError('blocked16.batch_norm_frozen is differentiable twice: a third-order use (a recorded sweep '
                                       'through the backward of its recorded backward) is not implemented')
-        if needs[1] and not accumulates_into(gamma):
-            raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps only '
-                                      '(straight into the fp32 gradient arena)')
+        if needs[1]:
+            _into_arena(gamma, 'batch-norm parameter')
         if not (needs[0] or needs[1]):
             return None, None
         back = _frozen_backward(u, s.data if needs[1] else None, None, inv_std, gamma, s_meta.mask_ref, s_meta.slope, needs[0],
@@ -762,13 +784,11 @@ def batch_norm_frozen(x, mean, inv_std, gamma, beta, slope=1.0):
     def backward(s, needs):
         if F.grad_enabled():                       # a recorded sweep: the gradient of x only, as a differentiable operation
             if needs[1] or needs[2]:
-                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
-                                          'only (straight into the fp32 gradient arena)')
+                _into_arena(None, 'batch-norm parameter')        # (a recorded sweep accumulates into nothing)
             return (_frozen_scale(s, gamma, inv_std.data, meta.mask_ref, meta.slope) if needs[0] else None), None, None
         for need, parameter in ((needs[1], gamma), (needs[2], beta)):
-            if need and not accumulates_into(parameter):
-                raise NotImplementedError('the 16-bit path computes batch-norm parameter gradients in plain backward sweeps '
-                                          'only (straight into the fp32 gradient arena)')
+            if need:
+                _into_arena(parameter, 'batch-norm parameter')
         if not any(needs):
             return None, None, None
         back = _frozen_backward(s, x.data if needs[1] else None, mean.data, inv_std.data, gamma, meta.mask_ref, meta.slope, needs[0],
