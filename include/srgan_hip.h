@@ -67,6 +67,8 @@ const char* srgan_last_error(void);
                                                    second order, of a norm with given statistics on blocked tensors) */
 #define SRGAN_FEATURE_DEVICE_DRAWS 0x400u /* ABI 1.1, additive: srgan_random_fill / srgan_random_advance (an iteration's random
                                              tensors from a counter-based generator on the device) */
+#define SRGAN_FEATURE_IMAGE_SUMMARIES 0x800u /* ABI 1.1, additive: srgan_image_grid / srgan_density_heatmaps (a summary step's
+                                               image grids and crowd map heatmaps built on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -445,6 +447,38 @@ int srgan_crowd_resize_bilinear(const float* in, int32_t B, int32_t h, int32_t w
 int srgan_crowd_blend_windows(const float* densities, const float* counts, const int32_t* ys, int32_t ny, const int32_t* xs,
                               int32_t nx, int32_t H, int32_t W, int32_t P, float* out_density, float* out_count,
                               void* stream);
+
+/* ---- image summaries on the device (SRGAN_FEATURE_IMAGE_SUMMARIES) --------------------------------------------------------
+ * The pictures the reference writes at every summary step (age/srgan.py:73-90, driving/srgan.py:68-85,
+ * crowd/srgan.py:119-145,193-245), which it builds on the host with torchvision.utils.make_grid and matplotlib after downloading
+ * whole batches.  Both kernels are gathers: every output element is written exactly once, whatever `out` / `tiles` held before.
+ *
+ * srgan_image_grid: torchvision's make_grid of one contiguous batch.  images [N, C, H, W], C in {1, 3}; out [3, GH, GW] (one
+ * channel is replicated).  N == 1: out is the image itself (GH = H, GW = W, no padding).  Otherwise xmaps = min(nrow, N),
+ * ymaps = ceil(N / xmaps), GH = ymaps * (H + padding) + padding, GW = xmaps * (W + padding) + padding; image k sits at rows
+ * (k / xmaps) * (H + padding) + padding ... and columns (k % xmaps) * (W + padding) + padding ...; everything else, the cells
+ * after image N - 1 in the last row included, is pad_value (never normalised).  normalize != 0:
+ * v = (min(max(x, low), high) - low) / max(high - low, 1e-5f) in fp32 with a correctly rounded division -- the rule of current
+ * torchvision; releases old enough to take `range=` divided by (high - low + 1e-5) instead, at most 1e-5 relative away.
+ * Before any device work: a NULL pointer, N < 1, C outside {1, 3}, H or W < 1, nrow < 1, padding < 0, or normalize with a
+ * non-finite bound or high < low: SRGAN_EINVAL; out above max_tensor_elements: SRGAN_ERANGE. */
+int srgan_image_grid(const float* images, int32_t N, int32_t C, int32_t H, int32_t W, int32_t nrow, int32_t padding,
+                     float pad_value, int32_t normalize, float low, float high, float* out, void* stream);
+/* srgan_density_heatmaps: the reference's convert_density_maps_to_heatmaps (crowd/srgan.py:193-217) for a whole batch and every
+ * map head.  labels [B, h, w]; predicted [B, M, h, w]; lut [lut_entries, 3] RGB (matplotlib's inferno: 256 entries), all on the
+ * device.  For each pair (b, m): vmin = min(min labels[b], min predicted[b, m]), vmax likewise, written to ranges[b, m, 0..1]
+ * (ranges: [B, M, 2] floats).  A pixel of a map is first resized to P x P with exactly the arithmetic of
+ * srgan_crowd_resize_bilinear (h == P and w == P: the identity, bit for bit); then t = (v - vmin) / (vmax - vmin) in fp32, t = 0
+ * when vmax == vmin; the entry is (int)(t * lut_entries) truncated, lut_entries itself becomes lut_entries - 1, a negative t
+ * gives entry 0 and anything above the last entry -- matplotlib's Normalize followed by Colormap.__call__ on a float32 array.
+ * For example b the M + 1 planar RGB tiles [3, P, P] start at tiles + b * tile_stride (in floats; tile_stride >= (M + 1) * 3 *
+ * P * P lets the caller leave a slot for the photograph in front of each row of tiles): first the label under the range of pair
+ * (b, 0) -- the reference computes it for every m and keeps only that one -- then the M predictions, each under its own pair's
+ * range.  Inputs are finite.  Two launches, no host round trip.  Argument errors (NULL, B / M / h / w / P / lut_entries < 1, a
+ * short tile_stride): SRGAN_EINVAL; P < h or P < w: SRGAN_EUNSUPPORTED, as in srgan_crowd_resize_bilinear; a tensor above
+ * max_tensor_elements or more than 65535 tiles: SRGAN_ERANGE. */
+int srgan_density_heatmaps(const float* labels, const float* predicted, int32_t B, int32_t M, int32_t h, int32_t w, int32_t P,
+                           const float* lut, int32_t lut_entries, float* tiles, int64_t tile_stride, float* ranges, void* stream);
 
 /* Offline ikNN label of a crowd scene (reference crowd/database_preprocessor.py:93-101,266-290: generate_knn_map +
  * 1 / (map + epsilon)): out[y, x] = 1 / (mean over the k nearest heads of the Euclidean distance from (y, x), each

@@ -52,5 +52,7 @@ class AgeExperiment(Experiment):
             self.DNN = Discriminator(image_size=size, **d_norm)
 
     def validation_summaries(self, step):
-        """MAE / MSE of DNN and D on the train and validation batches (reference age/srgan.py:52-71,92-107)."""
+        """MAE / MSE of DNN and D on the train and validation batches (reference age/srgan.py:52-71,92-107) and, with
+        ``settings.image_summaries``, the ``Real`` / ``Fake/Standard`` / ``Fake/Offset`` grids (:73-90)."""
         self.regression_validation_summaries()
+        self.regression_image_summaries()

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from .. import functional as F
+from .. import image_summaries
 from ..srgan import Experiment, as_var
 from ..tape import no_grad
 from .data import CrowdExample, DeviceSlidingWindows, ImageSlidingWindowDataset
@@ -58,7 +59,9 @@ class CrowdExperiment(Experiment):
     def validation_summaries(self, step):
         """The scalar summaries of reference crowd/srgan.py:98-147 when evaluation datasets are attached
         (``train_dataset`` / ``validation_dataset``: indexable, items ``(image, label, map)``; ``dataset_class`` for the
-        full-image test summaries); the image grids of the reference are out of scope."""
+        full-image test summaries).  With ``settings.image_summaries`` the pictures of :119-145 follow the scalars: the map
+        comparisons ``Real`` / ``Validation`` of both networks when the datasets are attached (``map_comparison_summaries``)
+        and G's samples ``Fake/Standard`` / ``Fake/Offset`` over (-1, 1)."""
         train_dataset = getattr(self, 'train_dataset', None)
         validation_dataset = getattr(self, 'validation_dataset', None)
         if train_dataset is not None and validation_dataset is not None:
@@ -69,8 +72,37 @@ class CrowdExperiment(Experiment):
             self.evaluation_epoch(settings, self.D, train_dataset, self.gan_summary_writer, '2 Train Error', shuffle=False)
             self.evaluation_epoch(settings, self.D, validation_dataset, self.gan_summary_writer, '1 Validation Error',
                                   comparison_value=dnn_validation_count_mae, shuffle=False)
+        if self.image_summaries_on():
+            if train_dataset is not None and validation_dataset is not None:
+                self.map_comparison_summaries(((self.D, self.gan_summary_writer), (self.DNN, self.dnn_summary_writer)))
+            self.generated_image_summaries(range=(-1, 1))
         if getattr(self, 'dataset_class', None) is not None:
             self.test_summaries()
+
+    def map_comparison_summaries(self, networks_and_writers):
+        """``Real`` from the first three items of ``train_dataset`` and ``Validation`` from the first three of
+        ``validation_dataset``, for every ``(network, writer)``: image | ikNN map | predicted maps (reference
+        crowd/srgan.py:119-135, crowd/dnn.py:82-91).  The reference reads ``train_dataset`` for ``Validation`` too (:128) -- a
+        slip, the tag says validation -- which is not reproduced."""
+        for tag, dataset in (('Real', self.train_dataset), ('Validation', self.validation_dataset)):
+            items = [dataset[index] for index in range(min(3, len(dataset)))]
+            images = as_var(torch.stack([torch.as_tensor(item[0]) for item in items]).float())
+            maps = as_var(torch.stack([torch.as_tensor(item[2]) for item in items]).float())
+            for network, writer in networks_and_writers:
+                with no_grad():
+                    _, _, predicted_maps = self.images_to_predicted_labels(network, images)
+                writer.add_image(tag, self.create_map_comparison_image(images, maps, predicted_maps))
+
+    def convert_density_maps_to_heatmaps(self, label, predicted_label):
+        """The reference's name (crowd/srgan.py:193-217) for one (map, predicted map) pair ``[h, w]``: the two inferno
+        heatmaps ``[3, P, P]`` at ``settings.image_patch_size`` under the pair's common range, on the device."""
+        tiles, _ = image_summaries.density_heatmaps(as_var(label).data[None], as_var(predicted_label).data[None, None],
+                                                    self.settings.image_patch_size)
+        return tiles[0, 0], tiles[0, 1]
+
+    def create_map_comparison_image(self, images, labels, predicted_labels, number_of_images=3):
+        """The reference's name (crowd/srgan.py:219-245) for ``image_summaries.map_comparison_image``."""
+        return image_summaries.map_comparison_image(images, labels, predicted_labels, number_of_images)
 
     def images_to_predicted_labels(self, network, images):
         """reference crowd/srgan.py:256-259"""

@@ -92,6 +92,19 @@ __device__ __forceinline__ void bilinear_source(float scale, int destination, in
   w_hi = source - (float)lo;
 }
 
+// One output element of a bilinear resize: the row taps (top / bottom rows of the source plane, weight ly of the bottom
+// one) come from bilinear_source on the output row, the column taps are taken here; the two horizontal lerps first.  The
+// resize arithmetic of srgan_crowd_resize_bilinear and of srgan_density_heatmaps -- stated once.  Equal extents: lx = ly = 0
+// and the result is top[ox] itself.
+__device__ __forceinline__ float bilinear_row_sample(const float* __restrict__ top, const float* __restrict__ bottom, float ly,
+                                                     float scale_x, int ox, int w) {
+  int x0, x1;
+  float lx;
+  bilinear_source(scale_x, ox, w, x0, x1, lx);
+  const float hx = 1.f - lx;
+  return (1.f - ly) * (hx * top[x0] + lx * top[x1]) + ly * (hx * bottom[x0] + lx * bottom[x1]);
+}
+
 // Grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs x 8, never more than the work.
 inline unsigned stream_grid(int64_t work_items, int per_block) {
   int64_t blocks = (work_items + per_block - 1) / per_block;

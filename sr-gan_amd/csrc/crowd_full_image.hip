@@ -8,8 +8,8 @@
 namespace srgan {
 
 // out[b, oy, ox] of a [B, h, w] -> [B, P, P] upscale with half-pixel centres and clamped edges: the arithmetic of
-// torch.nn.functional.interpolate(mode='bilinear', align_corners=False) (bilinear_source, common.h; the two horizontal
-// lerps first).  Values are not rescaled: sums change.
+// torch.nn.functional.interpolate(mode='bilinear', align_corners=False) (bilinear_source and bilinear_row_sample, common.h: the two
+// horizontal lerps first).  Values are not rescaled: sums change.
 template <int VEC>
 __global__ __launch_bounds__(256) void crowd_resize_bilinear_kernel(const float* __restrict__ in, int h, int w, int P,
                                                                     int64_t runs, float* __restrict__ out) {
@@ -25,13 +25,7 @@ __global__ __launch_bounds__(256) void crowd_resize_bilinear_kernel(const float*
     const float* bottom = in + (b * h + y1) * w;
     float v[VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      int x0, x1;
-      float lx;
-      bilinear_source(scale_x, ox + i, w, x0, x1, lx);
-      const float hx = 1.f - lx;
-      v[i] = (1.f - ly) * (hx * top[x0] + lx * top[x1]) + ly * (hx * bottom[x0] + lx * bottom[x1]);
-    }
+    for (int i = 0; i < VEC; ++i) v[i] = bilinear_row_sample(top, bottom, ly, scale_x, ox + i, w);
     if constexpr (VEC == 4) {
       *reinterpret_cast<float4*>(out + at) = make_float4(v[0], v[1], v[2], v[3]);
     } else {

@@ -104,4 +104,13 @@ int stem7x7_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
 int stem7x7_bwd_data_run(const float* gy, int64_t gy_bs, const float* w, float* gx, int64_t gx_bs, int32_t N, int32_t H,
                          int32_t W, int32_t K, int32_t OH, int32_t OW, hipStream_t stream);
 
+
+// image_summaries.hip: the image grid and the crowd map heatmaps of a summary step (contracts: srgan_image_grid,
+// srgan_density_heatmaps; arguments already checked).
+int image_grid_run(const float* images, int32_t N, int32_t C, int32_t H, int32_t W, int32_t nrow, int32_t padding, float pad_value,
+                   int32_t normalize, float low, float high, float* out, hipStream_t stream);
+int density_heatmaps_run(const float* labels, const float* predicted, int32_t B, int32_t M, int32_t h, int32_t w, int32_t P,
+                         const float* lut, int32_t lut_entries, float* tiles, int64_t tile_stride, float* ranges,
+                         hipStream_t stream);
+
 }  // namespace srgan

@@ -39,5 +39,7 @@ class DrivingExperiment(Experiment):
         self.DNN = Discriminator(image_size=self.image_size, **d_norm)
 
     def validation_summaries(self, step):
-        """MAE / NMAE / MSE of DNN and D on the train and validation batches (reference driving/srgan.py:48-67,87-104)."""
+        """MAE / NMAE / MSE of DNN and D on the train and validation batches (reference driving/srgan.py:48-67,87-104)
+        and, with ``settings.image_summaries``, the ``Real`` / ``Fake/Standard`` / ``Fake/Offset`` grids (:68-85)."""
         self.regression_validation_summaries(normalized=True)
+        self.regression_image_summaries()

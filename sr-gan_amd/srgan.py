@@ -34,7 +34,8 @@ from . import nn
 from .optim import Adam
 from .settings import Settings
 from .tape import Var, backward, no_grad
-from .utility import SummaryWriter, MixtureModel, current_device, make_directory_name_unique, seed_all
+from . import image_summaries
+from .utility import SummaryWriter, MixtureModel, current_device, make_directory_name_unique, seed_all, to_image_range
 
 
 def as_var(value, staged=False):
@@ -1048,7 +1049,7 @@ class Experiment(ABC):
 
     def regression_validation_summaries(self, normalized=False):
         """DNN and D on the train and validation batches, D's validation MAE relative to the DNN's (reference
-        age/srgan.py:52-71, driving/srgan.py:48-67; the image grids are out of scope).  A loader over a database
+        age/srgan.py:52-71, driving/srgan.py:48-67; the image grids: ``regression_image_summaries``).  A loader over a database
         (``in_order``) is walked once in stored order, every example of the split as upstream; any other loader is iterated."""
         train, validation = (loader.in_order() if hasattr(loader, 'in_order') else loader
                              for loader in (self.train_dataset_loader, self.validation_dataset_loader))
@@ -1058,6 +1059,59 @@ class Experiment(ABC):
         self.regression_evaluation_epoch(self.D, train, self.gan_summary_writer, '2 Train Error', normalized=normalized)
         self.regression_evaluation_epoch(self.D, validation, self.gan_summary_writer, '1 Validation Error',
                                          comparison_value=dnn_mae, normalized=normalized)
+
+    # ``settings.image_summaries`` (read with getattr, default off): the pictures the reference writes at every summary step --
+    # grids of training images and of G's samples, the crowd map comparison -- built on the device (``image_summaries.py``)
+    # and downloaded once each by ``SummaryWriter.add_image``.  Nothing here draws from a host stream or advances a loader's
+    # schedule, so a run trains the same bits with the setting on and off.
+    SUMMARY_DRAW_STANDARD, SUMMARY_DRAW_OFFSET = 8, 9      # draw ids of the two summary z (the training draws are 0, 1, 2)
+
+    def image_summaries_on(self):
+        """Under data parallelism only the rank that writes the trial's event files launches anything (no collective is
+        involved: G in eval mode and the two image kernels are local)."""
+        return bool(getattr(self.settings, 'image_summaries', False)) and (self.dp is None or self.dp.rank == 0)
+
+    def real_image_summary(self, examples, range):
+        """``Real`` on the GAN writer: the first ``min(9, B)`` of ``examples`` in a grid three wide (reference
+        age/srgan.py:74-78).  The callers pass the train loader's first batch in STORED order: the reference shows a shuffled
+        batch, which would consume torch's generator."""
+        examples = examples.data if isinstance(examples, Var) else examples
+        self.gan_summary_writer.add_image('Real', image_summaries.make_grid(examples[:9], nrow=3, normalize=True, range=range))
+
+    def first_train_batch(self):
+        """The examples of the train loader's first batch, in stored order where the loader can walk it (``in_order``)."""
+        loader = self.train_dataset_loader
+        return next(iter(loader.in_order() if hasattr(loader, 'in_order') else loader))[0]
+
+    def generated_image_summaries(self, range, to_images=None):
+        """``Fake/Standard`` and ``Fake/Offset`` on the GAN writer (reference age/srgan.py:79-90): G on ``min(9, batch_size)``
+        z drawn on the device -- N(0, 1), and the mixture at ``settings.mean_offset`` -- from a state of its own,
+        ``{device_random_seed, the writer's step}``, and draws 8 and 9: not the training draws' state, whether or not
+        ``settings.device_random_draws`` is set.  ``to_images`` maps G's output to the value range ``range`` names."""
+        count = min(9, self.settings.batch_size)
+        state = self.summary_draw_state(self.gan_summary_writer.step)
+        for tag, draw, offset in (('Fake/Standard', self.SUMMARY_DRAW_STANDARD, 0.0),
+                                  ('Fake/Offset', self.SUMMARY_DRAW_OFFSET, self.settings.mean_offset)):
+            z = F.random_fill((count, self.G.input_size), 1, offset, draw, state)
+            with no_grad():
+                fake = self.G(z).data
+            if to_images is not None:
+                fake = to_images(fake)
+            self.gan_summary_writer.add_image(tag, image_summaries.make_grid(fake, nrow=3, normalize=True, range=range))
+
+    def summary_draw_state(self, step):
+        """Device int32 x 4 {seed_lo, seed_hi, step, 0} for the summary draws of ``step`` (``srgan_random_fill``'s state)."""
+        seed = int(getattr(self.settings, 'device_random_seed', 0)) & (2 ** 64 - 1)
+        words = np.array([seed & 0xffffffff, seed >> 32, int(step) & 0xffffffff, 0], dtype=np.uint32)
+        return torch.from_numpy(words.view(np.int32)).to(current_device())
+
+    def regression_image_summaries(self):
+        """The image grids of the age and driving applications (reference age/srgan.py:73-90, driving/srgan.py:68-85): images
+        in 0..255 through ``to_image_range``, normalised over (0, 255)."""
+        if not self.image_summaries_on():
+            return
+        self.real_image_summary(to_image_range(self.first_train_batch()[:9]), range=(0, 255))
+        self.generated_image_summaries(range=(0, 255), to_images=to_image_range)
 
     @staticmethod
     def infinite_iter(dataset):

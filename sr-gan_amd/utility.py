@@ -40,8 +40,9 @@ gpu = _LazyDevice()
 
 
 class SummaryWriter:
-    """Scalar logger with the reference wrapper's interface (utility.py:21-49): implicit ``step``,
-    ``summary_period``, ``is_summary_step``.  Records in memory; forwards to tensorboardX when installed."""
+    """Scalar and image logger with the reference wrapper's interface (utility.py:21-49): implicit ``step``,
+    ``summary_period``, ``is_summary_step``.  Records in memory (every scalar; the most recent image per tag); forwards to
+    tensorboardX when installed."""
 
     def __init__(self, log_dir=None, comment='', summary_period=1, steps_to_run=-1, **kwargs):
         self.log_dir = log_dir
@@ -49,6 +50,7 @@ class SummaryWriter:
         self.summary_period = summary_period
         self.steps_to_run = steps_to_run
         self.scalars = {}
+        self.images = {}               # tag -> (step, float32 ndarray [3, H, W]) of the most recent add_image
         self._backend = None
         if log_dir is not None:
             try:
@@ -67,8 +69,19 @@ class SummaryWriter:
     def add_histogram(self, *args, **kwargs):
         pass
 
-    def add_image(self, *args, **kwargs):
-        pass
+    def add_image(self, tag, img_tensor, global_step=None, **kwargs):
+        """``img_tensor``: a ``[3, H, W]`` picture (a device tensor from ``image_summaries``, or anything NumPy reads); it is
+        downloaded once, here."""
+        if global_step is None:
+            global_step = self.step
+        if isinstance(img_tensor, Var):
+            img_tensor = img_tensor.data
+        if isinstance(img_tensor, torch.Tensor):
+            img_tensor = img_tensor.detach().cpu().numpy()
+        image = np.asarray(img_tensor, dtype=np.float32)
+        self.images[tag] = (global_step, image)
+        if self._backend is not None:
+            self._backend.add_image(tag, image, global_step, **kwargs)
 
     def is_summary_step(self):
         return self.step % self.summary_period == 0 or self.step == self.steps_to_run - 1
