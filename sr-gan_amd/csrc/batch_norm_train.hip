@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void bn_train_stats_kernel(const float* __rest
                                                              float* running_var, long long* batches_tracked, float momentum,
                                                              float eps, int N, int C, int64_t HW, int images_per_block,
                                                              float* partial, unsigned int* tickets) {
-  __shared__ Moments scratch[4];
-  __shared__ int last;
+  __shared__ Moments scratch[4][1];
   const int tid = (int)threadIdx.x, c = (int)blockIdx.x, part = (int)blockIdx.y, parts = (int)gridDim.y;
   const int n0 = part * images_per_block, n1 = min(N, n0 + images_per_block);
   const int per_plane = (int)(HW / W), total = (n1 - n0) * per_plane;
@@ -84,30 +83,9 @@ __global__ __launch_bounds__(256) void bn_train_stats_kernel(const float* __rest
       }
     mine = merge_moments(mine, tile);
   }
-  Moments all = block_moments_256(mine, scratch);          // thread 0: this workgroup's images
-  if (parts > 1) {
-    // The channel's workgroups meet in the workspace in part order (memory model: split_finish.h).
-    float* row = partial + (int64_t)c * parts * 3;
-    unsigned int* ticket = tickets + c;
-    if (tid == 0) {
-      __hip_atomic_store(row + part * 3 + 0, all.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(row + part * 3 + 1, all.mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(row + part * 3 + 2, all.m2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    Moments sum{0.f, 0.f, 0.f};
-    for (int s = tid; s < parts; s += 256) {
-      const Moments p{__hip_atomic_load(row + s * 3 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                      __hip_atomic_load(row + s * 3 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                      __hip_atomic_load(row + s * 3 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-      sum = merge_moments(sum, p);
-    }
-    all = block_moments_256(sum, scratch);
-    if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  Moments all = block_moments_256(mine, scratch[0]);       // thread 0: this workgroup's images
+  // the channel's workgroups meet in the workspace in part order (split_finish.h)
+  if (!ordered_lane_finish<LaneMoments, 1>(all, partial + (int64_t)c * parts * 3, part, parts, tickets + c, scratch)) return;
   if (tid != 0) return;
   const float variance = all.m2 / all.n;                   // biased: the one the batch is normalised with
   mean_out[c] = all.mean;
@@ -245,21 +223,17 @@ static int finish_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, in
 int bn_train_stats_run(const float* x, float* mean, float* inv_std, float* running_mean, float* running_var,
                        int64_t* num_batches_tracked, float momentum, float eps, int32_t N, int32_t C, int64_t HW,
                        hipStream_t stream) {
-  int per = images_per_workgroup(N, C, HW);
-  int parts = (N + per - 1) / per;
-  unsigned int* tickets = nullptr;
-  float* partial = parts > 1 ? row_finish_workspace(C, parts, 3, g_bn_train_tickets, stream, &tickets) : nullptr;
-  if (!partial) { per = N; parts = 1; }          // no workspace for this stream: one workgroup per channel
-  SRGAN_REQUIRE(parts <= 65535, SRGAN_ERANGE, "srgan_batch_norm_train_stats grid");
+  RowFinishGrid grid{images_per_workgroup(N, C, HW)};
+  if (const int status = row_finish_grid(C, N, 3, g_bn_train_tickets, stream, "srgan_batch_norm_train_stats grid", &grid)) return status;
   const int slot = profile_bracket_begin(stream);
   if (vectorisable(HW, {x}))
-    hipLaunchKernelGGL(bn_train_stats_kernel<4>, dim3(C, parts), dim3(256), 0, stream, x, mean, inv_std, running_mean, running_var,
-                       reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, HW, per, partial, tickets);
+    hipLaunchKernelGGL(bn_train_stats_kernel<4>, dim3(C, grid.parts), dim3(256), 0, stream, x, mean, inv_std, running_mean, running_var,
+                       reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, HW, grid.per, grid.partial, grid.tickets);
   else
-    hipLaunchKernelGGL(bn_train_stats_kernel<1>, dim3(C, parts), dim3(256), 0, stream, x, mean, inv_std, running_mean, running_var,
-                       reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, HW, per, partial, tickets);
+    hipLaunchKernelGGL(bn_train_stats_kernel<1>, dim3(C, grid.parts), dim3(256), 0, stream, x, mean, inv_std, running_mean, running_var,
+                       reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 20, per, parts, 1.0);
+  finish_bracket(slot, stream, N, C, HW, 20, grid.per, grid.parts, 1.0);
   return status;
 }
 
@@ -282,21 +256,17 @@ int bn_train_fwd_run(const float* x, const float* mean, const float* inv_std, co
 int bn_train_bwd_reduce_run(const float* g, const float* x, const float* mean, const float* inv_std, const float* gamma,
                             const float* beta, float slope, float* sums, float* g_gamma, float* g_beta, int32_t N, int32_t C,
                             int64_t HW, hipStream_t stream) {
-  int per = images_per_workgroup(N, C, HW);
-  int parts = (N + per - 1) / per;
-  unsigned int* tickets = nullptr;
-  float* partial = parts > 1 ? row_finish_workspace(C, parts, 2, g_bn_train_tickets, stream, &tickets) : nullptr;
-  if (!partial) { per = N; parts = 1; }
-  SRGAN_REQUIRE(parts <= 65535, SRGAN_ERANGE, "srgan_batch_norm_train_bwd_reduce grid");
+  RowFinishGrid grid{images_per_workgroup(N, C, HW)};
+  if (const int status = row_finish_grid(C, N, 2, g_bn_train_tickets, stream, "srgan_batch_norm_train_bwd_reduce grid", &grid)) return status;
   const int slot = profile_bracket_begin(stream);
   if (vectorisable(HW, {g, x}))
-    hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<4>, dim3(C, parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
-                       sums, g_gamma, g_beta, N, C, HW, per, partial, tickets);
+    hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<4>, dim3(C, grid.parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
+                       sums, g_gamma, g_beta, N, C, HW, grid.per, grid.partial, grid.tickets);
   else
-    hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<1>, dim3(C, parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
-                       sums, g_gamma, g_beta, N, C, HW, per, partial, tickets);
+    hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<1>, dim3(C, grid.parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
+                       sums, g_gamma, g_beta, N, C, HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 22, per, parts, 2.0);
+  finish_bracket(slot, stream, N, C, HW, 22, grid.per, grid.parts, 2.0);
   return status;
 }
 

@@ -44,7 +44,6 @@ __global__ __launch_bounds__(256) void h_bn_stats_kernel(const Slot* __restrict_
                                                          int HW, int images_per_block, float* partial, unsigned int* tickets) {
   constexpr int G = HGroup<PREC>::N;
   __shared__ Moments scratch[4][G];
-  __shared__ int last;
   const int tid = (int)threadIdx.x, g = (int)blockIdx.x, CG = (int)gridDim.x, part = (int)blockIdx.y, parts = (int)gridDim.y;
   const int n0 = part * images_per_block, n1 = min(N, n0 + images_per_block);
   const int total = (n1 - n0) * HW;
@@ -96,43 +95,8 @@ __global__ __launch_bounds__(256) void h_bn_stats_kernel(const Slot* __restrict_
   __syncthreads();
   Moments mine{0.f, 0.f, 0.f};                             // thread j < G: channel j of this workgroup's images
   if (tid < G) mine = merge_four_moments(scratch[0][tid], scratch[1][tid], scratch[2][tid], scratch[3][tid]);
-  if (parts > 1) {
-    // The group's workgroups meet in the workspace in part order (memory model: split_finish.h -- every store acknowledged,
-    // the barrier, then thread 0 takes the ticket).
-    float* row = partial + (int64_t)g * parts * (3 * G);
-    unsigned int* ticket = tickets + g;
-    if (tid < G) {
-      float* out = row + (part * G + tid) * 3;
-      __hip_atomic_store(out + 0, mine.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(out + 1, mine.mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(out + 2, mine.m2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
-    __syncthreads();
-    if (!last) return;
-    // thread t merges the parts t, t + 256, ... of all g channels (their loads in flight together), then the same tree
-    Moments sum[G];
-#pragma unroll
-    for (int j = 0; j < G; ++j) sum[j] = Moments{0.f, 0.f, 0.f};
-    for (int s = tid; s < parts; s += 256) {
-      const float* theirs = row + s * (3 * G);
-      float p[3 * G];
-#pragma unroll
-      for (int i = 0; i < 3 * G; ++i) p[i] = __hip_atomic_load(theirs + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int j = 0; j < G; ++j) sum[j] = merge_moments(sum[j], Moments{p[3 * j], p[3 * j + 1], p[3 * j + 2]});
-    }
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const Moments w = wave_moments(sum[j]);
-      if (lane == 0) scratch[wave][j] = w;                 // (its readers above passed two barriers since)
-    }
-    __syncthreads();
-    if (tid < G) mine = merge_four_moments(scratch[0][tid], scratch[1][tid], scratch[2][tid], scratch[3][tid]);
-    if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  // the group's workgroups meet in the workspace in part order, in the same tree (split_finish.h)
+  if (!ordered_lane_finish<LaneMoments, G>(mine, partial + (int64_t)g * parts * (3 * G), part, parts, tickets + g, scratch)) return;
   const int c = g * G + tid;
   if (tid == 0 && g == 0 && batches_tracked) *batches_tracked += 1;
   if (tid >= G || c >= C) return;
@@ -340,12 +304,10 @@ __global__ __launch_bounds__(256) void h_frozen_norm_bwd_kernel(const Slot* __re
   }
   if constexpr (SUMS >= 1) {
     // the workgroup's V sums with ONE barrier (every wave's butterfly first, then the four waves in a fixed order: thread i holds
-    // sum i), then the workgroups of the group in part order through the workspace -- the ticket protocol of split_finish.h as
-    // h_bn_stats_kernel walks it, all V values side by side: V barriers in a row in the last workgroup cost more than its loads
+    // sum i), then the workgroups of the group in part order through the workspace, in the same tree (split_finish.h)
     __shared__ float waves[4][V];
-    __shared__ int last;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int part = (int)blockIdx.y, parts = (int)gridDim.y;
+    const int parts = (int)gridDim.y;
 #pragma unroll
     for (int j = 0; j < G; ++j) {
       const float p = wave_sum(plain[j]);
@@ -358,35 +320,7 @@ __global__ __launch_bounds__(256) void h_frozen_norm_bwd_kernel(const Slot* __re
     __syncthreads();
     float mine = 0.f;                                        // thread i < V: sum i of this workgroup's images
     if (tid < V) mine = (waves[0][tid] + waves[1][tid]) + (waves[2][tid] + waves[3][tid]);
-    if (parts > 1) {
-      float* row = partial + (int64_t)g * parts * V;
-      unsigned int* ticket = tickets + g;
-      if (tid < V) __hip_atomic_store(row + part * V + tid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store acknowledged, the barrier, then thread 0 takes the ticket
-      __syncthreads();
-      if (tid == 0) last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
-      __syncthreads();
-      if (!last) return;
-      // thread t adds the parts t, t + 256, ... of all V sums (their loads in flight together), then the same tree
-      float sum[V];
-#pragma unroll
-      for (int i = 0; i < V; ++i) sum[i] = 0.f;
-      for (int p = tid; p < parts; p += 256) {
-        float theirs[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) theirs[i] = __hip_atomic_load(row + p * V + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 0; i < V; ++i) sum[i] += theirs[i];
-      }
-#pragma unroll
-      for (int i = 0; i < V; ++i) {
-        const float w = wave_sum(sum[i]);
-        if (lane == 0) waves[wave][i] = w;                   // (its readers above passed two barriers since)
-      }
-      __syncthreads();
-      if (tid < V) mine = (waves[0][tid] + waves[1][tid]) + (waves[2][tid] + waves[3][tid]);
-      if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (!ordered_lane_finish<LaneSums, V>(mine, partial + (int64_t)g * parts * V, (int)blockIdx.y, parts, tickets + g, waves)) return;
     // thread j adds sum s of channel j to g_beta, thread G + j the weighted sum to g_gamma
     const int j = tid < G ? tid : tid - G;
     if (tid >= V || j >= live) return;
@@ -407,7 +341,7 @@ static int h_bn_arguments(int32_t N, int32_t C, int64_t HW, int32_t dtype, bool 
   return SRGAN_OK;
 }
 
-struct HBnGrid { int group, CG, per, parts; };
+struct HBnGrid : RowFinishGrid { int group, CG; };
 
 // Images per workgroup as the NCHW kernels choose them, a slot counted as its 16 bytes = four fp32 elements.
 static HBnGrid h_bn_grid(int32_t N, int32_t C, int64_t HW, int32_t dtype) {
@@ -451,7 +385,7 @@ static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int6
   } while (0)
 #define H_FROZEN_ARGUMENTS                                                                                                        \
   (const Slot*)s, (const Slot*)x, mean, inv_std, gamma, (const Slot*)ref, slope, (Slot*)gx, g_gamma, g_beta, N, C, (int)HW, grid.per, \
-      partial, tickets
+      grid.partial, grid.tickets
 
 int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma, const void* ref,
                           float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW, int32_t dtype,
@@ -470,13 +404,11 @@ int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const
   while (sums && grid.per < N && (int64_t)grid.per * HW < 4096 && (int64_t)grid.CG * ((N + 2 * grid.per - 1) / (2 * grid.per)) >= 256)
     grid.per *= 2;
   grid.parts = (N + grid.per - 1) / grid.per;
-  unsigned int* tickets = nullptr;
-  float* partial = nullptr;
   if (sums) {
-    if (grid.parts > 1) partial = row_finish_workspace(grid.CG, grid.parts, sums * grid.group, g_h_bn_tickets, stream, &tickets);
-    if (!partial) { grid.per = N; grid.parts = 1; }        // no workspace for this stream: one workgroup per group
+    if (const int status = row_finish_grid(grid.CG, N, sums * grid.group, g_h_bn_tickets, stream, "srgan_h_frozen_norm_bwd grid", &grid)) return status;
+  } else {
+    SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_frozen_norm_bwd grid");
   }
-  SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_frozen_norm_bwd grid");
   const int slot = profile_bracket_begin(stream);
   if (gx && sums == 2) H_FROZEN_LAUNCH(true, 2);
   else if (gx && sums == 1) H_FROZEN_LAUNCH(true, 1);
@@ -501,13 +433,10 @@ int srgan_h_batch_norm_stats(const void* x, float* mean, float* inv_std, float* 
   SRGAN_REQUIRE(eps >= 0.f, SRGAN_EINVAL, "srgan_h_batch_norm_stats arguments");
   hipStream_t s = (hipStream_t)stream;
   HBnGrid grid = h_bn_grid(N, C, HW, dtype);
-  unsigned int* tickets = nullptr;
-  float* partial = grid.parts > 1 ? row_finish_workspace(grid.CG, grid.parts, 3 * grid.group, g_h_bn_tickets, s, &tickets) : nullptr;
-  if (!partial) { grid.per = N; grid.parts = 1; }          // no workspace for this stream: one workgroup per group
-  SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_batch_norm_stats grid");
+  if (const int status = row_finish_grid(grid.CG, N, 3 * grid.group, g_h_bn_tickets, s, "srgan_h_batch_norm_stats grid", &grid)) return status;
   const int slot = profile_bracket_begin(s);
   H_BN_LAUNCH(h_bn_stats_kernel, dtype, dim3(grid.CG, grid.parts), s, (const Slot*)x, mean, inv_std, running_mean, running_var,
-              reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, (int)HW, grid.per, partial, tickets);
+              reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
   h_bn_bracket(slot, s, N, C, HW, dtype, 20, grid, 1.0);
   return status;
@@ -534,13 +463,10 @@ int srgan_h_batch_norm_bwd_reduce(const void* s, const void* x, const float* mea
     return status;
   hipStream_t st = (hipStream_t)stream;
   HBnGrid grid = h_bn_grid(N, C, HW, dtype);
-  unsigned int* tickets = nullptr;
-  float* partial = grid.parts > 1 ? row_finish_workspace(grid.CG, grid.parts, 2 * grid.group, g_h_bn_tickets, st, &tickets) : nullptr;
-  if (!partial) { grid.per = N; grid.parts = 1; }
-  SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_batch_norm_bwd_reduce grid");
+  if (const int status = row_finish_grid(grid.CG, N, 2 * grid.group, g_h_bn_tickets, st, "srgan_h_batch_norm_bwd_reduce grid", &grid)) return status;
   const int slot = profile_bracket_begin(st);
   H_BN_LAUNCH(h_bn_bwd_reduce_kernel, dtype, dim3(grid.CG, grid.parts), st, (const Slot*)s, (const Slot*)x, mean, inv_std, sums, g_gamma,
-              g_beta, N, C, (int)HW, grid.per, partial, tickets);
+              g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
   h_bn_bracket(slot, st, N, C, HW, dtype, 22, grid, 2.0);
   return status;

@@ -35,6 +35,16 @@ __device__ __forceinline__ Moments merge_four_moments(const Moments& w0, const M
   return merge_moments(merge_moments(w0, w1), merge_moments(w2, w3));
 }
 
+// The three above as the Ops of ordered_lane_finish (split_finish.h): the workgroups of a row meet in the tree of a workgroup.
+struct LaneMoments {
+  using Value = Moments;
+  static __device__ __forceinline__ Moments combine(const Moments& a, const Moments& b) { return merge_moments(a, b); }
+  static __device__ __forceinline__ Moments wave(const Moments& v) { return wave_moments(v); }
+  static __device__ __forceinline__ Moments four(const Moments& w0, const Moments& w1, const Moments& w2, const Moments& w3) {
+    return merge_four_moments(w0, w1, w2, w3);
+  }
+};
+
 // The 256 threads' moments in a fixed tree (shuffle-down inside each wave, then the four waves in order): thread 0.
 __device__ __forceinline__ Moments block_moments_256(Moments v, Moments* scratch4) {
   v = wave_moments(v);

@@ -2,8 +2,8 @@
 // (bias and batch-norm parameter gradients), per-example dot products over C*H*W (the gradient-penalty
 // norms: N = 1, C = batch), column sums over the batch (feature means: HW = 1) and full sums (C = 1).
 // Each wavefront reduces with cross-lane shuffles (64 lanes), each workgroup with 4 LDS words, and
-// workgroups combine with one hardware fp32 atomic per (channel, segment) -- or, for up to 64 rows (the penalty's
-// per-example norms, full sums), through workspace partials that the row's last workgroup adds in a fixed order.
+// workgroups combine with one hardware fp32 atomic per (channel, segment) -- or, for up to 4096 rows, through
+// workspace partials that the row's last workgroup adds in a fixed order (split_finish.h).
 // Roofline: HBM; algorithmic bytes = 4 * elements read per operand.
 #include "common.h"
 #include "split_finish.h"
@@ -89,50 +89,23 @@ __global__ __launch_bounds__(256) void chan_reduce_rows_kernel(const float* __re
   if (threadIdx.x == 0) unsafeAtomicAdd(out + blockIdx.x, total * (scale ? scale[blockIdx.x] : 1.f));
 }
 
-// The same reduction for FEW rows (<= ROW_TICKETS: the per-example norms of the gradient penalty, full sums) in ONE launch
-// and in a FIXED order: every workgroup leaves the sum of its run in `partial` (the caller's workspace), takes a ticket of its
-// row, and the workgroup that draws the last one adds the row's partials -- thread t the entries t, t + 256, ..., then the
-// usual tree -- and writes (or adds to) out[c].  No zero-fill launch in front, no fp32 atomics: two runs give the same bits,
-// whatever else is in flight.  The tickets are device globals, one set per registered (device, stream) workspace -- launches
-// on a stream are ordered, streams do not share a set -- and the last workgroup puts its row's back to zero.
-constexpr int ROW_TICKETS = 2048, TICKET_SETS = 64;      // (round 5: 2048 rows -- bias / parameter sums of wide layers take the ordered form too)
-__device__ unsigned int g_row_tickets[TICKET_SETS * ROW_TICKETS];
-
+// The same reduction in ONE launch and in a FIXED order, for up to ROW_FINISH_ROWS rows (the per-example norms of the gradient
+// penalty, full sums, bias / parameter sums): the row's workgroups meet through ordered_row_finish (split_finish.h), and the one
+// that holds the total writes (or adds to) out[c].  No zero-fill launch in front, no fp32 atomics.
 __device__ unsigned int g_reduce_finish_tickets[SPLIT_TICKET_SETS * ROW_FINISH_ROWS];
 
 __global__ __launch_bounds__(256) void chan_reduce_rows_ordered_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                        const float* __restrict__ mean,
                                                                        const float* __restrict__ scale,
                                                                        float* __restrict__ out, float* __restrict__ partial,
-                                                                       int ticket_set, int C, int64_t HW, int segs, int64_t seg,
+                                                                       unsigned int* tickets, int C, int64_t HW, int segs, int64_t seg,
                                                                        int accumulate) {
   __shared__ float scratch[4];
-  __shared__ int last;
   const int c = blockIdx.x, parts = (int)gridDim.y;
-  const float total = row_run_sum(a, b, mean, C, HW, segs, seg, scratch);
-  float* row = partial + (int64_t)c * parts;
-  unsigned int* ticket = g_row_tickets + ticket_set * ROW_TICKETS + c;
-  if (threadIdx.x == 0) {
-    // Device-scope atomics only (they act at the memory side: coherent across the eight XCDs' L2s by themselves); a
-    // device-scope FENCE here would write back / invalidate a whole L2 per workgroup (measured: 76 us for the 30 us
-    // reduction).  The partial (a write-through `sc1` store) must be ACKNOWLEDGED before the ticket is taken: store and
-    // ticket live in different L2 channels, so without the wait the row's last workgroup -- possibly on another XCD --
-    // could draw the final ticket and still read the previous launch's partial (a workgroup-scope release fence
-    // emits no instruction at all here; the ISA had the atomic straight behind the store).  Stores count in vmcnt on gfx9.
-    __hip_atomic_store(row + blockIdx.y, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
-  }
-  __syncthreads();
-  if (!last) return;
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < parts; i += 256) acc += __hip_atomic_load(row + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();                                     // (scratch is reused)
-  const float sum = block_sum_256(acc, scratch);
-  if (threadIdx.x == 0) {
-    const float value = sum * (scale ? scale[c] : 1.f);
+  float v[1] = {row_run_sum(a, b, mean, C, HW, segs, seg, scratch)};
+  if (ordered_row_finish<1>(v, partial + (int64_t)c * parts, (int)blockIdx.y, parts, tickets + c, scratch)) {
+    const float value = v[0] * (scale ? scale[c] : 1.f);
     out[c] = accumulate ? out[c] + value : value;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -463,14 +436,11 @@ int srgan_chan_reduce(const float* a, const float* b, const float* mean, const f
   while (seg < seg_cap && (int64_t)N * C * ((HW + 2 * seg - 1) / (2 * seg)) >= min_wgs) seg *= 2;
   const int segs = (int)((HW + seg - 1) / seg);
   SRGAN_REQUIRE((int64_t)N * segs <= 65535, SRGAN_ERANGE, "srgan_chan_reduce grid");
-  const int ticket_set = C <= ROW_TICKETS ? workspace_index(s) : -1;
-  if (ticket_set >= 0 && ticket_set < TICKET_SETS) {
-    float* partial = partial_workspace((size_t)C * N * segs * sizeof(float), s);
-    if (partial) {
-      hipLaunchKernelGGL(chan_reduce_rows_ordered_kernel, dim3(C, N * segs), dim3(256), 0, s, a, b, mean, scale, out, partial,
-                         ticket_set, C, HW, segs, seg, accumulate);
-      return launch_status();
-    }
+  unsigned int* tickets = nullptr;
+  if (float* partial = row_finish_workspace(C, N * segs, 1, g_reduce_finish_tickets, s, &tickets)) {
+    hipLaunchKernelGGL(chan_reduce_rows_ordered_kernel, dim3(C, N * segs), dim3(256), 0, s, a, b, mean, scale, out, partial,
+                       tickets, C, HW, segs, seg, accumulate);
+    return launch_status();
   }
   if (!accumulate) if (const int status = zero_floats(out, C, s)) return status;
   hipLaunchKernelGGL(chan_reduce_rows_kernel, dim3(C, N * segs), dim3(256), 0, s, a, b, mean, scale, out, C, HW,

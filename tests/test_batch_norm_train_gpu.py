@@ -17,9 +17,10 @@ RTOL = 1e-3
 MOMENTUM, EPS = 0.1, 1e-5
 
 # (N, C, H, W): odd plane (scalar tail); M = 6 in one channel; N = 1; a plain float4 case; two shapes where several
-# workgroups share a channel (the ordered combine); and data far from zero (offset 1000), where E[x^2] - E[x]^2 in fp32
+# workgroups share a channel (the ordered combine); 300 workgroups of one image per channel -- and per channel group of the
+# blocked twin -- so that the finishing loop of the last one wraps (parts t and t + 256); and data far from zero (offset 1000), where E[x^2] - E[x]^2 in fp32
 # loses the variance (14 % off) while sums of deviations do not.
-SHAPES = [(4, 5, 3, 5), (3, 1, 1, 2), (1, 4, 64, 64), (2, 3, 32, 32), (16, 64, 8, 8), (8, 8, 64, 64)]
+SHAPES = [(4, 5, 3, 5), (3, 1, 1, 2), (1, 4, 64, 64), (2, 3, 32, 32), (16, 64, 8, 8), (8, 8, 64, 64), (300, 5, 1, 2)]
 CASES = [(shape, 0.0) for shape in SHAPES] + [((4, 5, 6, 7), 1000.0)]
 SLOPES = [1.0, 0.05]
 
@@ -92,6 +93,12 @@ def abi_backward(g, x, stats, gamma, beta, slope, gamma_grad=None, beta_grad=Non
     return gx, sums
 
 
+def poison_workspace():
+    """NaN in the stream's workspace: a partial that the last workgroup of a row reads before it was written shows."""
+    from srgan_amd import _lib
+    _lib._workspaces[(torch.cuda.current_device(), _lib.stream_handle())].fill_(float('nan'))
+
+
 def on_device(case):
     return {key: value.clone().cuda() for key, value in inputs(case).items()}
 
@@ -110,6 +117,7 @@ def test_forward_statistics_and_running_buffers(case, slope):
     want, d = reference(case, slope), on_device(case)
     tracked = torch.zeros((), dtype=torch.int64, device='cuda')
     for call in (1, 2, 3):
+        poison_workspace()
         y, stats = abi_forward(d['x'], d['gamma'], d['beta'], d['running_mean'], d['running_var'], tracked, slope)
         if call in (1, 3):
             for name in ('running_mean', 'running_var'):

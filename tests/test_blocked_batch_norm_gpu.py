@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from helpers import assert_close_norm
-from test_batch_norm_train_gpu import CASES, EPS, MOMENTUM, _ids, inputs
+from test_batch_norm_train_gpu import CASES, EPS, MOMENTUM, _ids, inputs, poison_workspace
 
 pytestmark = pytest.mark.gpu
 CODES = [0, 1, 2]
@@ -247,6 +247,7 @@ def test_statistics_forward_and_backward_against_fp64(code, case):
     tracked = torch.zeros((), dtype=torch.int64, device='cuda')
     label = f'code {code} {_ids(case)}'
     for call in (1, 2, 3):
+        poison_workspace()
         stats = abi_stats(xb, shape, code, d['running_mean'], d['running_var'], tracked)
         if call in (1, 3):
             for name in ('running_mean', 'running_var'):
