@@ -69,6 +69,9 @@ const char* srgan_last_error(void);
                                              tensors from a counter-based generator on the device) */
 #define SRGAN_FEATURE_IMAGE_SUMMARIES 0x800u /* ABI 1.1, additive: srgan_image_grid / srgan_density_heatmaps (a summary step's
                                                image grids and crowd map heatmaps built on the device) */
+#define SRGAN_FEATURE_DISTRIBUTION_SUMMARIES 0x1000u /* ABI 1.1, additive: srgan_wasserstein_1d / srgan_kde_curves /
+                                                        srgan_curve_frame (the coefficient application's distribution summaries
+                                                        built on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -479,6 +482,56 @@ int srgan_image_grid(const float* images, int32_t N, int32_t C, int32_t H, int32
  * max_tensor_elements or more than 65535 tiles: SRGAN_ERANGE. */
 int srgan_density_heatmaps(const float* labels, const float* predicted, int32_t B, int32_t M, int32_t h, int32_t w, int32_t P,
                            const float* lut, int32_t lut_entries, float* tiles, int64_t tile_stride, float* ranges, void* stream);
+
+/* ---- distribution summaries on the device (SRGAN_FEATURE_DISTRIBUTION_SUMMARIES) ----------------------------------------------
+ * What the reference's coefficient application logs at a summary step beside its error scalars (coefficient/srgan.py:56-78,
+ * coefficient/presentation.py:19-55): the 1-D Wasserstein distance between two sets of predictions and a frame of kernel-density
+ * curves, which it computes on the host with scipy / seaborn / matplotlib after downloading every prediction.  All pointers are
+ * device pointers; no call synchronises or reads anything back; no fp32 atomics; every sum that lanes or workgroups share is
+ * finished in a fixed order, so a call repeats its bits; every output element is written exactly once, whatever it held before.
+ * Inputs are finite (a NaN or an infinity in `u`, `v`, `samples` or `vertices` gives an unspecified, but in-bounds, result).
+ *
+ * srgan_wasserstein_1d: scipy.stats.wasserstein_distance(u, v) of unweighted samples u [n], v [m]; one float to `out`.  One
+ * workgroup sorts the N = n + m values, each tagged with its origin, in LDS (a bitonic network over the next power of two,
+ * padded with +inf), counts the values of u up to each sorted position (cu; cv = position + 1 - cu), and sums over the N - 1
+ * gaps |cu * m - cv * n| * (x[k + 1] - x[k]) -- the CDF difference in integers, so equal values and their order cannot change
+ * the result: their gap is 0 -- each thread over a contiguous run of gaps in order, the threads in a halving tree; then one
+ * division by n * m.  SRGAN_WASSERSTEIN_MAX_VALUES is the largest power of two whose keys (4 bytes) and tags (1 byte) fit the
+ * 160 KiB of LDS a workgroup may take together with the 8 KiB of scan and reduction scratch: 16384 values = 64 KiB + 16 KiB
+ * (32768 values would fill the 160 KiB with keys and tags alone).  A NULL pointer, n < 1 or m < 1: SRGAN_EINVAL;
+ * n + m > SRGAN_WASSERSTEIN_MAX_VALUES: SRGAN_EUNSUPPORTED. */
+#define SRGAN_WASSERSTEIN_MAX_VALUES 16384
+int srgan_wasserstein_1d(const float* u, int32_t n, const float* v, int32_t m, float* out, void* stream);
+/* srgan_kde_curves: C Gaussian kernel-density curves, each as seaborn's kdeplot(data, bw=factor, cut=cut, gridsize=G) draws it
+ * without statsmodels: scipy.stats.gaussian_kde(data, bw_method=factor) on linspace(min - cut * h, max + cut * h, G), h = factor *
+ * std(data, ddof=1).  samples: the curves' values back to back, curve c = samples[offsets[c] .. offsets[c + 1]) (offsets: C + 1
+ * int32, non-decreasing, offsets[0] >= 0); support, density [C, G]; stats [C, 4] = (count, min, max, h).  First launch, one
+ * workgroup per curve: min, max and (count, mean, M2) in a fixed tree (Chan's merge), h = factor * sqrt(M2 / (count - 1)).
+ * Second launch, one thread per (c, g): lo = min - cut * h, support[c, g] = lo + g * ((max + cut * h - lo) / (G - 1)) with every
+ * operation rounded to fp32 on its own; density[c, g] = (sum_i exp(-0.5 * ((support[c, g] - x_i) * (1 / h))^2)) * (1 / (count * h *
+ * sqrt(2 pi))), the samples staged through LDS and added in stored order.  A curve with fewer than 2 samples, or whose h is 0 or
+ * not finite, is invalid: stats[c, 3] = 0 and its support and density rows are zeros, never NaN (min = max = 0 for an empty
+ * curve).  A NULL pointer, C < 1, G < 2, factor <= 0 or cut < 0 (or either not finite): SRGAN_EINVAL; C * G above
+ * max_tensor_elements or C > 65535: SRGAN_ERANGE.  The length of `samples` is on the device only: offsets[C] <=
+ * max_tensor_elements is the caller's to keep. */
+int srgan_kde_curves(const float* samples, const int32_t* offsets, int32_t C, int32_t G, float factor, float cut, float* support,
+                     float* density, float* stats, void* stream);
+/* srgan_curve_frame: a line chart out [3, H, W], planar RGB in [0, 1], one thread per pixel (a gather).  Data coordinates map to
+ * pixel coordinates by px = (x - x_lo) / (x_hi - x_lo) * W - 0.5, py = (y_hi - y) / (y_hi - y_lo) * H - 0.5; pixel (row r, column
+ * c) has its centre at (px, py) = (c, r).  The colour starts as background[3]; then the grid: one vertical line per x_ticks[n_x]
+ * and one horizontal line per y_ticks[n_y] (data coordinates, device arrays; n_x / n_y may be 0, the array then NULL), one pixel
+ * wide, in grid_colour[3]; then the C polylines in order, polyline k = vertices[offsets[k] .. offsets[k + 1]) (vertices [total, 2]
+ * = (x, y) in data coordinates, offsets C + 1 int32) in colours[k, 0..2] at widths[k] pixels; fewer than 2 vertices: skipped.
+ * Each line is composited as colour = colour * (1 - a) + line colour * a with the coverage a = clamp(0.5 + width / 2 - d, 0, 1),
+ * d = the distance in pixels from the pixel's centre to the line (for a polyline the smallest over its segments, each taken in
+ * coordinates relative to the segment's first vertex; a segment of length 0 is a point).  So a width <= -1 draws nothing.
+ * Nothing outside the frame is special-cased: a curve above y_hi simply leaves it.  C may be 0 (vertices, offsets, colours,
+ * widths then unused).  A NULL required pointer, H or W < 1, C, n_x or n_y < 0, a non-finite bound, x_hi <= x_lo or
+ * y_hi <= y_lo: SRGAN_EINVAL; 3 * H * W above max_tensor_elements: SRGAN_ERANGE. */
+int srgan_curve_frame(const float* vertices, const int32_t* offsets, int32_t C, const float* colours, const float* widths,
+                      int32_t H, int32_t W, float x_lo, float x_hi, float y_lo, float y_hi, const float* background,
+                      const float* grid_colour, const float* x_ticks, int32_t n_x, const float* y_ticks, int32_t n_y, float* out,
+                      void* stream);
 
 /* Offline ikNN label of a crowd scene (reference crowd/database_preprocessor.py:93-101,266-290: generate_knn_map +
  * 1 / (map + epsilon)): out[y, x] = 1 / (mean over the k nearest heads of the Euclidean distance from (y, x), each

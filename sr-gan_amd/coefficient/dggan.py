@@ -52,13 +52,8 @@ class CoefficientDgganExperiment(CoefficientExperiment):
             _, scores = self.D(fake_examples)
         return bce_with_logits(scores, 0.0, self.batch_mean_of_examples)
 
-    def validation_summaries(self, step):
-        """MAE / MSE of the value heads (the distribution plots of the reference are out of scope)."""
-        dnn_validation = None
-        for network, writer in ((self.DNN, self.dnn_summary_writer), (self.D, self.gan_summary_writer)):
-            value_head = lambda examples, network=network: network(examples)[0]
-            for dataset, name in ((self.train_dataset, '2 Train Error'), (self.validation_dataset, '1 Validation Error')):
-                values = self.evaluation_epoch(value_head, dataset, writer, name,
-                                               dnn_validation if (network is self.D and name.startswith('1')) else None)
-                if network is self.DNN and name.startswith('1'):
-                    dnn_validation = values
+    def predicted_values(self, network, examples):
+        """The value heads: ``validation_summaries`` is the coefficient application's -- MAE / MSE of the value heads and, with
+        ``settings.distribution_summaries``, the Wasserstein scalar and the ``Distributions`` frame (reference
+        coefficient/dggan.py:66-117)."""
+        return network(examples)[0]

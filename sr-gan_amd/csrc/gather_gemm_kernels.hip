@@ -1414,7 +1414,8 @@ int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
   out->features = SRGAN_FEATURE_FUSED_BNRELU | SRGAN_FEATURE_SPLITK_WORKSPACE | SRGAN_FEATURE_LIVE_PROFILE |
                   SRGAN_FEATURE_BLOCKED16 | SRGAN_FEATURE_BATCHED_SHADOWS | SRGAN_FEATURE_CROWD_FULL_IMAGE |
                   SRGAN_FEATURE_IMAGE_BATCHES | SRGAN_FEATURE_BATCH_NORM_TRAIN | SRGAN_FEATURE_BLOCKED_BATCH_NORM |
-                  SRGAN_FEATURE_BLOCKED_FROZEN_NORM | SRGAN_FEATURE_DEVICE_DRAWS | SRGAN_FEATURE_IMAGE_SUMMARIES;
+                  SRGAN_FEATURE_BLOCKED_FROZEN_NORM | SRGAN_FEATURE_DEVICE_DRAWS | SRGAN_FEATURE_IMAGE_SUMMARIES |
+                  SRGAN_FEATURE_DISTRIBUTION_SUMMARIES;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;

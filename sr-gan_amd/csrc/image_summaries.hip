@@ -47,21 +47,6 @@ __global__ __launch_bounds__(256) void image_grid_kernel(const float* __restrict
   }
 }
 
-// Largest and smallest value across the workgroup's 256 threads (valid in every thread): the wave's butterfly, then the four
-// waves through LDS.  min / max are order-independent: any tree gives the same bits.
-__device__ __forceinline__ void block_min_max_256(float& lo, float& hi, float (*scratch)[4]) {
-#pragma unroll
-  for (int offset = 32; offset > 0; offset >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, offset, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, offset, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { scratch[0][wave] = lo; scratch[1][wave] = hi; }
-  __syncthreads();
-  lo = fminf(fminf(scratch[0][0], scratch[0][1]), fminf(scratch[0][2], scratch[0][3]));
-  hi = fmaxf(fmaxf(scratch[1][0], scratch[1][1]), fmaxf(scratch[1][2], scratch[1][3]));
-}
-
 // ranges[b, m] = {min, max} over labels[b] and predicted[b, m] together: workgroup b * M + m.
 __global__ __launch_bounds__(256) void density_ranges_kernel(const float* __restrict__ labels, const float* __restrict__ predicted,
                                                              int M, int pixels, float* __restrict__ ranges) {

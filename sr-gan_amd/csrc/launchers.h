@@ -113,4 +113,13 @@ int density_heatmaps_run(const float* labels, const float* predicted, int32_t B,
                          const float* lut, int32_t lut_entries, float* tiles, int64_t tile_stride, float* ranges,
                          hipStream_t stream);
 
+// distribution_summaries.hip: the Wasserstein distance, the kernel-density curves and the line chart of a coefficient summary
+// step (contracts: srgan_wasserstein_1d, srgan_kde_curves, srgan_curve_frame; arguments already checked).
+int wasserstein_run(const float* u, int32_t n, const float* v, int32_t m, float* out, hipStream_t stream);
+int kde_curves_run(const float* samples, const int32_t* offsets, int32_t C, int32_t G, float factor, float cut, float* support,
+                   float* density, float* stats, hipStream_t stream);
+int curve_frame_run(const float* vertices, const int32_t* offsets, int32_t C, const float* colours, const float* widths, int32_t H,
+                    int32_t W, float x_lo, float x_hi, float y_lo, float y_hi, const float* background, const float* grid_colour,
+                    const float* x_ticks, int32_t n_x, const float* y_ticks, int32_t n_y, float* out, hipStream_t stream);
+
 }  // namespace srgan
