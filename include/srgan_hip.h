@@ -72,6 +72,9 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_DISTRIBUTION_SUMMARIES 0x1000u /* ABI 1.1, additive: srgan_wasserstein_1d / srgan_kde_curves /
                                                         srgan_curve_frame (the coefficient application's distribution summaries
                                                         built on the device) */
+#define SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE 0x2000u /* ABI 1.1, additive: srgan_conv3x3_image_floats / srgan_h_pack_conv3x3_image /
+                                                      srgan_h_pack_job_conv3x3_image and the *_image forms of the fused fp32 3x3
+                                                      calls (weights staged from a per-step packed image) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -185,6 +188,23 @@ int srgan_conv2d_bwd_data_bnrelu_partials(const srgan_conv_desc* desc, const flo
                                           const float* x, float* gx, float* partials, int accumulate, void* stream);
 int srgan_bn_partial_reduce_batched(const srgan_bn_reduce_job* jobs_device, int32_t count, int32_t max_channels, int32_t max_tiles,
                                     const float* scratch, void* stream);
+/* The 3x3 / stride 1 / padding 1 cases of the three calls above with the operand's WEIGHT IMAGE next to w
+ * (SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE): fp32, 16-byte aligned, srgan_conv3x3_image_floats(CI, CO) floats,
+ *   image[(ci * 9 + tap) * CO_pad + o], CO_pad = CO rounded up to 64, ci up to CI rounded up to 8, zeros where o >= CO or ci >= CI,
+ * with (CO, CI, tap) = (K, C, kh * 3 + kw) of w[K][C][3][3] for the forward ("forward" image) and (C, K, mirrored tap) for the
+ * data gradient ("transposed" image): the elements the kernel otherwise gathers from w in every workgroup.  The image must hold
+ * the current w (srgan_h_pack_conv3x3_image, or its job in srgan_h_pack_batched behind the optimizer update).  Same plans, tiles
+ * and splits as the calls above and BIT-IDENTICAL results; other geometries: SRGAN_EUNSUPPORTED.  SRGAN_NO_CONV3_IMAGE=1 in the
+ * environment (read once per process) makes them ignore the image. */
+int64_t srgan_conv3x3_image_floats(int32_t CI, int32_t CO);
+int srgan_conv2d_fwd_bnrelu_image(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
+                                  const float* image, const float* bias, float* y, void* stream);
+int srgan_conv2d_bwd_data_bnrelu_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
+                                       const srgan_bn_relu* bn, const float* x, float* gx, float* g_gamma, float* g_beta,
+                                       int accumulate, void* stream);
+int srgan_conv2d_bwd_data_bnrelu_partials_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
+                                                const srgan_bn_relu* bn, const float* x, float* gx, float* partials,
+                                                int accumulate, void* stream);
 
 /* Grouped form of srgan_conv2d_bwd_weight_bnrelu: MANY independent weight gradients (all the 1x1, or all the 3x3,
  * convolutions of a dense block's backward: reference crowd/models.py:335-353 through loss.backward()) in ONE launch.
@@ -663,6 +683,12 @@ int64_t srgan_h_pack_job_matrix(void* jobs, int64_t first_block, const float* sr
                                 int64_t rows_real, int64_t cols_real, int64_t row_stride, int64_t col_stride, int32_t row_plane,
                                 int32_t col_plane, int dtype);
 int64_t srgan_h_pack_job_bias_rows(void* jobs, int64_t first_block, const float* bias, float* rows, int32_t channels, int32_t plane);
+/* The fp32 weight images of a 3x3 convolution w[K][C][3][3] (SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE; layout above): transposed 0
+ * writes the forward image (srgan_conv3x3_image_floats(C, K) floats), 1 the data gradient's (srgan_conv3x3_image_floats(K, C)),
+ * padding zeros included; `image` 16-byte aligned.  The job form is one more job kind of srgan_h_pack_batched. */
+int srgan_h_pack_conv3x3_image(const float* w, float* image, int32_t K, int32_t C, int transposed, void* stream);
+int64_t srgan_h_pack_job_conv3x3_image(void* jobs, int64_t first_block, const float* w, float* image, int32_t K, int32_t C,
+                                       int transposed);
 int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks, void* stream);
 int srgan_h_conv4x4s2(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
                       int32_t N, int32_t C_in, int32_t rows, int32_t H, int32_t W, int dtype, void* stream);
@@ -734,7 +760,8 @@ int srgan_profile_bytes(double* algorithmic_bytes_total);
 int srgan_profile_mixed(double* flops, double* kernel_ms);
 /* Per-shape text report of the last profiled region ("M N K kind bm bn split akf bkf count ms bytes" per line; kind:
  * 0 gg_direct, 1 gg_mfma, 2 conv3x3_lds, 3 pointwise, 4 conv3x3_wgrad, 5 gg_rows, 6 pointwise_wgrad,
- * 8 pointwise_ksplit, 9 gg_dot, 10 stem7x7_fwd, 11 stem7x7_wgrad); returns the bytes needed. */
+ * 8 pointwise_ksplit, 9 gg_dot, 10 stem7x7_fwd, 11 stem7x7_wgrad; for kind 2, akf = 1 marks a launch that staged its weights
+ * from the weight image); returns the bytes needed. */
 int64_t srgan_profile_report(char* buffer, int64_t capacity);
 
 #ifdef __cplusplus

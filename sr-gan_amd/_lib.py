@@ -50,6 +50,12 @@ SIGNATURES = {
     'srgan_conv2d_bwd_data_bnrelu_tiles': ([ctypes.POINTER(ConvDesc)], ctypes.c_int64),
     'srgan_conv2d_bwd_data_bnrelu_partials': ([ctypes.POINTER(ConvDesc), vp, vp, ctypes.POINTER(BnRelu), vp, vp, vp,
                                                ctypes.c_int, vp], ctypes.c_int),
+    'srgan_conv3x3_image_floats': ([i32, i32], ctypes.c_int64),
+    'srgan_conv2d_fwd_bnrelu_image': ([ctypes.POINTER(ConvDesc), vp, ctypes.POINTER(BnRelu), vp, vp, vp, vp, vp], ctypes.c_int),
+    'srgan_conv2d_bwd_data_bnrelu_image': ([ctypes.POINTER(ConvDesc), vp, vp, vp, ctypes.POINTER(BnRelu), vp, vp, vp, vp,
+                                            ctypes.c_int, vp], ctypes.c_int),
+    'srgan_conv2d_bwd_data_bnrelu_partials_image': ([ctypes.POINTER(ConvDesc), vp, vp, vp, ctypes.POINTER(BnRelu), vp, vp, vp,
+                                                     ctypes.c_int, vp], ctypes.c_int),
     'srgan_bn_partial_reduce_batched': ([vp, i32, i32, i32, vp, vp], ctypes.c_int),
     'srgan_conv2d_bwd_weight_bnrelu': ([ctypes.POINTER(ConvDesc), vp, ctypes.POINTER(BnRelu), vp, vp, ctypes.c_int, vp],
                                        ctypes.c_int),
@@ -144,6 +150,8 @@ SIGNATURES = {
     'srgan_h_pack_job_k4s2_weights': ([vp, i64, vp, vp, i32, i32, ctypes.c_int, ctypes.c_int, vp], ctypes.c_int64),
     'srgan_h_pack_job_matrix': ([vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32, ctypes.c_int], ctypes.c_int64),
     'srgan_h_pack_job_bias_rows': ([vp, i64, vp, vp, i32, i32], ctypes.c_int64),
+    'srgan_h_pack_conv3x3_image': ([vp, vp, i32, i32, ctypes.c_int, vp], ctypes.c_int),
+    'srgan_h_pack_job_conv3x3_image': ([vp, i64, vp, vp, i32, i32, ctypes.c_int], ctypes.c_int64),
     'srgan_h_pack_batched': ([vp, i32, i64, vp], ctypes.c_int),
     'srgan_h_conv4x4s2': ([vp, vp, vp, vp, f32, ctypes.c_int, vp, i32, i32, i32, i32, i32, ctypes.c_int, vp], ctypes.c_int),
     'srgan_h_conv_transpose4x4s2': ([vp, vp, vp, vp, f32, ctypes.c_int, vp, i32, i32, i32, i32, i32, ctypes.c_int, vp], ctypes.c_int),

@@ -312,6 +312,25 @@ class Conv3x3Shadow(Shadow):
               xm.h, xm.w, xm.code, F._stream())
 
 
+class Conv3x3ImageShadow(Shadow):
+    """A 3x3 / stride 1 / padding 1 ``nn.Conv2d`` of the fp32 NCHW family (the dense layers' ``conv2``), weights [K][C][3][3]: the
+    fp32 WEIGHT IMAGES ``srgan_conv2d_*_bnrelu_image`` stage from (include/srgan_hip.h; ``code`` is 0) -- ``forward`` for the
+    convolution, ``transposed`` for its data gradient.  No rounding: the images hold the masters' own bits in the kernel's
+    staging order, so the calls that read them are bit-identical to the ones that gather from the masters.  The layer's launches
+    live in ``fused.dense_block``; the weight gradient does not read the weights."""
+    kind = 'conv3x3_image'
+
+    def _measure(self):
+        self.k, self.c, r, s = self.module.weight.shape
+        if (r, s) != (3, 3):
+            raise ValueError('blocked16: a weight image is the operand of a 3x3 convolution')
+
+    def forms(self):
+        floats = _lib.library().srgan_conv3x3_image_floats
+        for name, transposed, rows, reduced in (('forward', 0, self.k, self.c), ('transposed', 1, self.c, self.k)):
+            yield Form(name, floats(reduced, rows) // 4, self.module.weight, 'conv3x3_image', (self.k, self.c, transposed), torch.float32)
+
+
 class K4s2Shadow(Shadow):
     """The 4x4 / stride 2 / padding 1 family, weights [A][B][4][4] with A = the channels on the small plane: conv2d weights
     [K][C], conv_transpose2d weights [Cin][Cout].  ``down`` is the operand big -> small plane, ``up`` small -> big."""
@@ -442,7 +461,7 @@ class SeedShadow(Shadow):
               self.features, self.c_in, 1, self.features, self.plane, 1, xm.code, F._stream())
 
 
-SHADOW_KINDS = {cls.kind: cls for cls in (Conv3x3Shadow, K4s2Shadow, LinearShadow, SeedShadow)}
+SHADOW_KINDS = {cls.kind: cls for cls in (Conv3x3Shadow, Conv3x3ImageShadow, K4s2Shadow, LinearShadow, SeedShadow)}
 # the shadow kinds of the batched refresh: all of them (the matrix shadows and the seed layer's bias rows since ABI 1.1's
 # SRGAN_FEATURE_BATCHED_SHADOWS)
 BATCHED_KINDS = tuple(SHADOW_KINDS)

@@ -164,6 +164,24 @@ __device__ __forceinline__ void h_pack_conv_weights_slot(const float* __restrict
   packed[slot] = h_pack8<PREC>(v);
 }
 
+// The fp32 weight image of a 3x3 convolution, the operand of conv3x3_lds_kernel's WIMG forms (conv3x3.hip):
+//   img[(ci * 9 + tap) * CO_pad + o] = element (o, ci, tap / 3, tap % 3) at w[base + o * so + ci * si + kh * skh + kw * skw]
+// with CO_pad = CO rounded up to 64 and ci running to CI rounded up to 8; rows o >= CO and channels ci >= CI are zeros, so a
+// chunk's slice is read without a predicate.  One thread = one element (consecutive o: coalesced stores).
+__host__ __device__ __forceinline__ int32_t conv3x3_image_co_pad(int32_t CO) { return (CO + 63) & ~63; }
+__host__ __device__ __forceinline__ int64_t conv3x3_image_floats(int32_t CI, int32_t CO) {
+  return (int64_t)((CI + 7) & ~7) * 9 * conv3x3_image_co_pad(CO);
+}
+__device__ __forceinline__ void conv3x3_image_element(const float* __restrict__ w, float* __restrict__ image, int64_t element,
+                                                      int32_t CO, int32_t CI, int32_t base, int32_t so, int32_t si, int32_t skh,
+                                                      int32_t skw) {
+  const int co_pad = conv3x3_image_co_pad(CO);
+  const int o = (int)(element % co_pad), row = (int)(element / co_pad);
+  const int ci = row / 9, tap = row - ci * 9;
+  const int kh = tap / 3, kw = tap - kh * 3;
+  image[element] = (o < CO && ci < CI) ? w[base + o * so + ci * si + kh * skh + kw * skw] : 0.f;
+}
+
 // 4x4 / stride 2 weights as 2x2-tap operands (mode 0: "down", 1 .. 4: the "up" parity classes; layout in blocked16_k4s2.hip)
 template <int PREC>
 __device__ __forceinline__ void h_pack_k4s2_weights_slot(const float* __restrict__ w, Slot* __restrict__ packed, int64_t slot,
@@ -266,7 +284,8 @@ struct HPackJob {
   const float* w; Slot* packed;     // kind 4: packed = the fp32 bias rows
   int64_t slots, first_block;       // this job's workgroups are [first_block, first_block + ceil(slots / 256))
   int32_t kind, prec;               // kind 0: conv weights, 1: 4x4 / stride 2 weights, 2: matrix, 3: transposed matrix (one
-                                    // 64 x 64 tile per workgroup, slots = 256 x tiles), 4: bias rows; prec = dtype
+                                    // 64 x 64 tile per workgroup, slots = 256 x tiles), 4: bias rows, 5: fp32 3x3 weight image
+                                    // (slots = its floats, packed = the image); prec = dtype
   int32_t p[10];                    // the body's integer arguments, in its order
 };
 

@@ -241,6 +241,14 @@ __global__ __launch_bounds__(256) void h_pack_conv_weights_kernel(const float* _
   h_pack_conv_weights_slot<PREC>(w, packed, slot, CO, CI, R, S, base, so, si, skh, skw);
 }
 
+__global__ __launch_bounds__(256) void conv3x3_image_kernel(const float* __restrict__ w, float* __restrict__ image, int64_t floats,
+                                                            int32_t CO, int32_t CI, int32_t base, int32_t so, int32_t si,
+                                                            int32_t skh, int32_t skw) {
+  const int64_t element = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (element >= floats) return;
+  conv3x3_image_element(w, image, element, CO, CI, base, so, si, skh, skw);
+}
+
 // Every weight shadow of one network in ONE launch: a workgroup finds its job by bisection over the jobs' first blocks
 // (wave-uniform), then runs that job's body.  A step of the driving configuration re-rounds 80 operands, of the VGG
 // configuration 52: as single launches they were 0.45 / 0.34 ms of 5 us kernels with the launch gaps on top.  The matrix shadows
@@ -273,8 +281,10 @@ __global__ __launch_bounds__(256) void h_pack_batched_kernel(const HPackJob* __r
     const int tile_index = (int)(block - job.first_block);
     if (job.prec == 1) h_pack_matrix_tile<1>(job.w, job.packed, tile, tile_index, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
     else h_pack_matrix_tile<2>(job.w, job.packed, tile, tile_index, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
-  } else {
+  } else if (job.kind == 4) {
     h_bias_rows_slot(job.w, reinterpret_cast<float*>(job.packed), slot, q[0], q[1]);
+  } else {
+    conv3x3_image_element(job.w, reinterpret_cast<float*>(job.packed), slot, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
   }
 }
 
@@ -978,6 +988,20 @@ static void conv_weights_job(HPackJob& job, const float* w, void* packed, int32_
   job.p[7] = transposed ? -S : S; job.p[8] = transposed ? -1 : 1;
 }
 
+// the job of one weight image of conv2d weights w[K][C][3][3]; transposed: the data gradient's operand (rows = C, reduced = K,
+// taps mirrored) -- the strides conv3x3_run is called with for that direction
+static void conv3x3_image_job(HPackJob& job, const float* w, float* image, int32_t K, int32_t C, int transposed) {
+  memset(&job, 0, sizeof(job));
+  const int rows = transposed ? C : K, reduced = transposed ? K : C;
+  job.w = w; job.packed = (Slot*)image; job.kind = 5; job.prec = 0;
+  job.slots = conv3x3_image_floats(reduced, rows);
+  job.p[0] = rows; job.p[1] = reduced;
+  job.p[2] = transposed ? 8 : 0;                            // base
+  job.p[3] = transposed ? 9 : C * 9;                        // row stride
+  job.p[4] = transposed ? C * 9 : 9;                        // reduced-channel stride
+  job.p[5] = transposed ? -3 : 3; job.p[6] = transposed ? -1 : 1;
+}
+
 }  // namespace srgan
 
 using namespace srgan;
@@ -1186,6 +1210,35 @@ int64_t srgan_h_pack_job_bias_rows(void* jobs, int64_t first_block, const float*
   job.w = bias; job.packed = (Slot*)rows; job.first_block = first_block; job.kind = 4; job.prec = 0;
   job.slots = (int64_t)(channels + 7) / 8 * plane;
   job.p[0] = channels; job.p[1] = plane;
+  memcpy(jobs, &job, sizeof(job));
+  return (job.slots + 255) / 256;
+}
+
+// ---- the fp32 weight image of a 3x3 convolution (layout: conv3x3_image_element, blocked16.h)
+int64_t srgan_conv3x3_image_floats(int32_t CI, int32_t CO) {
+  return (CI > 0 && CO > 0) ? conv3x3_image_floats(CI, CO) : 0;
+}
+
+// transposed = 0: the forward operand of conv2d weights w[K][C][3][3] (CO = K, CI = C); 1: the data gradient's (CO = C, CI = K)
+int srgan_h_pack_conv3x3_image(const float* w, float* image, int32_t K, int32_t C, int transposed, void* stream) {
+  SRGAN_REQUIRE(w && image && K > 0 && C > 0 && (transposed == 0 || transposed == 1) && (((uintptr_t)image) & 15) == 0 &&
+                (int64_t)K * C * 9 < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_pack_conv3x3_image arguments");
+  HPackJob job;
+  conv3x3_image_job(job, w, image, K, C, transposed);
+  const int32_t* q = job.p;
+  hipLaunchKernelGGL(conv3x3_image_kernel, dim3((unsigned)((job.slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, image,
+                     job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+  return launch_status();
+}
+
+int64_t srgan_h_pack_job_conv3x3_image(void* jobs, int64_t first_block, const float* w, float* image, int32_t K, int32_t C,
+                                       int transposed) {
+  SRGAN_REQUIRE(jobs && first_block >= 0 && w && image && K > 0 && C > 0 && (transposed == 0 || transposed == 1) &&
+                (((uintptr_t)image) & 15) == 0 && (int64_t)K * C * 9 < ((int64_t)1 << 31), SRGAN_EINVAL,
+                "srgan_h_pack_job_conv3x3_image arguments");
+  HPackJob job;
+  conv3x3_image_job(job, w, image, K, C, transposed);
+  job.first_block = first_block;
   memcpy(jobs, &job, sizeof(job));
   return (job.slots + 255) / 256;
 }

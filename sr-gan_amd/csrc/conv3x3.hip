@@ -15,6 +15,7 @@
 // Roofline: fp32 MFMA (157.3 TF/s); algorithmic work 2 * 9 * CI * CO FLOP per output pixel.
 #include "common.h"
 #include "launchers.h"
+#include "lds_dma.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -44,7 +45,8 @@ struct Conv3Params {
   // OUTPUT channels, see BnBackwardEpilogue); epi_partial[q][workgroup tile][CO] receives the parameter-gradient sums
   const float* epi_x; int64_t epi_x_bs;
   float* epi_partial; int32_t epi_tiles;
-  const void* w_packed;   // mixed precision: the weights repacked by conv3x3_pack_weights_kernel (16-byte operand slots)
+  const void* w_packed;   // mixed precision: the weights repacked by conv3x3_pack_weights_kernel (16-byte operand slots);
+                          // fp32 (WIMG kernels): the layer's weight image img[(ci * 9 + tap) * CO_pad + o] (blocked16.h)
   // Output placement: element (o, y, x) of the H x W grid the kernel walks goes to out[o * out_plane + y * out_sy +
   // x * out_sx + out_off] (a plain convolution: H * W, W, 1, 0; a stride-2 class of a transposed convolution writes every
   // other pixel of a 2H x 2W plane) and `taps` is the 9-bit mask of the window positions (kh * 3 + kw) that exist.
@@ -70,24 +72,36 @@ __device__ unsigned int g_conv3_split_tickets[SPLIT_TICKET_SETS * SPLIT_TICKET_T
 // two parameter-gradient row sums (store mode only, no split over input channels).
 // TAPS: compile-time mask of the window positions the inner loop multiplies (0x1FF = the full 3x3 window; the four
 // stride-2 classes of a k4 / s2 / p1 transposed convolution are 2x2 sub-windows: 0x01B, 0x036, 0x0D8, 0x1B0).
-template <int BM, int TH, int CI_T, bool PRO, int TW, bool EPI = false, int TAPS = 0x1FF>
+// WIMG: the weights come from the layer's weight image (p.w_packed, packed once per optimizer step: conv3x3_image_element,
+// blocked16.h) instead of being gathered, transposed and zero-padded from p.w in every workgroup.  A chunk's slice of the image
+// is CI_T * 9 runs of BM contiguous floats, rows and channels that do not exist are zeros IN the image, so each wave moves its
+// share with two or three global_load_lds_dwordx4 (no register, no predicate, no LDS write instruction) into one of TWO weight
+// stages: the next chunk's slice lands during this chunk's MFMAs.  The LDS rows are BM floats, unpadded: the fragment reads are
+// ds_read_b32 of 32 consecutive floats per half-wave, conflict-free at any row pitch (the BM + 1 pitch of the gathered form
+// serves its transposing WRITES).  Same values in the same LDS roles and the same MFMA order: bit-identical outputs.
+template <int BM, int TH, int CI_T, bool PRO, int TW, bool EPI = false, int TAPS = 0x1FF, bool WIMG = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p) {
   static_assert(!EPI || !PRO, "the batch-norm backward epilogue pairs with the plain kernel");
   static_assert(TAPS == 0x1FF || (!EPI && !PRO), "tap subsets pair with the plain kernel");
+  static_assert(!WIMG || TAPS == 0x1FF, "the weight image holds the full window");
   constexpr int RPB = 32 / TW;                    // image rows per 32-lane column block
   constexpr int ROWS = TH * RPB;                  // image rows of the workgroup's tile
   constexpr int PH = ROWS + 2, PW = TW + 2, PHPW = PH * PW;
   constexpr int MI = BM / 32, NI = TH / 4;        // each of the 4 waves owns NI column blocks
-  constexpr int LDW = BM + 1;
+  constexpr int LDW = WIMG ? BM : BM + 1;
   constexpr int PATCH = CI_T * PHPW, WTS = CI_T * 9 * BM;
-  constexpr int NP = (PATCH + 255) / 256, NW = (WTS + 255) / 256;
+  constexpr int NP = (PATCH + 255) / 256, NW = WIMG ? 0 : (WTS + 255) / 256;
+  constexpr int WSTAGE = CI_T * 9 * LDW;            // floats of one weight stage (WIMG: two of them)
+  constexpr int WDMA = WTS / 256, WROWS = 256 / BM; // WIMG: wave instructions per chunk, image rows per instruction
   static_assert(CI_T % 2 == 0 && NI >= 1 && MI >= 1, "bad tile");
-  __shared__ float lds[PATCH + CI_T * 9 * LDW];
+  static_assert(!WIMG || (WTS % 256 == 0 && PATCH % 4 == 0 && 256 % BM == 0), "whole 16-byte DMA instructions, aligned stages");
+  __shared__ __attribute__((aligned(16))) float lds[PATCH + (WIMG ? 2 : 1) * WSTAGE];
   __shared__ float2 coef[PRO ? CONV3_PRO_MAX_CI : 1];
   float* patch = lds;
   float* wt = lds + PATCH;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+  const int wave = WIMG ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;      // (WIMG: scalar DMA bases)
   int block = blockIdx.x;
   if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
   const int logical_block = block;
@@ -101,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
   const int HW = p.H * p.W;
 
   // Per-thread staging offsets (relative to the chunk's first channel), computed once.
-  int poff[NP], woff[NW];
+  int poff[NP], woff[NW > 0 ? NW : 1];
 #pragma unroll
   for (int e = 0; e < NP; ++e) {
     const int flat = e * 256 + tid;
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
 
   // Raw loads only in fetch(); validity is applied when the registers are written to LDS (any use of a loaded value
   // before the MFMA loop would make the compiler wait for the loads there instead of overlapping them).
-  float rp[NP], rw[NW];
+  float rp[NP], rw[NW > 0 ? NW : 1];
   auto fetch = [&](int c0) {
     const int room = cend - c0;                         // channels of this chunk that exist
 #pragma unroll
@@ -163,6 +177,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
     }
   };
 
+  // WIMG: chunk c0's slice of the image into weight stage `stage_index`.  Instruction j (wave j % 4) moves the image rows
+  // (c0 * 9 + j * WROWS) .. + WROWS - 1, columns m0 .. m0 + BM - 1, to the stage's floats [j * 256, j * 256 + 256): lane l owns the
+  // four floats at row (4 l) / BM, column (4 l) % BM.  c0 + CI_T <= CI rounded up to 8 and m0 + BM <= CO_pad: inside the image.
+  const int co_pad = (p.CO + 63) & ~63;
+  const uint32_t w_lane = (uint32_t)(((lane * 4) / BM) * co_pad + (lane * 4) % BM) * 4u;
+  const uint32_t w_lds = ring_lds_address(wt);
+  auto dma_weights = [&](int c0, int stage_index) {
+    const float* slice = reinterpret_cast<const float*>(p.w_packed) + (int64_t)c0 * 9 * co_pad + m0;
+#pragma unroll
+    for (int q = 0; q < (WDMA + 3) / 4; ++q) {
+      const int j = wave + 4 * q;
+      if (j >= WDMA) continue;
+      // (wave-uniform by construction; stated to the compiler, which must hold the base in scalar registers)
+      const uint64_t source = (uint64_t)(slice + (int64_t)j * WROWS * co_pad);
+      // (the builtin returns int: each half goes through uint32_t, or a low half with bit 31 set would sign-extend over the high one)
+      const uint32_t base_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)source);
+      const uint32_t base_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(source >> 32));
+      const uint64_t base = ((uint64_t)base_hi << 32) | base_lo;
+      ring_glds16((const void*)base, w_lane, __builtin_amdgcn_readfirstlane(w_lds + (uint32_t)(stage_index * WSTAGE + j * 256) * 4u));
+    }
+  };
+
   f32x16 acc[MI][NI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
@@ -177,6 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
   const float* b_base = patch + lhi * PHPW + ((wave * NI) * RPB + l31 / TW) * PW + l31 % TW;
 
   if (cbeg < cend) {
+    if constexpr (WIMG) dma_weights(cbeg, 0);
     fetch(cbeg);
     if (PRO) {
       for (int c = tid; c < cend - cbeg; c += 256) {
@@ -187,15 +224,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
       __syncthreads();
     }
     stage(cbeg);
+    if (WIMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMAs have landed; the barrier tells the others'
     __syncthreads();
+    int cur = 0;                                                     // WIMG: the weight stage of this chunk
     for (int c0 = cbeg; c0 < cend; c0 += CI_T) {
       const bool more = c0 + CI_T < cend;
-      if (more) fetch(c0 + CI_T);
+      if (more) {
+        fetch(c0 + CI_T);
+        // the other stage: everyone left it at the previous chunk's barrier.  (Behind the patch loads: the compiler guards the
+        // patch registers it overwrites with a full vmcnt wait in front of those loads, which would wait for these DMAs too.)
+        if constexpr (WIMG) dma_weights(c0 + CI_T, cur ^ 1);
+      }
       // (the channel-pair loop is kept rolled: full unrolling makes the scheduler hoist hundreds of LDS reads and
       // spill; the 9 taps x MI x NI MFMAs inside are plenty of straight-line work)
 #pragma unroll 1
       for (int cp = 0; cp < CI_T / 2; ++cp) {
-        const float* a_cp = a_base + cp * (2 * 9 * LDW);
+        const float* a_cp = a_base + (WIMG ? cur * WSTAGE : 0) + cp * (2 * 9 * LDW);
         const float* b_cp = b_base + cp * (2 * PHPW);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -213,11 +257,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
               acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
         }
       }
+      if (WIMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the next chunk's slice (and patch registers) have arrived
       __syncthreads();
       if (more) {
         stage(c0 + CI_T);
         __syncthreads();
       }
+      cur ^= 1;
     }
   }
 
@@ -695,7 +741,13 @@ static void launch_conv3_plain(const Conv3Params& p, int th, dim3 grid, hipStrea
 
 template <int BM, int CI_T, int TW>
 static void launch_conv3_w(const Conv3Params& p, int th, dim3 grid, hipStream_t stream) {
-  if (p.epi_x) {
+  if (p.w_packed && p.epi_x) {          // the weight image: the two fused forms of the dense layers (conv3x3_run admits no other)
+    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+  } else if (p.w_packed) {
+    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, true, TW, false, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, true, TW, false, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+  } else if (p.epi_x) {
     if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
   } else if (p.bn_mean) {
@@ -828,7 +880,14 @@ int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int
 int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, int32_t w_so, int32_t w_si, int32_t w_skh,
                 int32_t w_skw, const float* bias, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t H,
                 int32_t W, int accumulate, hipStream_t stream, const float* const* bn, const BnBackwardEpilogue* epilogue,
-                int precision, const Conv3Placement* placement) {
+                int precision, const Conv3Placement* placement, const float* w_image) {
+  // SRGAN_NO_CONV3_IMAGE=1 (read once): the weight image is ignored and the weights are gathered from w, so that a test or
+  // bench.py reaches the reference path through the same calls
+  static const bool no_image = getenv("SRGAN_NO_CONV3_IMAGE") != nullptr && atoi(getenv("SRGAN_NO_CONV3_IMAGE")) == 1;
+  if (no_image) w_image = nullptr;
+  SRGAN_REQUIRE(w_image == nullptr || (precision == 0 && placement == nullptr && (bn != nullptr) != (epilogue != nullptr) &&
+                                       (((uintptr_t)w_image) & 15) == 0), SRGAN_EUNSUPPORTED,
+                "conv3x3 weight image: the fp32 fused batch-norm forms, full window, 16-byte aligned image");
   Conv3Params p;
   p.taps = placement ? placement->taps : 0x1FF;
   p.out_plane = placement ? placement->out_plane : H * W;
@@ -906,13 +965,18 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
     else if (plan.small) launch_conv3_mixed_small<8>(p, bm, precision, grid, stream);
     else launch_conv3_mixed(p, bm, th, tw, precision, grid, stream);
   }
-  else if (bm == 32) launch_conv3<32, 8>(p, th, tw, grid, stream);
-  else launch_conv3<64, 4>(p, th, tw, grid, stream);
+  else {
+    p.w_packed = w_image;
+    if (bm == 32) launch_conv3<32, 8>(p, th, tw, grid, stream);
+    else launch_conv3<64, 4>(p, th, tw, grid, stream);
+  }
   if (p.epi_partial && !epilogue->partial_out)
     bn_partial_reduce_run(p.epi_partial, p.epi_tiles, CO, p.bn_inv, epilogue->g_gamma, epilogue->g_beta, stream);
   const int status = launch_status();
   const int64_t pixels3 = (int64_t)N * H * W;       // (+ x read by the fused batch-norm backward epilogue)
-  profile_bracket_end(profile_slot, stream, CO, pixels3, (int64_t)CI * __builtin_popcount((unsigned)p.taps), 2, bm, th * 32, split, 0, 0,
+  // (the report's akf column: 1 = the weights were staged from the weight image)
+  profile_bracket_end(profile_slot, stream, CO, pixels3, (int64_t)CI * __builtin_popcount((unsigned)p.taps), 2, bm, th * 32, split,
+                      (precision == 0 && p.w_packed) ? 1 : 0, 0,
                       (int64_t)CI * pixels3 + (epilogue ? (int64_t)CO * pixels3 : 0), precision);
   return status;
 }

@@ -1169,13 +1169,14 @@ int srgan_conv2d_bnrelu_supported(const srgan_conv_desc* desc, int pass) {
 // y_state: 0 = y holds anything (stored over), 2 = y is already zero where the convolution writes (a kernel that splits
 // K over the grid then skips its own zero-fill launch; see srgan_conv2d_fwd_bnrelu_splits).
 static int fwd_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w, const float* bias,
-                      float* y, int y_state, int* plan_only_split, void* stream) {
+                      float* y, int y_state, int* plan_only_split, void* stream, const float* image = nullptr) {
   ConvGeom g;
   SRGAN_GEOM(desc, g, "srgan_conv2d_fwd_bnrelu");
   SRGAN_REQUIRE(plan_only_split || (x && w && y && bn_ok(bn)), SRGAN_EINVAL, "srgan_conv2d_fwd_bnrelu pointers");
   SRGAN_REQUIRE(srgan_conv2d_bnrelu_supported(desc, 0), SRGAN_EUNSUPPORTED, "srgan_conv2d_fwd_bnrelu geometry support");
   const float* const coefficients[4] = {bn ? bn->mean : nullptr, bn ? bn->inv_std : nullptr, bn ? bn->gamma : nullptr,
                                         bn ? bn->beta : nullptr};
+  SRGAN_REQUIRE(image == nullptr || !pointwise(g), SRGAN_EUNSUPPORTED, "srgan_conv2d_fwd_bnrelu_image: 3x3 convolutions");
   if (pointwise(g) && (plan_only_split || ((uintptr_t)w & 15) == 0) &&
       pointwise_ksplit_wanted(g.N, g.C, g.K, g.H * g.W, true)) {
     if (plan_only_split) { *plan_only_split = 1; return SRGAN_OK; }
@@ -1187,7 +1188,13 @@ static int fwd_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_b
                          coefficients, nullptr, plan_only_split);
   if (plan_only_split) { *plan_only_split = conv3x3_splits(g.N, g.C, g.K, g.H, g.W); return SRGAN_OK; }
   return conv3x3_run(x, g.x_bs, w, 0, g.C * 9, 9, 3, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H, g.W, y_state,
-                     (hipStream_t)stream, coefficients);
+                     (hipStream_t)stream, coefficients, nullptr, 0, nullptr, image);
+}
+
+int srgan_conv2d_fwd_bnrelu_image(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
+                                  const float* image, const float* bias, float* y, void* stream) {
+  SRGAN_REQUIRE(image != nullptr, SRGAN_EINVAL, "srgan_conv2d_fwd_bnrelu_image: the weight image");
+  return fwd_bnrelu(desc, x, bn, w, bias, y, 0, nullptr, stream, image);
 }
 
 int srgan_conv2d_fwd_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
@@ -1206,7 +1213,8 @@ int srgan_conv2d_fwd_bnrelu_splits(const srgan_conv_desc* desc) {
 }
 
 static int bwd_data_bnrelu(const srgan_conv_desc* desc, const float* gy, const float* w, const srgan_bn_relu* bn, const float* x,
-                          float* gx, float* g_gamma, float* g_beta, float* partials, int accumulate, void* stream) {
+                          float* gx, float* g_gamma, float* g_beta, float* partials, int accumulate, void* stream,
+                          const float* image = nullptr) {
   ConvGeom g;
   SRGAN_GEOM(desc, g, "srgan_conv2d_bwd_data_bnrelu");
   SRGAN_REQUIRE(gy && w && x && gx && bn_ok(bn), SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu pointers");
@@ -1218,12 +1226,28 @@ static int bwd_data_bnrelu(const srgan_conv_desc* desc, const float* gy, const f
   epilogue.x = x; epilogue.x_bs = g.x_bs;
   epilogue.bn[0] = bn->mean; epilogue.bn[1] = bn->inv_std; epilogue.bn[2] = bn->gamma; epilogue.bn[3] = bn->beta;
   epilogue.g_gamma = g_gamma; epilogue.g_beta = g_beta; epilogue.partial_out = partials;
+  SRGAN_REQUIRE(image == nullptr || !pointwise(g), SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu_image: 3x3 convolutions");
   if (pointwise(g))
     return pointwise_run(gy, g.y_bs, w, 1, g.C, nullptr, gx, g.x_bs, g.N, g.K, g.C, g.H * g.W, accumulate,
                          (hipStream_t)stream, nullptr, &epilogue);
   SRGAN_REQUIRE(!accumulate, SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu 3x3: gx is stored, not accumulated");
   return conv3x3_run(gy, g.y_bs, w, 8, 9, g.C * 9, -3, -1, nullptr, gx, g.x_bs, g.N, g.K, g.C, g.H, g.W, 0,
-                     (hipStream_t)stream, nullptr, &epilogue);
+                     (hipStream_t)stream, nullptr, &epilogue, 0, nullptr, image);
+}
+
+int srgan_conv2d_bwd_data_bnrelu_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
+                                       const srgan_bn_relu* bn, const float* x, float* gx, float* g_gamma, float* g_beta,
+                                       int accumulate, void* stream) {
+  SRGAN_REQUIRE(image != nullptr, SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu_image: the weight image");
+  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, g_gamma, g_beta, nullptr, accumulate, stream, image);
+}
+
+int srgan_conv2d_bwd_data_bnrelu_partials_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
+                                                const srgan_bn_relu* bn, const float* x, float* gx, float* partials,
+                                                int accumulate, void* stream) {
+  SRGAN_REQUIRE(partials != nullptr && image != nullptr, SRGAN_EINVAL,
+                "srgan_conv2d_bwd_data_bnrelu_partials_image: the partial-sum region and the weight image");
+  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, nullptr, nullptr, partials, accumulate, stream, image);
 }
 
 int srgan_conv2d_bwd_data_bnrelu(const srgan_conv_desc* desc, const float* gy, const float* w, const srgan_bn_relu* bn,
@@ -1415,7 +1439,7 @@ int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
                   SRGAN_FEATURE_BLOCKED16 | SRGAN_FEATURE_BATCHED_SHADOWS | SRGAN_FEATURE_CROWD_FULL_IMAGE |
                   SRGAN_FEATURE_IMAGE_BATCHES | SRGAN_FEATURE_BATCH_NORM_TRAIN | SRGAN_FEATURE_BLOCKED_BATCH_NORM |
                   SRGAN_FEATURE_BLOCKED_FROZEN_NORM | SRGAN_FEATURE_DEVICE_DRAWS | SRGAN_FEATURE_IMAGE_SUMMARIES |
-                  SRGAN_FEATURE_DISTRIBUTION_SUMMARIES;
+                  SRGAN_FEATURE_DISTRIBUTION_SUMMARIES | SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;

@@ -23,7 +23,8 @@ int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int
 int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, int32_t w_so, int32_t w_si, int32_t w_skh,
                 int32_t w_skw, const float* bias, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t H,
                 int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
-                const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const Conv3Placement* placement = nullptr);
+                const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const Conv3Placement* placement = nullptr,
+                const float* w_image = nullptr);      // w_image: the operand's weight image (blocked16.h), fused fp32 forms only
 
 // A grouped weight-gradient launch (conv3x3_wgrad.hip, pointwise_wgrad.hip) asks for this many times the resident
 // workgroups, shared out over its problems.

@@ -265,6 +265,37 @@ def _block_parameters(layers):
     return cached[1]
 
 
+WEIGHT_IMAGE = True  # the 3x3 convolutions stage their weights from per-step packed images (tests flip this)
+
+
+def _weight_images(layers):
+    """Per layer, the device addresses (forward, transposed) of ``conv2``'s weight images (``blocked16.Conv3x3ImageShadow``),
+    current with the masters; None when the weights do not live in an arena (nothing would refresh the images behind an
+    update).  The images are refreshed behind ``Adam.step()`` with the arena's other shadows; here a stamp over the arena's and
+    the weights' version counters tells when to look at the shadows again (an update, a checkpoint load, a test editing a
+    weight), so a pass over an unchanged block costs one tuple comparison.  Inside a HIP-graph capture nothing can be packed:
+    images that do not exist yet are not used (the calls without them give the same bits)."""
+    from . import blocked16
+    cache = layers[0].__dict__.get('_srgan_weight_images')
+    if cache is None or cache['count'] != len(layers):
+        weights = [layer.conv2.weight for layer in layers]
+        arena = getattr(weights[0], '_srgan_arena', None)
+        if arena is None or any(getattr(w, '_srgan_arena', None) is not arena for w in weights):
+            return None
+        if blocked16._capturing():
+            return None
+        cache = layers[0].__dict__['_srgan_weight_images'] = dict(
+            count=len(layers), weights=weights, arena=arena, stamp=None, pointers=None,
+            shadows=[blocked16.shadow_of(layer.conv2, 'conv3x3_image', 0) for layer in layers])
+    arena = cache['arena']
+    stamp = (getattr(arena, 'version', 0), arena.data._version, cache['weights'][0].data_ptr(),
+             tuple(w._version for w in cache['weights']))
+    if stamp != cache['stamp']:
+        cache['pointers'] = [(s.forward.data_ptr(), s.transposed.data_ptr()) for s in (shadow.fresh() for shadow in cache['shadows'])]
+        cache['stamp'] = stamp
+    return cache['pointers']
+
+
 def dense_block(x, layers):
     """``layers``: the block's ``_DenseLayer`` modules (norm1, conv1, norm2, conv2)."""
     n, c0, h, w = x.shape
@@ -317,14 +348,21 @@ def dense_block(x, layers):
     F._call('srgan_copy_channels', x.data.data_ptr(), c0, 0, buffer.data_ptr(), total, 0, c0, n, hw, 0, stream)
     forward1 = 'srgan_conv2d_fwd_bnrelu_into_zeros' if zero_b1 else 'srgan_conv2d_fwd_bnrelu'
     forward2 = 'srgan_conv2d_fwd_bnrelu_into_zeros' if zero_new else 'srgan_conv2d_fwd_bnrelu'
+    # conv2's weights from the per-step packed images (the forward here, the data gradient in `backward`)
+    images = _weight_images(layers) if (WEIGHT_IMAGE and prologue) else None
     for index, layer in enumerate(layers):
         cin = c0 + index * growth
         b1 = b1_all[index] if b1_all is not None else _empty((n, width, h, w), device)
         if prologue:
             F._call(forward1, _desc(n, cin, h, w, width, 1, 1, 1, 0, buffer_bs, 0), buffer.data_ptr(),
                     bn_struct(layer.norm1), layer.conv1.weight.data_ptr(), None, b1.data_ptr(), stream)
-            F._call(forward2, _desc(n, width, h, w, growth, 3, 3, 1, 1, 0, buffer_bs), b1.data_ptr(),
-                    bn_struct(layer.norm2), layer.conv2.weight.data_ptr(), None, _ptr(buffer, cin * hw), stream)
+            if images is not None and not zero_new:
+                F._call('srgan_conv2d_fwd_bnrelu_image', _desc(n, width, h, w, growth, 3, 3, 1, 1, 0, buffer_bs), b1.data_ptr(),
+                        bn_struct(layer.norm2), layer.conv2.weight.data_ptr(), images[index][0], None, _ptr(buffer, cin * hw),
+                        stream)
+            else:
+                F._call(forward2, _desc(n, width, h, w, growth, 3, 3, 1, 1, 0, buffer_bs), b1.data_ptr(),
+                        bn_struct(layer.norm2), layer.conv2.weight.data_ptr(), None, _ptr(buffer, cin * hw), stream)
             if requires:
                 saved.append([None, b1, None])
             continue
@@ -360,6 +398,8 @@ def dense_block(x, layers):
                                       'gradient only; set srgan_amd.fused.ENABLED = False for parameter gradients of '
                                       'a recorded backward')
         stream = F._stream()
+        # (looked up again: an optimizer update may lie between the forward and this sweep -- the generator step's second pass)
+        images = _weight_images(layers) if (WEIGHT_IMAGE and epilogue2) else None
         if not recorded and incoming_gradient_is_exclusive() and g.data.is_contiguous():
             gbuf = g.data                         # nobody else reads it: the layers accumulate into it in place
         else:
@@ -409,9 +449,17 @@ def dense_block(x, layers):
                 F._call('srgan_conv2d_bwd_weight', desc2, t2.data_ptr(), g_new, layer.conv2.weight.grad.data_ptr(), 1, 0,
                         stream)
             g_b1 = g_b1_all[index] if g_b1_all is not None else _empty(b1.shape, device)
-            if epilogue2 and plan is not None:
+            if epilogue2 and plan is not None and images is not None:
+                F._call('srgan_conv2d_bwd_data_bnrelu_partials_image', desc2, g_new, layer.conv2.weight.data_ptr(), images[index][1],
+                        bn_struct(layer.norm2), b1.data_ptr(), g_b1.data_ptr(), _ptr(scratch, plan['offsets'][index][2]), 0, stream)
+            elif epilogue2 and plan is not None:
                 F._call('srgan_conv2d_bwd_data_bnrelu_partials', desc2, g_new, layer.conv2.weight.data_ptr(),
                         bn_struct(layer.norm2), b1.data_ptr(), g_b1.data_ptr(), _ptr(scratch, plan['offsets'][index][2]), 0, stream)
+            elif epilogue2 and images is not None:
+                F._call('srgan_conv2d_bwd_data_bnrelu_image', desc2, g_new, layer.conv2.weight.data_ptr(), images[index][1],
+                        bn_struct(layer.norm2), b1.data_ptr(), g_b1.data_ptr(),
+                        layer.norm2.weight.grad.data_ptr() if want_params else None,
+                        layer.norm2.bias.grad.data_ptr() if want_params else None, 0, stream)
             elif epilogue2:
                 F._call('srgan_conv2d_bwd_data_bnrelu', desc2, g_new, layer.conv2.weight.data_ptr(),
                         bn_struct(layer.norm2), b1.data_ptr(), g_b1.data_ptr(),
