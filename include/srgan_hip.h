@@ -13,6 +13,10 @@
  *     workspace the CALLER registers per (device, stream) with srgan_set_workspace (below); a contraction that
  *     needs it on a stream without one fails with -1 and a message.  Activations are NCHW, conv weights
  *     [K, C, R, S], transposed-conv weights [Cin, Cout, R, S] (torch layouts).
+ *   - alignment: any 4-byte-aligned fp32 pointer is accepted (a view may start at any element of a buffer) unless an
+ *     entry point states otherwise (srgan_pack_bf16 / srgan_unpack_bf16, the fused pooling calls, the workspace);
+ *     16-byte alignment of every pointer of a call selects the 16-byte vector paths of the streaming kernels, anything
+ *     else their single-float loops, with the same results.
  *   - thread safety: calls may come from several host threads (the registry and the profile state are locked,
  *     srgan_last_error is thread-local); two threads must not launch on the SAME stream with the same workspace
  *     concurrently, as with any stream-ordered resource.
@@ -251,6 +255,11 @@ int srgan_gemm(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int
  * 17 softplus, 18 one_minus_square, 19 rsqrt.
  * Binary op codes: 0 add, 1 sub, 2 mul, 3 div, 4 div_safe (0 where b == 0), 5 max,
  * 6 leaky_mask_mul (a where b > 0 else p0*a: the backward of leaky_relu / relu), 7 axpy (a + p0*b).
+ * tanh is exactly +-1 from |x| = 9 on (1 - tanh(9) = 3.0e-8 is below the fp32 spacing 2^-24 under 1: at most 0.51 ulp off).
+ * NaN rule: the ops that select with `x > 0` or take fmaxf -- relu, step, sign, leaky_relu, leaky_mask_mul (its mask b),
+ * max, and srgan_row_max -- treat a NaN as "not positive" / drop it (relu, step, sign: NaN -> 0; leaky_relu: NaN -> p0 * NaN
+ * = NaN; leaky_mask_mul: NaN mask -> p0 * a; max, row_max: the other operand), where torch propagates the NaN.  The same
+ * `> 0` is the mask of the fused convolution epilogues, bit for bit; every other op follows IEEE arithmetic.
  * Replace torch elementwise call sites: leaky_relu/relu/tanh (reference coefficient/models.py:24-26;
  * age/models.py:47-51,70-73; crowd/models.py:339,343,780-784,1150,1154), the distance functions
  * (utility.py:201-243), logsumexp / BCE / CE pieces (utility.py:161-182, sgan.py:14-15). */

@@ -1,7 +1,7 @@
 // elementwise.hip -- HBM-bound streaming kernels: unary / binary maps, per-channel affine broadcast
 // (frozen batch-norm, bias, row / column / scalar broadcasts) and channel-range copies (concat / slice).
-// All are one read + one write per element (roofline: HBM ~6.3 TB/s achievable), float4 wide, grid-stride
-// over at most 2048 workgroups.
+// All are one read + one write per element (roofline: HBM ~6.3 TB/s achievable), float4 wide where every pointer of
+// the call is 16-byte aligned (single floats otherwise: include/srgan_hip.h), grid-stride over at most 2048 workgroups.
 #include "common.h"
 
 namespace srgan {
@@ -23,7 +23,7 @@ __device__ __forceinline__ float unary(float x, float p0, float p1) {
     case U_LOG1P: return log1pf(x);
     case U_SQUARE: return x * x;
     case U_RECIP: return 1.f / x;
-    case U_TANH: return tanhf(x);
+    case U_TANH: return fabsf(x) >= 9.f ? copysignf(1.f, x) : tanhf(x);   // saturated from 9 on (1 - tanh(9) < 2^-24); NaN falls through
     case U_RELU: return x > 0.f ? x : 0.f;
     case U_STEP: return x > 0.f ? 1.f : 0.f;
     case U_AFFINE: return p0 * x + p1;
@@ -56,6 +56,10 @@ template <int OP>
 // (no __restrict__: these run in place for gradient accumulation and fills)
 __global__ __launch_bounds__(256) void unary_kernel(const float* x, float* y, int64_t n, float p0, float p1) {
   const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+  if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) {       // a view that starts off a 16-byte boundary: single floats (uniform)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = unary<OP>(x[i], p0, p1);
+    return;
+  }
   const float4* x4 = reinterpret_cast<const float4*>(x);
   float4* y4 = reinterpret_cast<float4*>(y);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -71,6 +75,10 @@ __global__ __launch_bounds__(256) void unary_kernel(const float* x, float* y, in
 template <int OP>
 __global__ __launch_bounds__(256) void binary_kernel(const float* a, const float* b, float* y, int64_t n, float p0) {
   const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+  if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) != 0) {       // as unary_kernel: single floats (uniform)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = binary<OP>(a[i], b[i], p0);
+    return;
+  }
   const float4* a4 = reinterpret_cast<const float4*>(a);
   const float4* b4 = reinterpret_cast<const float4*>(b);
   float4* y4 = reinterpret_cast<float4*>(y);

@@ -28,7 +28,7 @@ __device__ __forceinline__ float row_run_sum(const float* __restrict__ a, const 
   const int64_t end = beg + seg < HW ? beg + seg : HW;
   const float mu = mean ? mean[c] : 0.f;
   float acc = 0.f;
-  if (((base | beg) & 3) == 0) {       // 16-byte aligned run: float4 loads
+  if (((base | beg) & 3) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0) {       // 16-byte aligned run: float4 loads
     const int64_t n4 = (end - beg) >> 2;
     const float4* a4 = reinterpret_cast<const float4*>(a + base + beg);
     const float4* b4 = b ? reinterpret_cast<const float4*>(b + base + beg) : nullptr;

@@ -65,6 +65,26 @@ def assert_close_norm(actual, expected, rtol=1e-3, what=''):
     assert err <= rtol, f'{what}: max err / max|expected| = {err:.3e} > {rtol}'
 
 
+def assert_exact(got, want, what, dims=('n', 'c', 'h', 'w')):
+    """got (device fp32) == want (float64) exactly; on a mismatch: how many, the first eight with got / want, and which
+    indices of every dimension (channels, rows, pixels) the mismatches fall in."""
+    got = got.detach().cpu().double()
+    want = want.detach().cpu().double()
+    assert got.shape == want.shape, f'{what}: shape {tuple(got.shape)} != {tuple(want.shape)}'
+    bad = ~(got == want)
+    if not bool(bad.any()):
+        return
+    where = bad.nonzero()
+    lines = [f'{what}: {where.shape[0]} of {got.numel()} elements differ (shape {tuple(got.shape)})']
+    for index in where[:8].tolist():
+        lines.append(f'  {dict(zip(dims, index))}: got {got[tuple(index)].item()!r} want {want[tuple(index)].item()!r}')
+    for axis, name in enumerate(dims[:got.dim()]):
+        values = torch.unique(where[:, axis]).tolist()
+        shown = values[:24]
+        lines.append(f'  {name}: {len(values)} of {got.shape[axis]} distinct {shown}{" ..." if len(values) > len(shown) else ""}')
+    raise AssertionError('\n'.join(lines))
+
+
 def _check(status, what):
     from srgan_amd import _lib
     _lib.check(status, what)

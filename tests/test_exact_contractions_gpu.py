@@ -23,7 +23,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from helpers import profiled
+from helpers import assert_exact, profiled
 from contraction_cases import (B, BN_DATA_CASES, BN_FORWARD_CASES, CONV_CASES, CONVT_CASES, EXACT_LIMIT, FUSED_WGRAD_REACH,
                                GEMM_CASES, GROUPED_WGRAD_CASES, GROUPED_WGRAD_REACH, PREFILL, W, X, direct_is_cheap)
 
@@ -84,26 +84,6 @@ def assert_limit(magnitude, fraction_bits, what):
     below 2^(24 - f)."""
     limit = EXACT_LIMIT >> fraction_bits
     assert magnitude < limit, f'{what}: a partial sum reaches {magnitude:g} >= 2^{24 - fraction_bits}: the case is broken'
-
-
-def assert_exact(got, want, what, dims=('n', 'c', 'h', 'w')):
-    """got (device fp32) == want (float64) exactly; on a mismatch: how many, the first eight with got / want, and which
-    indices of every dimension (channels, rows, pixels) the mismatches fall in."""
-    got = got.detach().cpu().double()
-    want = want.detach().cpu().double()
-    assert got.shape == want.shape, f'{what}: shape {tuple(got.shape)} != {tuple(want.shape)}'
-    bad = ~(got == want)
-    if not bool(bad.any()):
-        return
-    where = bad.nonzero()
-    lines = [f'{what}: {where.shape[0]} of {got.numel()} elements differ (shape {tuple(got.shape)})']
-    for index in where[:8].tolist():
-        lines.append(f'  {dict(zip(dims, index))}: got {got[tuple(index)].item()!r} want {want[tuple(index)].item()!r}')
-    for axis, name in enumerate(dims[:got.dim()]):
-        values = torch.unique(where[:, axis]).tolist()
-        shown = values[:24]
-        lines.append(f'  {name}: {len(values)} of {got.shape[axis]} distinct {shown}{" ..." if len(values) > len(shown) else ""}')
-    raise AssertionError('\n'.join(lines))
 
 
 # ------------------------------------------------------------------------------------------------- convolutions
