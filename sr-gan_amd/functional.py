@@ -782,8 +782,10 @@ def bn_relu_max_pool2d(x, mean, inv_std, gamma, beta, kernel_size, stride, paddi
         into_gamma = gamma.grad_buffer.data_ptr() if direct else (both[0].data_ptr() if want_params else None)
         into_beta = beta.grad_buffer.data_ptr() if direct else (both[1].data_ptr() if want_params else None)
         gx_data = _empty(x.shape, x.data)
-        _call('srgan_bn_relu_maxpool_bwd', _ptr(g), argmax.data_ptr(), _ptr(x), _ptr(mean), _ptr(inv_std), _ptr(gamma),
-              _ptr(beta), gx_data.data_ptr(), into_gamma, into_beta, n, c, h, w, kernel_size, stride, padding, oh, ow, _stream())
+        upstream = g.data if g.data.is_contiguous() else g.data.contiguous()
+        _call('srgan_bn_relu_maxpool_bwd', upstream.data_ptr(), argmax.data_ptr(), _ptr(x), _ptr(mean), _ptr(inv_std),
+              _ptr(gamma), _ptr(beta), gx_data.data_ptr(), into_gamma, into_beta, n, c, h, w, kernel_size, stride, padding,
+              oh, ow, _stream())
         ggamma = Var(both[0]) if want_params and not direct else None
         gbeta = Var(both[1]) if want_params and not direct else None
         return (Var(gx_data) if needs[0] else None), ggamma, gbeta
@@ -819,6 +821,9 @@ def bn_relu_avg_pool2d(x, mean, inv_std, gamma, beta):
         into_gamma = gamma.grad_buffer.data_ptr() if direct else (both[0].data_ptr() if want_params else None)
         into_beta = beta.grad_buffer.data_ptr() if direct else (both[1].data_ptr() if want_params else None)
         gx_data = _empty(x.shape, x.data)
+        # (every gradient the sweep itself makes is contiguous; the ROOT's cotangent is the caller's tensor as it came -- a
+        # channel slice of a wider one, say -- and reaches the op that made the root: bn_relu_max_pool2d and
+        # _max_pool2d_backward guard in the same way)
         upstream = g.data if g.data.is_contiguous() else g.data.contiguous()
         _call('srgan_bn_relu_avgpool2_bwd', upstream.data_ptr(), _ptr(x), _ptr(mean), _ptr(inv_std), _ptr(gamma), _ptr(beta),
               gx_data.data_ptr(), into_gamma, into_beta, n, c, h, w, _stream())
@@ -835,8 +840,9 @@ def _max_pool2d_backward(g, argmax, in_shape, geometry):
     n, c, h, w = in_shape
     kernel_size, stride, padding, oh, ow = geometry
     data = _empty(in_shape, g.data)
-    _call('srgan_maxpool2d_bwd', _ptr(g), argmax.data_ptr(), data.data_ptr(), n * c, h, w, kernel_size, stride, padding,
-          oh, ow, _stream())
+    upstream = g.data if g.data.is_contiguous() else g.data.contiguous()
+    _call('srgan_maxpool2d_bwd', upstream.data_ptr(), argmax.data_ptr(), data.data_ptr(), n * c, h, w, kernel_size, stride,
+          padding, oh, ow, _stream())
     return _out(data, (g,), lambda gg, needs: (_pool_gather(gg, argmax, g.shape),), 'max_pool2d_backward')
 
 

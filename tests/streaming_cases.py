@@ -1,4 +1,4 @@
-"""The cases of the streaming-kernel tests (elementwise.hip, reduce.hip, the plain parts of pool.hip), shared by
+"""The cases of the streaming-kernel tests (elementwise.hip, reduce.hip, all of pool.hip), shared by
 test_streaming_cases_cpu.py (no library needed) and test_streaming_ops_gpu.py (the C ABI, bit for bit): the case tables, a
 float64 reference of every operation written from the formulas of include/srgan_hip.h, the branch each table entry exists to
 reach -- re-derived here from the hosts' constants, so that a changed constant fails the CPU test instead of un-covering a
@@ -8,6 +8,13 @@ Exact operands: tensors and cotangents are integers in [-X, X]; per-channel mean
 are in {0.5, 1, 2}, alpha in {0, 0.25, 0.5, 1}.  Every partial sum of absolute values stays below 2^(24 - f), f = the
 fractional bits of the terms (assert_exact_limit), so every fp32 sum is exact in any order, fma(x, a, b) is exact (the
 recomputed ReLU mask has no borderline element), and a correct kernel equals float64 bit for bit.
+
+The fused pools (srgan_bn_relu_maxpool_*, srgan_bn_relu_avgpool2_*) take the same operands with gamma of EITHER SIGN
+(fused_pool_vectors: at least one negative channel per case -- a = inv_std * gamma < 0 flips the order of the activated window
+-- and one channel whose norm is exactly 0 at x = mean, so `> 0` against `>= 0` shows).  a is then a multiple of 1/4, b = beta -
+mean * a and fma(x, a, b) multiples of 1/16 below 32; the pooled gradient per pixel S is an integer (max form) or a multiple of
+1/4 (average form: the 0.25 adds two fractional bits), S * a, S * (x - mean) and the sum times inv_std follow with the bits
+FUSED_POOL_FRACTION_BITS lists.
 """
 import functools
 import math
@@ -24,6 +31,9 @@ ROWS_MIN_HW = 256               # chan_affine_launch: rows kernel from this plan
 BLOCK_MIN_C, BLOCK_MAX_NHW = 256, 8192      # srgan_chan_reduce: one workgroup per channel
 REDUCE_MIN_WGS, REDUCE_SEG_CAP = 256, 65536
 TANGENT_ROWS = 16
+POOL_BWD_QUADS = 1024           # pool.hip: thread items (float4s of x; pairs of them in the average form) of one plane per workgroup
+ROW_FINISH_ROWS = 4096          # split_finish.h: channels per launch that can use the ordered finish; above: fp32 atomics
+POOL_MAX_PLANES = 65535         # the fused backwards and the fused average forward put N * C into the grid's y
 
 X, PREFILL = 3, 64
 EXACT_LIMIT = 2 ** 24
@@ -75,6 +85,17 @@ MAXPOOL = [(10, 13, 11, 3, 2, 1), (10, 13, 11, 2, 2, 0)] + \
     [(12, h, w, k, s, p) for (k, s, p, h, w) in [(2, 2, 0, 12, 10), (3, 1, 1, 9, 7), (3, 2, 1, 16, 16), (3, 3, 0, 10, 11), (2, 1, 0, 5, 6),
                                                   (2, 2, 0, 12, 8), (3, 2, 1, 15, 20), (3, 2, 1, 8, 4)]]
 AVGPOOL = [(6, 8, 8, 2), (3, 8, 6, 2), (2, 8, 8, 4), (3, 12, 10, 4), (4, 9, 12, 3), (5, 9, 6, 3)]   # (planes, H, W, k), s = k
+AVGPOOL_STRIDED = [(6, 12, 12, 3, 1), (6, 10, 10, 3, 2), (4, 5, 6, 2, 1), (3, 9, 12, 3, 2)]         # (planes, H, W, k, s), s != k
+# the fused pools, (N, C, H, W[, k, s, p]); C divides nothing, so c = plane % C is tested
+FUSED_MAX_FWD = [(2, 3, 13, 11, 3, 2, 1), (2, 3, 13, 11, 2, 2, 0), (1, 5, 9, 7, 3, 1, 1), (2, 3, 10, 11, 3, 3, 0)]
+FUSED_MAX_BWD = [(1, 1, 1, 4), (2, 3, 8, 4), (3, 5, 15, 20), (2, 3, 32, 128), (2, 3, 41, 100), (3, 2, 80, 64), (1, 4096, 2, 4),
+                 (1, 4097, 2, 4), (1, 65535, 1, 4)]                                              # 3 / 2 / 1 windows
+FUSED_AVG = [(1, 1, 2, 4), (2, 3, 6, 8), (3, 5, 10, 12), (2, 3, 64, 128), (2, 3, 50, 164), (3, 2, 80, 128), (1, 4096, 2, 4),
+             (1, 4097, 2, 4)]
+# back-to-back launches on one stream, parts (= N x workgroups per plane) 2, 6, 1, 2 with another C each time
+FUSED_MAX_SEQUENCE = [(2, 3, 8, 4), (3, 2, 41, 100), (1, 5, 15, 20), (1, 4, 80, 64)]
+FUSED_AVG_SEQUENCE = [(2, 3, 6, 8), (3, 2, 50, 164), (1, 5, 10, 12), (1, 4, 80, 128)]
+FUSED_REPEAT = dict(max=[(2, 3, 41, 100), (3, 2, 80, 64)], avg=[(2, 3, 50, 164), (3, 2, 80, 128)])     # several workgroups per plane
 COPY_CHANNELS = [dict(N=3, HW=35, src=(7, 2), dst=(5, 1), count=3, accumulate=0),      # (channels, first channel)
                  dict(N=2, HW=1025, src=(4, 1), dst=(6, 3), count=2, accumulate=1)]
 ADAM_N = [1, 3, 255, 257, STREAM_BLOCKS * THREADS + 1]
@@ -136,6 +157,39 @@ def tangent_span(taps):
     return 64 - 64 % taps
 
 
+def fused_pool_grid(form, n, c, h, w):
+    """(workgroups per plane, thread items in the last one, 'ordered' | 'atomic' parameter sums in the default mode) of the
+    fused backwards and the fused average forward; form 'max': one item = a float4 of x, 'avg': two rows' float4s."""
+    items = h * (w // 4) if form == 'max' else (h // 2) * (w // 4)
+    groups = -(-items // POOL_BWD_QUADS)
+    return groups, items - (groups - 1) * POOL_BWD_QUADS, 'ordered' if c <= ROW_FINISH_ROWS else 'atomic'
+
+
+def fused_pool_parts(form, n, c, h, w):
+    """The partial sums per channel that meet in ordered_row_finish: images x workgroups per plane."""
+    return n * fused_pool_grid(form, n, c, h, w)[0]
+
+
+def fused_max_bwd_supported(n, c, h, w, k, s, p):
+    return (k, s, p) == (3, 2, 1) and w % 4 == 0 and n * c <= POOL_MAX_PLANES and n * c * h * w < 2 ** 31
+
+
+def fused_avg_supported(n, c, h, w):
+    return (n > 0 and c > 0 and h >= 2 and w >= 4 and h % 2 == 0 and w % 4 == 0 and n * c <= POOL_MAX_PLANES
+            and n * c * h * w < 2 ** 31)
+
+
+def maxpool_bwd_path(w, k, s, p, offset=0):
+    """The kernel srgan_maxpool2d_bwd takes for rows of w floats with gx `offset` floats past a 16-byte boundary."""
+    if w % 4 == 0 and offset % 4 == 0 and (k, s, p) in ((3, 2, 1), (2, 2, 0)):
+        return 'quad321' if k == 3 else 'quad220'
+    return 'scalar'
+
+
+def pool_out(size, k, s, p=0):
+    return (size + 2 * p - k) // s + 1
+
+
 # ---- operands -------------------------------------------------------------------------------------------------------------
 def generator(*key):
     import zlib
@@ -170,6 +224,19 @@ def full_mantissa(n, gen):
 def channel_vectors(c, gen):
     return dict(mean=pick(QUARTERS, (c,), gen), inv_std=pick(SCALES, (c,), gen), gamma=pick(SCALES, (c,), gen),
                 beta=pick(QUARTERS, (c,), gen))
+
+
+def fused_pool_vectors(c, gen):
+    """channel_vectors with gamma of either sign -- at least one channel negative -- and one channel whose norm is exactly zero
+    at x = mean (mean = +-1, beta = 0): the recomputed mask meets its borderline, exactly."""
+    v = channel_vectors(c, gen)
+    sign = pick([-1.0, 1.0], (c,), gen)
+    sign[int(torch.randint(0, c, (1,), generator=gen))] = -1.0
+    v['gamma'] = v['gamma'] * sign
+    zero = int(torch.randint(0, c, (1,), generator=gen))
+    v['mean'][zero] = float(pick([-1.0, 1.0], (1,), gen))
+    v['beta'][zero] = 0.0
+    return v
 
 
 # ---- float64 references ---------------------------------------------------------------------------------------------------
@@ -405,17 +472,131 @@ def pool_scatter_ref(g, index, in_plane):
                           g.reshape(-1).double(), accumulate=True)
 
 
-def avgpool_ref(x, k):
+def maxpool_bwd_ref(g, index, h, w):
+    """gx [planes, H, W]: every g added at its window's arg-max (pool_scatter_ref, reshaped)."""
+    return pool_scatter_ref(g.reshape(g.shape[0], -1), index.reshape(index.shape[0], -1), h * w).reshape(g.shape[0], h, w)
+
+
+def avgpool_ref(x, k, s=None):
+    """Windows of k x k at stride s (default k), no padding: the mean of each."""
     planes, h, w = x.shape
-    oh, ow = h // k, w // k
-    return x[:, :oh * k, :ow * k].reshape(planes, oh, k, ow, k).sum(dim=(2, 4)) / (k * k)
+    if s is None or s == k:
+        oh, ow = h // k, w // k
+        return x[:, :oh * k, :ow * k].reshape(planes, oh, k, ow, k).sum(dim=(2, 4)) / (k * k)
+    return x.unfold(1, k, s).unfold(2, k, s).sum(dim=(3, 4)) / (k * k)
 
 
-def avgpool_bwd_ref(g, k, h, w):
+def avgpool_bwd_ref(g, k, h, w, s=None):
+    """gx[h, w] = (1 / k^2) x the sum of g over the windows that contain (h, w)."""
     planes, oh, ow = g.shape
     gx = torch.zeros(planes, h, w, dtype=torch.float64)
-    gx[:, :oh * k, :ow * k] = (g / (k * k)).repeat_interleave(k, dim=1).repeat_interleave(k, dim=2)
-    return gx
+    if s is None or s == k:
+        gx[:, :oh * k, :ow * k] = (g / (k * k)).repeat_interleave(k, dim=1).repeat_interleave(k, dim=2)
+        return gx
+    for r in range(k):
+        for c in range(k):
+            gx[:, r:r + s * oh:s, c:c + s * ow:s] += g
+    return gx / (k * k)
+
+
+def batch_norm_eval_ref(x, v):
+    """(x - mean) * inv_std * gamma + beta per channel of [N, C, H, W] (include/srgan_hip.h)."""
+    shape = (1, -1, 1, 1)
+    return (x - v['mean'].view(shape)) * v['inv_std'].view(shape) * v['gamma'].view(shape) + v['beta'].view(shape)
+
+
+def bn_relu_maxpool_ref(x, v, k, s, p):
+    """maxpool(relu(bn(x))): (values, flat in-plane arg-max) [N, C, OH, OW] -- the first maximum in row-major window order,
+    padding skipped (maxpool_ref)."""
+    n, c, h, w = x.shape
+    oh, ow = pool_out(h, k, s, p), pool_out(w, k, s, p)
+    values, index = maxpool_ref(batch_norm_eval_ref(x, v).clamp_min(0.0).reshape(n * c, h, w), k, s, p, oh, ow)
+    return values.reshape(n, c, oh, ow), index.reshape(n, c, oh, ow)
+
+
+def fused_pool_bwd_from(pooled, x, v):
+    """From S, the pooled gradient per input pixel: (masked S, gx = S * inv_std * gamma, g_gamma = sum S * (x - mean) * inv_std,
+    g_beta = sum S), S masked by [bn(x) > 0]."""
+    shape = (1, -1, 1, 1)
+    masked = torch.where(batch_norm_eval_ref(x, v) > 0, pooled, torch.zeros_like(pooled))
+    gx = masked * v['inv_std'].view(shape) * v['gamma'].view(shape)
+    g_gamma = (masked * (x - v['mean'].view(shape)) * v['inv_std'].view(shape)).sum(dim=(0, 2, 3))
+    return masked, gx, g_gamma, masked.sum(dim=(0, 2, 3))
+
+
+def bn_relu_maxpool_bwd_ref(g, index, x, v):
+    """(gx, g_gamma, g_beta): g scattered through the arg-max, times [bn(x) > 0]."""
+    n, c, h, w = x.shape
+    pooled = maxpool_bwd_ref(g.reshape(n * c, *g.shape[2:]), index.reshape(n * c, *index.shape[2:]), h, w).reshape(n, c, h, w)
+    return fused_pool_bwd_from(pooled, x, v)[1:]
+
+
+def bn_relu_avgpool2_ref(x, v):
+    n, c, h, w = x.shape
+    return avgpool_ref(batch_norm_eval_ref(x, v).clamp_min(0.0).reshape(n * c, h, w), 2).reshape(n, c, h // 2, w // 2)
+
+
+def bn_relu_avgpool2_bwd_ref(g, x, v):
+    """The same with S = 0.25 * g[h / 2, w / 2]."""
+    pooled = (0.25 * g).repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    return fused_pool_bwd_from(pooled, x, v)[1:]
+
+
+# fractional bits of every exact output of the fused pools (a: 2, b and fma(x, a, b): 4, x - mean: 2, inv_std: 1)
+FUSED_POOL_FRACTION_BITS = {'max': dict(y=4, gx=2, g_gamma=3, g_beta=0), 'avg': dict(y=6, gx=4, g_gamma=5, g_beta=2)}
+
+
+def fused_pool_magnitudes(form, g, index, x, v, old_gamma, old_beta):
+    """Per output, the largest sum of ABSOLUTE values any order of adding its terms can reach (the old contents included)."""
+    n, c, h, w = x.shape
+    shape = (1, -1, 1, 1)
+    if form == 'max':
+        pooled = maxpool_bwd_ref(g.abs().reshape(n * c, *g.shape[2:]), index.reshape(n * c, *index.shape[2:]), h, w).reshape(n, c, h, w)
+    else:
+        pooled = (0.25 * g.abs()).repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    a = (v['inv_std'] * v['gamma']).abs().view(shape)
+    activated = x.abs() * a + (v['beta'].abs() + v['mean'].abs() * a.view(-1)).view(shape)
+    centred = pooled * (x.abs() + v['mean'].abs().view(shape)) * v['inv_std'].view(shape)
+    return dict(y=float(activated.max()) * (1 if form == 'max' else 4), gx=float((pooled * a).max()),
+                g_gamma=float((centred.sum(dim=(0, 2, 3)) + old_gamma.abs()).max()),
+                g_beta=float((pooled.sum(dim=(0, 2, 3)) + old_beta.abs()).max()))
+
+
+@functools.lru_cache(maxsize=None)
+def fused_pool_problem(form, case):
+    """Operands and float64 results of one fused-pool case, computed once and shared (do not modify): x, g, v, old_gamma,
+    old_beta, y, (index), gx, g_gamma, g_beta (the last two WITH the old contents), magnitudes."""
+    n, c, h, w = case[:4]
+    k, s, p = case[4:] if len(case) > 4 else (3, 2, 1) if form == 'max' else (2, 2, 0)
+    gen = generator('fused-pool', form, case)
+    v = fused_pool_vectors(c, gen)
+    x = ints((n, c, h, w), X, gen)
+    g = ints((n, c, pool_out(h, k, s, p), pool_out(w, k, s, p)), X, gen)
+    old = distinct((2, c), gen)
+    problem = dict(x=x, g=g, v=v, old_gamma=old[0], old_beta=old[1], geometry=(k, s, p))
+    if form == 'max':
+        problem['y'], problem['index'] = bn_relu_maxpool_ref(x, v, k, s, p)
+        gx, g_gamma, g_beta = bn_relu_maxpool_bwd_ref(g, problem['index'], x, v)
+    else:
+        problem['y'], problem['index'] = bn_relu_avgpool2_ref(x, v), None
+        gx, g_gamma, g_beta = bn_relu_avgpool2_bwd_ref(g, x, v)
+    problem.update(gx=gx, g_gamma=g_gamma + old[0], g_beta=g_beta + old[1],
+                   magnitudes=fused_pool_magnitudes(form, g, problem['index'], x, v, old[0], old[1]))
+    return problem
+
+
+def fused_pool_random_problem(form, case):
+    """Full-mantissa operands (randn) for the repeatability test: no result is exact, only its bits from run to run matter
+    (the arg-max of the max form is the fused forward's own, taken on the device)."""
+    n, c, h, w = case
+    gen = generator('fused-pool-random', form, case)
+    k, s, p = (3, 2, 1) if form == 'max' else (2, 2, 0)
+    v = dict(mean=torch.randn(c, generator=gen) * 0.3, inv_std=(torch.rand(c, generator=gen) + 0.5).rsqrt(),
+             gamma=torch.randn(c, generator=gen), beta=torch.randn(c, generator=gen) * 0.3)
+    x = torch.randn(n, c, h, w, generator=gen)
+    g = torch.randn(n, c, pool_out(h, k, s, p), pool_out(w, k, s, p), generator=gen)
+    return dict(x=x.double(), g=g.double(), v={key: value.double() for key, value in v.items()}, geometry=(k, s, p),
+                old_gamma=torch.randn(c, generator=gen).double(), old_beta=torch.randn(c, generator=gen).double())
 
 
 def adam_ref(p, g, m, v, step, weight_decay, dtype=torch.float64, lr=ADAM['lr'], beta1=ADAM['beta1'], beta2=ADAM['beta2'],

@@ -805,7 +805,7 @@ def test_crowd_density_label_variants(F):
 def test_fused_stem_norm_relu_pool(F, shape):
     """functional.bn_relu_max_pool2d (norm0 -> relu0 -> pool0 in one pass each way) against the two-op form: output,
     first-order gradients of x / gamma / beta, and the recorded (gradient-penalty) route through it."""
-    from srgan_amd.tape import backward
+    from srgan_amd.tape import Var, backward
     gen = torch.Generator().manual_seed(41)
     n, c, h, w = shape
     x_host = torch.randn(n, c, h, w, generator=gen)
@@ -827,6 +827,15 @@ def test_fused_stem_norm_relu_pool(F, shape):
         y = forward(x)
         backward(y, grad=F.leaf(dev(cotangent)))
         first = (y.cpu(), x.grad.cpu(), gamma.grad.cpu(), beta.grad.cpu())
+        # the same cotangent arriving as a channel slice of a wider tensor (the root's cotangent reaches the op as the caller
+        # made it): the same gradients, bit for bit
+        wide = dev(torch.cat([torch.full((n, 1, oh, ow), 1e3), cotangent, torch.full((n, 2, oh, ow), -1e3)], dim=1))
+        assert not wide[:, 1:1 + c].is_contiguous()
+        x1 = F.leaf(dev(x_host), requires_grad=True)
+        gamma.grad = beta.grad = None
+        backward(forward(x1), grad=Var(wide[:, 1:1 + c]))
+        for got, want, what in zip((x1.grad.cpu(), gamma.grad.cpu(), beta.grad.cpu()), first[1:], ('input', 'gamma', 'beta')):
+            assert torch.equal(got, want), f'fused={fused_form}: {what} gradient from a strided cotangent'
         # second order: a function of the recorded input gradient, back to gamma and x
         x2 = F.leaf(dev(x_host), requires_grad=True)
         gamma.grad = beta.grad = None

@@ -1,7 +1,9 @@
 """The tables and references of the streaming-kernel tests (streaming_cases.py) on the CPU, no library needed: every float64
 reference agrees with torch's own fp32 op to fp32 rounding, the exact-operand cases meet their precondition, and every table
 entry reaches the branch it is named for -- re-derived from the hosts' constants, so that a changed constant (or an edited
-table) fails here instead of quietly un-covering a kernel."""
+table) fails here instead of quietly un-covering a kernel.  That holds for all of pool.hip too: the fused norm -> relu -> pool
+references against torch's autograd in float64, the workgroups per plane and the ordered / atomic choice of every fused case,
+and the kernel srgan_maxpool2d_bwd takes at every window alignment."""
 import math
 
 import pytest
@@ -156,6 +158,52 @@ def test_pooling_references_agree_with_torch():
         g = S.ints(y.shape, S.X, gen)
         y.backward(g)
         assert torch.allclose(S.avgpool_bwd_ref(g, k, h, w), x.grad, rtol=1e-15, atol=0)
+        assert torch.equal(S.avgpool_ref(x.detach(), k), S.avgpool_ref(x.detach(), k, k))            # the stride argument: s = k as before
+        assert torch.equal(S.avgpool_bwd_ref(g, k, h, w), S.avgpool_bwd_ref(g, k, h, w, k))
+        assert torch.equal(S.avgpool_ref(x.detach(), k), x.detach().unfold(1, k, k).unfold(2, k, k).sum(dim=(3, 4)) / (k * k))
+    for (planes, h, w, k, s) in S.AVGPOOL_STRIDED:
+        gen = S.generator('avg', planes, h, w, k, s)
+        x = S.ints((planes, h, w), S.X, gen).requires_grad_(True)
+        y = TF.avg_pool2d(x.unsqueeze(0), k, s)[0]
+        assert y.shape[1:] == (S.pool_out(h, k, s), S.pool_out(w, k, s))
+        assert torch.allclose(S.avgpool_ref(x.detach(), k, s), y.detach(), rtol=1e-15, atol=0)
+        g = S.ints(y.shape, S.X, gen)
+        y.backward(g)
+        # (k = 3: torch adds the ninths, the reference divides the sum: float64 roundings of a sum that may cancel)
+        assert torch.allclose(S.avgpool_bwd_ref(g, k, h, w, s), x.grad, rtol=1e-15, atol=0 if k == 2 else 1e-15)
+
+
+def fused_cases():
+    return [('max', case) for case in S.FUSED_MAX_FWD + S.FUSED_MAX_BWD + S.FUSED_MAX_SEQUENCE] + \
+        [('avg', case) for case in S.FUSED_AVG + S.FUSED_AVG_SEQUENCE]
+
+
+def test_fused_pool_references_agree_with_torch_autograd():
+    """max_pool2d(relu(batch_norm(x))) and avg_pool2d(relu(batch_norm(x)), 2, 2) in float64 on the CPU, with the gradients to x,
+    gamma and beta: on the dyadic operands every float64 operation is exact, so the references EQUAL torch's."""
+    for form, case in fused_cases():
+        problem = S.fused_pool_problem(form, case)
+        v, (k, s, p) = problem['v'], problem['geometry']
+        x = problem['x'].clone().requires_grad_(True)
+        gamma, beta = v['gamma'].clone().requires_grad_(True), v['beta'].clone().requires_grad_(True)
+        variance = 1.0 / v['inv_std'] ** 2                             # eps below half an ulp of it: inv_std IS 1 / sqrt(var)
+        activated = TF.batch_norm(x, v['mean'], variance, gamma, beta, training=False, eps=1e-30).relu()
+        if form == 'max':
+            y, index = TF.max_pool2d(activated, k, s, p, return_indices=True)
+            assert torch.equal(problem['index'], index), (form, case)
+        else:
+            y = TF.avg_pool2d(activated, 2, 2)
+        assert torch.equal(problem['y'], y.detach()), (form, case)
+        y.backward(problem['g'])
+        assert torch.equal(problem['gx'], x.grad), (form, case)
+        assert torch.equal(problem['g_gamma'] - problem['old_gamma'], gamma.grad), (form, case)
+        assert torch.equal(problem['g_beta'] - problem['old_beta'], beta.grad), (form, case)
+        if form == 'max' and (k, s, p) == (3, 2, 1):                     # maxpool_bwd_ref IS the scatter, per plane
+            n, c, h, w = case[:4]
+            unmasked = S.maxpool_bwd_ref(problem['g'].reshape(n * c, *y.shape[2:]), problem['index'].reshape(n * c, *y.shape[2:]), h, w)
+            leaf = activated.detach().clone().requires_grad_(True)
+            TF.max_pool2d(leaf, k, s, p).backward(problem['g'])
+            assert torch.equal(unmasked.reshape(n, c, h, w), leaf.grad), (form, case)
 
 
 def test_adam_reference_agrees_with_torch_adam():
@@ -196,6 +244,43 @@ def test_exact_cases_meet_their_precondition():
     for (planes, h, w, k) in S.AVGPOOL:
         if k != 3:
             S.assert_exact_limit(3 * k * k, int(math.log2(k * k)), f'avgpool {k}')
+    for (planes, h, w, k, s) in S.AVGPOOL_STRIDED:
+        if k != 3:                     # forward: k^2 integers; backward: at most ceil(k / s)^2 cotangents per pixel; both times 1 / k^2
+            S.assert_exact_limit(3 * k * k, int(math.log2(k * k)), f'avgpool {k} / {s}')
+            S.assert_exact_limit(3 * (-(-k // s)) ** 2, int(math.log2(k * k)), f'avgpool {k} / {s} backward')
+
+
+def test_fused_pool_cases_meet_their_precondition():
+    """Per output the sum of absolute values (old contents included) below 2^(24 - f), f = the output's fractional bits: a
+    multiple of 1/4, b and fma(x, a, b) of 1/16; S an integer (max form) or a multiple of 1/4 (average form: the 0.25 adds two
+    bits everywhere); gx = S * a two more, g_gamma = inv_std * sum S * (x - mean) three more.  Every case has a channel with
+    negative gamma, and the tables reach the mask's borderline bn(x) == 0 under a non-zero pooled gradient."""
+    borderline = {'max': 0, 'avg': 0}
+    for form, case in fused_cases():
+        problem = S.fused_pool_problem(form, case)
+        v, x = problem['v'], problem['x']
+        assert bool((v['gamma'] < 0).any()), (form, case)
+        assert bool((v['gamma'] != 0).all()) and bool((v['inv_std'] > 0).all())
+        for name, bits in S.FUSED_POOL_FRACTION_BITS[form].items():
+            S.assert_exact_limit(problem['magnitudes'][name], bits, f'fused {form} pool {case} {name}')
+            unit = 2.0 ** -bits
+            assert torch.equal(problem[name] / unit, (problem[name] / unit).round()), (form, case, name)     # the bits are enough
+        assert torch.equal(S.batch_norm_eval_ref(x, v) * 16, (S.batch_norm_eval_ref(x, v) * 16).round())
+        # the worst case whatever the draw: |x| <= 3, |a| <= 4, |b| <= 2 + 2 * 4, |S| <= 4 * 3 (max: four windows) or 3 / 4
+        n, c, h, w = case[:4]
+        per_pixel = 12 if form == 'max' else 0.75
+        S.assert_exact_limit(per_pixel * 5 * 2 * n * h * w + c, S.FUSED_POOL_FRACTION_BITS[form]['g_gamma'], f'fused {form} pool {case} (worst case)')
+        if form == 'avg' or problem['geometry'] == (3, 2, 1):
+            pooled = problem['gx'] / (v['inv_std'] * v['gamma']).view(1, -1, 1, 1)
+            zero_norm = S.batch_norm_eval_ref(x, v) == 0
+            assert bool((pooled[zero_norm] == 0).all())                              # masked: `> 0`
+            raw = (S.maxpool_bwd_ref(problem['g'].reshape(n * c, *problem['g'].shape[2:]), problem['index'].reshape(n * c, *problem['g'].shape[2:]), h, w)
+                   .reshape(n, c, h, w) if form == 'max' else problem['g'].repeat_interleave(2, dim=2).repeat_interleave(2, dim=3))
+            hits = int((zero_norm & (raw != 0)).sum())
+            borderline[form] += hits
+            if form == 'avg' and n * h * w >= 64:
+                assert hits > 0, (form, case)
+    assert borderline['max'] > 0 and borderline['avg'] > 0, borderline
 
 
 # ------------------------------------------------------------------------------------------------- branches
@@ -266,6 +351,65 @@ def test_small_kernels_tables():
     assert {case['accumulate'] for case in S.COPY_CHANNELS} == {0, 1}
 
 
+def test_fused_pool_shapes_reach_every_workgroup_count_and_both_finishes():
+    """(workgroups per plane, thread items in the last, ordered | atomic in the default mode) of every fused case."""
+    grid = {case: S.fused_pool_grid('max', *case) for case in S.FUSED_MAX_BWD}
+    assert grid[(1, 1, 1, 4)] == (1, 1, 'ordered')                                  # the smallest plane: one float4
+    assert grid[(2, 3, 8, 4)] == (1, 8, 'ordered') and grid[(3, 5, 15, 20)] == (1, 75, 'ordered') and 15 % 2 == 1
+    assert grid[(2, 3, 32, 128)] == (1, S.POOL_BWD_QUADS, 'ordered')                # exactly one full workgroup
+    assert grid[(2, 3, 41, 100)] == (2, 1, 'ordered')                               # the second holds one quad
+    assert grid[(3, 2, 80, 64)] == (2, 256, 'ordered')
+    assert grid[(1, 4096, 2, 4)] == (1, 2, 'ordered') and grid[(1, 4097, 2, 4)] == (1, 2, 'atomic')
+    assert grid[(1, 65535, 1, 4)] == (1, 1, 'atomic')
+    assert S.ROW_FINISH_ROWS == 4096 and S.POOL_MAX_PLANES == 65535
+    grid = {case: S.fused_pool_grid('avg', *case) for case in S.FUSED_AVG}
+    assert grid[(1, 1, 2, 4)] == (1, 1, 'ordered') and grid[(2, 3, 6, 8)] == (1, 6, 'ordered') and grid[(3, 5, 10, 12)] == (1, 15, 'ordered')
+    assert grid[(2, 3, 64, 128)] == (1, S.POOL_BWD_QUADS, 'ordered') and grid[(2, 3, 50, 164)] == (2, 1, 'ordered')
+    assert grid[(3, 2, 80, 128)] == (2, 256, 'ordered')
+    assert grid[(1, 4096, 2, 4)] == (1, 1, 'ordered') and grid[(1, 4097, 2, 4)] == (1, 1, 'atomic')
+    for case in S.FUSED_MAX_BWD + S.FUSED_MAX_SEQUENCE:
+        assert S.fused_max_bwd_supported(*case, 3, 2, 1), case
+    for case in S.FUSED_AVG + S.FUSED_AVG_SEQUENCE:
+        assert S.fused_avg_supported(*case), case
+    # several parts per channel (images x workgroups per plane) is what ordered_row_finish needs to do anything at all
+    assert max(S.fused_pool_parts('max', *case) for case in S.FUSED_MAX_BWD) == 6
+    assert max(S.fused_pool_parts('avg', *case) for case in S.FUSED_AVG) == 6
+    # back to back: the parts per channel go 2, 6, 1, 2 with another C, N and plane every time
+    for form, sequence in (('max', S.FUSED_MAX_SEQUENCE), ('avg', S.FUSED_AVG_SEQUENCE)):
+        assert [S.fused_pool_parts(form, *case) for case in sequence] == [2, 6, 1, 2]
+        assert all(a[1] != b[1] and a[2:] != b[2:] for a, b in zip(sequence, sequence[1:]))
+        assert len({case[0] for case in sequence}) > 1
+        assert all(S.fused_pool_grid(form, *case)[2] == 'ordered' for case in sequence)
+    for form, cases in S.FUSED_REPEAT.items():
+        assert all(S.fused_pool_grid(form, *case)[0] > 1 and S.fused_pool_grid(form, *case)[2] == 'ordered' for case in cases)
+    # the fused forward: every geometry of the plain max pool, C coprime to N and to the plane
+    assert {case[4:] for case in S.FUSED_MAX_FWD} == {(3, 2, 1), (2, 2, 0), (3, 1, 1), (3, 3, 0)}
+    assert all(c > 1 and c % 2 == 1 for _, c, *_ in S.FUSED_MAX_FWD)
+
+
+def test_maxpool_backward_cases_reach_the_three_kernels():
+    """srgan_maxpool2d_bwd: the two four-pixels-per-thread kernels, the scalar gather kernel, and the scalar kernel again
+    wherever a W % 4 == 0 case has its gx 1, 2 or 3 floats off a 16-byte boundary."""
+    labels = {case: S.maxpool_bwd_path(case[2], *case[3:]) for case in S.MAXPOOL}
+    assert set(labels.values()) == {'quad321', 'quad220', 'scalar'}
+    assert labels[(12, 16, 16, 3, 2, 1)] == labels[(12, 15, 20, 3, 2, 1)] == labels[(12, 8, 4, 3, 2, 1)] == 'quad321'
+    assert labels[(12, 12, 8, 2, 2, 0)] == 'quad220'
+    assert labels[(10, 13, 11, 3, 2, 1)] == labels[(10, 13, 11, 2, 2, 0)] == labels[(12, 12, 10, 2, 2, 0)] == 'scalar'       # W % 4 != 0
+    assert labels[(12, 9, 7, 3, 1, 1)] == labels[(12, 10, 11, 3, 3, 0)] == labels[(12, 5, 6, 2, 1, 0)] == 'scalar'
+    for case, label in labels.items():
+        if case[2] % 4 == 0:
+            assert label != 'scalar' and all(S.maxpool_bwd_path(case[2], *case[3:], offset) == 'scalar' for offset in (1, 2, 3))
+    assert any(planes * h * (w // 4) > S.THREADS for planes, h, w, k, s, p in S.MAXPOOL if w % 4 == 0)      # more than one workgroup
+    # the windows of a row that one float4 (w0 % 4 == 0) can meet: 3 (3 / 2 / 1) and 2 (2 / 2 / 0).  The kernels' SPAN -- 4 and 3 -- is
+    # an upper bound with one to spare: a loop of SPAN - 1 computes the same values, one of SPAN - 2 loses a window (and fails the cases)
+    for (k, s, p), span in (((3, 2, 1), 4), ((2, 2, 0), 3)):
+        assert (3 + p) // s - ((p - k + 1 + s - 1) // s if p - k + 1 > 0 else 0) + 2 == span
+        met = {sum(any(ow * s - p <= w < ow * s - p + k for w in range(w0, w0 + 4)) for ow in range(64)) for w0 in range(0, 64, 4)}
+        assert max(met) == span - 1, (k, s, p, met)
+    assert {(w % 4 == 0, k, s) for _, _, w, k, s in S.AVGPOOL_STRIDED} == {(True, 3, 1), (False, 3, 2), (False, 2, 1), (True, 3, 2)}
+    assert all(s < k for _, _, _, k, s in S.AVGPOOL_STRIDED)                                               # overlapping windows
+
+
 def test_transcendental_bounds_are_the_documented_ones():
     """max(2, 4 x torch's CPU fp32 error against float64 on the same inputs) + the formula's further roundings."""
     for name in S.TRANSCENDENTAL:
@@ -283,7 +427,14 @@ def test_constants_mirror_the_kernel_sources():
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'sr-gan_amd', 'csrc')
-    text = {name: open(os.path.join(csrc, name)).read() for name in ('elementwise.hip', 'reduce.hip', 'common.h')}
+    text = {name: open(os.path.join(csrc, name)).read() for name in ('elementwise.hip', 'reduce.hip', 'common.h', 'pool.hip', 'split_finish.h')}
+    assert f'constexpr int POOL_BWD_QUADS = {S.POOL_BWD_QUADS};' in text['pool.hip']
+    assert f'constexpr int ROW_FINISH_ROWS = {S.ROW_FINISH_ROWS};' in text['split_finish.h']
+    assert 'if (split_atomics_forced() || rows > ROW_FINISH_ROWS || parts < 1) return nullptr;' in text['split_finish.h']
+    assert text['pool.hip'].count(f'(int64_t)N * C <= {S.POOL_MAX_PLANES}') == 2            # both `_supported` predicates
+    assert text['pool.hip'].count('(plane_quads + POOL_BWD_QUADS - 1) / POOL_BWD_QUADS') == 1
+    assert text['pool.hip'].count('(items + POOL_BWD_QUADS - 1) / POOL_BWD_QUADS') == 2
+    assert 'if (W % 4 == 0 && ((uintptr_t)gx & 15) == 0 && n < ((int64_t)1 << 31)) {\n    const uint32_t quads' in text['pool.hip']
 
     def product(expression):
         value = 1
