@@ -10,11 +10,27 @@
 // hardware's 16-bit transpose read: 16 lanes fetch a 4-pixel x 16-channel block and every lane receives four consecutive
 // pixels of its own channel.  Channels beyond C inside the last group are stored as zeros (the packed weights are zero
 // there too, so they never contribute).  A [N, F] matrix is the H = W = 1 case: plain row-major.
+//
+// The host side of a blocked kernel: its entry point checks the dtype with check_precision<codes the family has>, takes the
+// slot arithmetic from slot_channels / channel_groups (precision_dispatch.h: HGroup below is the same constant for the
+// device) and launches through launch_for_precision<the same codes>, which hands the code to the kernel's PREC parameter and
+// instantiates the listed codes only.  A kernel with more than 64 KB of dynamic LDS asks for it with allow_dynamic_lds (common.h).
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "precision_dispatch.h"
 
 namespace srgan {
+
+static_assert(PRECISION_EINVAL == SRGAN_EINVAL, "precision_dispatch.h reports the C ABI's invalid-argument status");
+
+// The launch a blocked entry point ends in: functor(std::integral_constant<int, CODE>{}) for CODE == dtype enqueues the
+// kernel(s); the launch status, or SRGAN_EINVAL for a dtype outside the list (check_precision with no code accepts nothing).
+template <int... CODES, class Functor>
+int launch_for_precision(int dtype, Functor&& functor) {
+  if (!for_precision<CODES...>(dtype, functor)) return check_precision<>(dtype, "blocked kernel launch");
+  return launch_status();
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 h_bf16x8 __attribute__((ext_vector_type(8)));
@@ -65,7 +81,7 @@ __device__ __forceinline__ Slot h_pack8(const float (&f)[8]) {
 // ([N][ceil(C / 4)][H][W][4] floats): the exact path of the 4x4 / stride 2 family (blocked16_k4s2.hip) -- the fp32 gradient-
 // penalty chain of the fp16 configuration and the crowd generator -- where v_mfma_f32_32x32x2_f32 takes one float per lane
 // and a slot feeds four matrix instructions.
-template <int PREC> struct HGroup { static constexpr int N = PREC == 0 ? 4 : 8; };
+template <int PREC> struct HGroup { static constexpr int N = slot_channels(PREC); };
 template <int PREC>
 __device__ __forceinline__ void h_unpack(const Slot& s, float (&f)[HGroup<PREC>::N]) {
   if constexpr (PREC == 0) {

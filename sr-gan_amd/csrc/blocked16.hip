@@ -18,7 +18,6 @@
 #include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
-#include <atomic>
 
 namespace srgan {
 
@@ -738,16 +737,8 @@ static int hconv3_dma_launch_one(const HConv3Params& p, dim3 grid, hipStream_t s
   constexpr int PATCH_I = (2 * IMG * PLANE + 63) / 64, T = PATCH_I + 18, TP = (T + 3) / 4 * 4;
   constexpr int bytes = RING * TP * 64 * 16;
   static_assert(bytes <= 160 * 1024, "the ring fits the CU's LDS");
-  auto kernel = hconv3x3_dma_kernel<64, NI, TW, ROWS, PREC, RING>;
-  // more than 64 KB of dynamic LDS needs the attribute, once per kernel and device (as pointwise_ring.hip)
-  static std::atomic<uint64_t> configured_devices{0};
-  int device = 0;
-  SRGAN_HIP(hipGetDevice(&device));
-  const uint64_t bit = (uint64_t)1 << (device & 63);
-  if (!(configured_devices.load(std::memory_order_acquire) & bit)) {
-    SRGAN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    configured_devices.fetch_or(bit, std::memory_order_release);
-  }
+  constexpr auto kernel = hconv3x3_dma_kernel<64, NI, TW, ROWS, PREC, RING>;
+  SRGAN_HIP(allow_dynamic_lds<kernel>(bytes));
   hipLaunchKernelGGL(kernel, grid, dim3(256), bytes, stream, p, zero);
   return SRGAN_OK;
 }
@@ -965,14 +956,15 @@ __global__ __launch_bounds__(256) void hwgrad3x3_finish_kernel(const float* __re
   }
 }
 
-static int check_dtype(int dtype) {
-  SRGAN_REQUIRE(dtype == 1 || dtype == 2, SRGAN_EINVAL, "blocked 16-bit tensors are bf16 (1) or fp16 (2)");
-  return SRGAN_OK;
+template <int TW, int ROWS, int PREC>
+static void hwgrad3_launch(const HWgrad3Params& p, int mb, dim3 grid, hipStream_t stream) {
+  if (mb == 4) hipLaunchKernelGGL((hwgrad3x3_kernel<TW, ROWS, PREC, 4>), grid, dim3(512), 0, stream, p);
+  else hipLaunchKernelGGL((hwgrad3x3_kernel<TW, ROWS, PREC, 2>), grid, dim3(256), 0, stream, p);
 }
-static int check_dtype_or_f32(int dtype) {        // the layout conversions and sums also take dtype 0: fp32, four channels per slot
-  SRGAN_REQUIRE(dtype >= 0 && dtype <= 2, SRGAN_EINVAL, "blocked tensors are fp32 (0), bf16 (1) or fp16 (2)");
-  return SRGAN_OK;
-}
+
+static const char* const H16_ONLY = "blocked 16-bit tensors are bf16 (1) or fp16 (2)";
+// the layout conversions and sums also take dtype 0: fp32, four channels per slot
+static const char* const H16_OR_F32 = "blocked tensors are fp32 (0), bf16 (1) or fp16 (2)";
 
 // the job (= the single-layer kernel's arguments) of one conv-weight operand; transposed: rows = C, taps mirrored
 static void conv_weights_job(HPackJob& job, const float* w, void* packed, int32_t K, int32_t C, int32_t R, int32_t S, int transposed,
@@ -1011,50 +1003,47 @@ extern "C" {
 int srgan_h_pack(const float* x, void* out, const void* mask_ref, float slope, int32_t N, int32_t C, int64_t HW, int dtype,
                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_or_f32(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H16_OR_F32)) return status;
   SRGAN_REQUIRE(x && out && N >= 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_pack arguments");
-  const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
+  const int CG = channel_groups(C, dtype);
   const int64_t slots = (int64_t)N * CG * HW;
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_pack_kernel<0>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
-  else if (dtype == 1) hipLaunchKernelGGL(h_pack_kernel<1>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
-  else hipLaunchKernelGGL(h_pack_kernel<2>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
-  return launch_status();
+  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_pack_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, x, (Slot*)out, (const Slot*)mask_ref, slope, slots, C, CG, (int32_t)HW);
+  });
 }
 
 int srgan_h_unpack(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_or_f32(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H16_OR_F32)) return status;
   SRGAN_REQUIRE(x && out && N >= 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_unpack arguments");
-  const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
+  const int CG = channel_groups(C, dtype);
   const int64_t slots = (int64_t)N * CG * HW;
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_unpack_kernel<0>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
-  else if (dtype == 1) hipLaunchKernelGGL(h_unpack_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
-  else hipLaunchKernelGGL(h_unpack_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
-  return launch_status();
+  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_unpack_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, (const Slot*)x, out, slots, C, CG, (int32_t)HW);
+  });
 }
 
 int srgan_h_add(const void* a, const void* b, void* out, int64_t slots, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_or_f32(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H16_OR_F32)) return status;
   SRGAN_REQUIRE(a && b && out && slots >= 0, SRGAN_EINVAL, "srgan_h_add arguments");
   if (slots == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(slots, 256));
-  if (dtype == 0) hipLaunchKernelGGL(h_add_kernel<0>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
-  else if (dtype == 1) hipLaunchKernelGGL(h_add_kernel<1>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
-  else hipLaunchKernelGGL(h_add_kernel<2>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
-  return launch_status();
+  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_add_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, (const Slot*)a, (const Slot*)b, (Slot*)out, slots);
+  });
 }
 
 // out[c] += sum over n and pixels of x[n, c, pixel]   (c < C; fp32; the bias gradient of a fused convolution / linear layer)
 int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_or_f32(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H16_OR_F32)) return status;
   SRGAN_REQUIRE(x && out && N > 0 && C > 0 && HW > 0 && HW < ((int64_t)1 << 31), SRGAN_EINVAL, "srgan_h_channel_sums arguments");
-  const int group = dtype == 0 ? 4 : 8, CG = (C + group - 1) / group;
+  const int CG = channel_groups(C, dtype);
   const int64_t per_group = (int64_t)N * HW;
   int parts = (int)((per_group + 4095) / 4096);
   if (parts > 256) parts = 256;
@@ -1068,46 +1057,42 @@ int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_
   }
   SRGAN_REQUIRE(part, SRGAN_EINVAL, "srgan_h_channel_sums: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)CG, (unsigned)parts);
-  if (dtype == 0) hipLaunchKernelGGL(h_channel_sums_kernel<0>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  else if (dtype == 1) hipLaunchKernelGGL(h_channel_sums_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  else hipLaunchKernelGGL(h_channel_sums_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
-  if (!tickets) hipLaunchKernelGGL(h_channel_sums_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, out, C, parts, group);
-  return launch_status();
+  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_channel_sums_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, (const Slot*)x, part, N, CG, (int32_t)HW, parts, tickets, out, C);
+    if (!tickets) hipLaunchKernelGGL(h_channel_sums_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, out, C, parts, slot_channels(dtype));
+  });
 }
 
 // mode 0: out = maxpool2x2(x); mode 2: out = `g` gathered at the arg-max of x (both [planes][H/2][W/2] slots, planes = N * groups)
 int srgan_h_maxpool2(const void* x, const void* g, void* out, int64_t planes, int32_t H, int32_t W, int mode, int dtype,
                      void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(x && out && planes >= 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && (mode == 0 || (mode == 2 && g)),
                 SRGAN_EINVAL, "srgan_h_maxpool2 arguments (even planes; mode 0 or 2)");
   const int64_t total = planes * (H / 2) * (W / 2);
   if (total == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(total, 256));
-  if (dtype == 1) {
-    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<1, 0>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-    else hipLaunchKernelGGL((h_maxpool_kernel<1, 2>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<2, 0>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-    else hipLaunchKernelGGL((h_maxpool_kernel<2, 2>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
-  }
-  return launch_status();
+  return launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    constexpr int PREC = decltype(prec)::value;
+    if (mode == 0) hipLaunchKernelGGL((h_maxpool_kernel<PREC, 0>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+    else hipLaunchKernelGGL((h_maxpool_kernel<PREC, 2>), grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)g, (Slot*)out, planes, H, W);
+  });
 }
 
 // gx (shape of x) = gp placed at the arg-max of x, times mask(x, slope) when `masked`
 int srgan_h_maxpool2_bwd(const void* x, const void* gp, void* gx, int64_t planes, int32_t H, int32_t W, int masked, float slope,
                          int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(x && gp && gx && planes >= 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, SRGAN_EINVAL,
                 "srgan_h_maxpool2_bwd arguments");
   const int64_t total = planes * (H / 2) * (W / 2);
   if (total == 0) return SRGAN_OK;
   const dim3 grid(stream_grid(total, 256));
-  if (dtype == 1) hipLaunchKernelGGL(h_maxpool_bwd_kernel<1>, grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
-  else hipLaunchKernelGGL(h_maxpool_bwd_kernel<2>, grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
-  return launch_status();
+  return launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_maxpool_bwd_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, (const Slot*)x, (const Slot*)gp, (Slot*)gx, planes, H, W, masked, slope);
+  });
 }
 
 // Slots of a packed convolution weight tensor of CO rows, CI reduced channels and R x S taps.
@@ -1120,15 +1105,15 @@ int64_t srgan_h_conv_weight_slots(int32_t CO, int32_t CI, int32_t R, int32_t S) 
 int srgan_h_pack_conv_weights(const float* w, void* packed, int32_t K, int32_t C, int32_t R, int32_t S, int transposed, int dtype,
                               void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(w && packed && K > 0 && C > 0 && R > 0 && S > 0, SRGAN_EINVAL, "srgan_h_pack_conv_weights arguments");
   HPackJob job;
   conv_weights_job(job, w, packed, K, C, R, S, transposed, dtype);
   const dim3 grid((unsigned)((job.slots + 255) / 256));
   const int32_t* q = job.p;
-  if (dtype == 1) hipLaunchKernelGGL(h_pack_conv_weights_kernel<1>, grid, dim3(256), 0, s, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
-  else hipLaunchKernelGGL(h_pack_conv_weights_kernel<2>, grid, dim3(256), 0, s, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
-  return launch_status();
+  return launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_pack_conv_weights_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, w, (Slot*)packed, job.slots, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  });
 }
 
 // ---- the batched form: the caller keeps a device array of jobs (srgan_h_pack_job_bytes() each), filled on the host by the two
@@ -1138,7 +1123,7 @@ int32_t srgan_h_pack_job_bytes(void) { return (int32_t)sizeof(HPackJob); }
 
 int64_t srgan_h_pack_job_conv_weights(void* jobs, int64_t first_block, const float* w, void* packed, int32_t K, int32_t C, int32_t R,
                                       int32_t S, int transposed, int dtype) {
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(jobs && first_block >= 0 && w && packed && K > 0 && C > 0 && R > 0 && S > 0, SRGAN_EINVAL,
                 "srgan_h_pack_job_conv_weights arguments");
   HPackJob job;
@@ -1150,7 +1135,7 @@ int64_t srgan_h_pack_job_conv_weights(void* jobs, int64_t first_block, const flo
 
 int64_t srgan_h_pack_job_k4s2_weights(void* jobs, int64_t first_block, const float* w, void* packed, int32_t A, int32_t B,
                                       int direction, int dtype, int32_t* jobs_written) {
-  SRGAN_REQUIRE(dtype >= 0 && dtype <= 2, SRGAN_EINVAL, "srgan_h_pack_job_k4s2_weights dtype");
+  if (const int status = check_precision<0, 1, 2>(dtype, "srgan_h_pack_job_k4s2_weights dtype")) return status;
   SRGAN_REQUIRE(jobs && first_block >= 0 && w && packed && A > 0 && B > 0 && (direction == 0 || direction == 1) && jobs_written,
                 SRGAN_EINVAL, "srgan_h_pack_job_k4s2_weights arguments");
   const int64_t slots = srgan_h_k4s2_weight_slots(A, B, direction, dtype) / (direction ? 4 : 1);
@@ -1176,7 +1161,7 @@ int64_t srgan_h_pack_job_k4s2_weights(void* jobs, int64_t first_block, const flo
 int64_t srgan_h_pack_job_matrix(void* jobs, int64_t first_block, const float* src, void* out, int64_t rows, int64_t cols,
                                 int64_t rows_real, int64_t cols_real, int64_t row_stride, int64_t col_stride, int32_t row_plane,
                                 int32_t col_plane, int dtype) {
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   const int64_t limit = (int64_t)1 << 31;
   SRGAN_REQUIRE(jobs && first_block >= 0 && src && out && rows > 0 && cols > 0 && rows < limit && cols < limit && rows_real >= 0 &&
                 rows_real < limit && cols_real >= 0 && cols_real < limit && row_stride > 0 && row_stride < limit && col_stride > 0 &&
@@ -1256,7 +1241,7 @@ int srgan_h_pack_batched(const void* jobs_device, int32_t count, int64_t blocks,
 int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
                     int32_t N, int32_t C_in, int32_t C_out, int32_t rows, int32_t H, int32_t W, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && C_out > 0 && rows > 0 && H > 0 && W > 0 && epi >= 0 && epi <= 2 &&
                 (epi != 2 || ref), SRGAN_EINVAL, "srgan_h_conv3x3 arguments");
   HConv3Params p;
@@ -1297,17 +1282,18 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
   const Slot* zero = (ring == 2 || ring == 3) && split == 1 && plan.bm == 64
                          ? h_zero_slots() : nullptr;
   const int slot = profile_bracket_begin(s);
-  if (zero) {
-    int launched;
-    if (ring == 3) launched = dtype == 1 ? hconv3_dma_launch<1, 3>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 3>(p, plan, grid, s, zero);
-    else launched = dtype == 1 ? hconv3_dma_launch<1, 2>(p, plan, grid, s, zero) : hconv3_dma_launch<2, 2>(p, plan, grid, s, zero);
-    if (launched != SRGAN_OK) {
-      profile_bracket_end(slot, s, 0, 0, 0, 14, plan.bm, plan.ni * 128, split);      // close the bracket this call opened
-      return launched;
-    }
+  int launched = SRGAN_OK;
+  if (!for_precision<1, 2>(dtype, [&](auto prec) {
+        constexpr int PREC = decltype(prec)::value;
+        if (!zero) hconv3_launch<PREC>(p, plan, grid, s);
+        else if (ring == 3) launched = hconv3_dma_launch<PREC, 3>(p, plan, grid, s, zero);
+        else launched = hconv3_dma_launch<PREC, 2>(p, plan, grid, s, zero);
+      }))
+    launched = check_precision<>(dtype, "srgan_h_conv3x3 launch");
+  if (launched != SRGAN_OK) {
+    profile_bracket_end(slot, s, 0, 0, 0, 14, plan.bm, plan.ni * 128, split);      // close the bracket this call opened
+    return launched;
   }
-  else if (dtype == 1) hconv3_launch<1>(p, plan, grid, s);
-  else hconv3_launch<2>(p, plan, grid, s);
   const int status = launch_status();
   const double pixels = (double)N * H * W;
   profile_bracket_end_bytes(slot, s, rows_needed, (int64_t)pixels, (int64_t)p.CGI * 8 * 9, 14, plan.bm, plan.ni * 128, split,
@@ -1319,7 +1305,7 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
 int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, int32_t C_in, int32_t C_out, int32_t H, int32_t W,
                           int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(x && gy && gw && N > 0 && C_in > 0 && C_out > 0 && H > 0 && W > 0, SRGAN_EINVAL, "srgan_h_conv3x3_wgrad arguments");
   HWgrad3Params p;
   p.x = (const Slot*)x; p.gy = (const Slot*)gy;
@@ -1353,25 +1339,16 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
   SRGAN_REQUIRE(p.partial, SRGAN_EINVAL, "srgan_h_conv3x3_wgrad: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)blocks, (unsigned)walkers);
   const int slot = profile_bracket_begin(s);
-#define HWGRAD_LAUNCH(TWv, ROWSv)                                                                                       \
-  do {                                                                                                                  \
-    if (mb == 4) {                                                                                                      \
-      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 4>), grid, dim3(512), 0, s, p);               \
-      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 4>), grid, dim3(512), 0, s, p);                          \
-    } else {                                                                                                            \
-      if (dtype == 1) hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 1, 2>), grid, dim3(256), 0, s, p);               \
-      else hipLaunchKernelGGL((hwgrad3x3_kernel<TWv, ROWSv, 2, 2>), grid, dim3(256), 0, s, p);                          \
-    }                                                                                                                   \
-  } while (0)
-  if (tw == 32) HWGRAD_LAUNCH(32, 2);
-  else if (tw == 16) HWGRAD_LAUNCH(16, 4);
-  else if (tw == 8) HWGRAD_LAUNCH(8, 8);
-  else HWGRAD_LAUNCH(4, 4);
-#undef HWGRAD_LAUNCH
   const int64_t elements = (int64_t)C_out * C_in * 9;
-  hipLaunchKernelGGL(hwgrad3x3_finish_kernel, dim3((unsigned)(blocks * 32 * mb)), dim3(256), 0, s, p.partial, gw,
-                     C_out, C_in, p.tiles_ci, walkers, 32 * mb);
-  const int status = launch_status();
+  const int status = launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    constexpr int PREC = decltype(prec)::value;
+    if (tw == 32) hwgrad3_launch<32, 2, PREC>(p, mb, grid, s);
+    else if (tw == 16) hwgrad3_launch<16, 4, PREC>(p, mb, grid, s);
+    else if (tw == 8) hwgrad3_launch<8, 8, PREC>(p, mb, grid, s);
+    else hwgrad3_launch<4, 4, PREC>(p, mb, grid, s);
+    hipLaunchKernelGGL(hwgrad3x3_finish_kernel, dim3((unsigned)(blocks * 32 * mb)), dim3(256), 0, s, p.partial, gw,
+                       C_out, C_in, p.tiles_ci, walkers, 32 * mb);
+  });
   const double pixels = (double)N * H * W;
   profile_bracket_end_bytes(slot, s, C_out, (int64_t)C_in * 9, (int64_t)pixels, 15, 32 * mb, 64, walkers,
                             2.0 * pixels * (p.CGX + p.CGY) * 8 + 8.0 * (double)elements, dtype);

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void h_frozen_norm_bwd_kernel(const Slot* __re
 
 // What the four batch-statistics entry points check before any device work.
 static int h_bn_arguments(int32_t N, int32_t C, int64_t HW, int32_t dtype, bool pointers, const char* what) {
-  SRGAN_REQUIRE(dtype == 0 || dtype == 1 || dtype == 2, SRGAN_EINVAL, what);
+  if (const int status = check_precision<0, 1, 2>(dtype, what)) return status;
   SRGAN_REQUIRE(pointers && N > 0 && C > 0 && HW > 0, SRGAN_EINVAL, what);
   const int64_t M = HW > ((int64_t)1 << 24) ? HW : (int64_t)N * HW;      // values per channel (no overflow: N < 2^31)
   SRGAN_REQUIRE(M >= 2, SRGAN_EINVAL, what);
@@ -346,8 +346,8 @@ struct HBnGrid : RowFinishGrid { int group, CG; };
 // Images per workgroup as the NCHW kernels choose them, a slot counted as its 16 bytes = four fp32 elements.
 static HBnGrid h_bn_grid(int32_t N, int32_t C, int64_t HW, int32_t dtype) {
   HBnGrid grid;
-  grid.group = dtype == 0 ? 4 : 8;
-  grid.CG = (C + grid.group - 1) / grid.group;
+  grid.group = slot_channels(dtype);
+  grid.CG = channel_groups(C, dtype);
   grid.per = images_per_workgroup(N, grid.CG, HW * 4);
   grid.parts = (N + grid.per - 1) / grid.per;
   return grid;
@@ -362,36 +362,18 @@ static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int6
                                    element * tensors * (double)N * C * (double)HW, 0);
 }
 
-#define H_BN_LAUNCH(kernel, dtype, grid, stream, ...)                                                           \
-  do {                                                                                                          \
-    if ((dtype) == 0) hipLaunchKernelGGL(kernel<0>, grid, dim3(256), 0, stream, __VA_ARGS__);                    \
-    else if ((dtype) == 1) hipLaunchKernelGGL(kernel<1>, grid, dim3(256), 0, stream, __VA_ARGS__);               \
-    else hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, stream, __VA_ARGS__);                                 \
-  } while (0)
-
-// The modes of h_frozen_norm_bwd_kernel that a call can ask for (gx alone; sums alone, with or without the gamma sums; both; gx
-// with or without the mask reference).
-#define H_FROZEN_LAUNCH(GX, SUMS)                                                                                     \
-  do {                                                                                                                \
-    if (ref && (GX)) H_FROZEN_LAUNCH_MODE(GX, SUMS, true);                                                            \
-    else H_FROZEN_LAUNCH_MODE(GX, SUMS, false);                                                                       \
-  } while (0)
-#define H_FROZEN_LAUNCH_MODE(GX, SUMS, REF)                                                                           \
-  do {                                                                                                                \
-    const dim3 blocks(grid.CG, grid.parts);                                                                           \
-    if (dtype == 0) hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<0, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS);      \
-    else if (dtype == 1) hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<1, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS); \
-    else hipLaunchKernelGGL((h_frozen_norm_bwd_kernel<2, GX, SUMS, REF>), blocks, dim3(256), 0, stream, H_FROZEN_ARGUMENTS);                 \
-  } while (0)
-#define H_FROZEN_ARGUMENTS                                                                                                        \
-  (const Slot*)s, (const Slot*)x, mean, inv_std, gamma, (const Slot*)ref, slope, (Slot*)gx, g_gamma, g_beta, N, C, (int)HW, grid.per, \
-      grid.partial, grid.tickets
+// The modes of h_frozen_norm_bwd_kernel that a call can ask for: gx alone (SUMS 0), sums alone with or without the gamma sums,
+// both; the mask reference counts only where gx is written (the GX = false forms with REF are compiled here and never chosen).
+template <int PREC, bool GX, int SUMS>
+static auto h_frozen_kernel(bool masked) {
+  return masked && GX ? h_frozen_norm_bwd_kernel<PREC, GX, SUMS, true> : h_frozen_norm_bwd_kernel<PREC, GX, SUMS, false>;
+}
 
 int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const float* inv_std, const float* gamma, const void* ref,
                           float slope, void* gx, float* g_gamma, float* g_beta, int32_t N, int32_t C, int64_t HW, int32_t dtype,
                           hipStream_t stream) {
   const char* what = "srgan_h_frozen_norm_bwd arguments";
-  SRGAN_REQUIRE(dtype == 0 || dtype == 1 || dtype == 2, SRGAN_EINVAL, what);
+  if (const int status = check_precision<0, 1, 2>(dtype, what)) return status;
   SRGAN_REQUIRE(s && inv_std && gamma && N > 0 && C > 0 && HW > 0, SRGAN_EINVAL, what);
   SRGAN_REQUIRE(gx || g_gamma || g_beta, SRGAN_EINVAL, what);
   SRGAN_REQUIRE(x || !g_gamma, SRGAN_EINVAL, what);
@@ -410,12 +392,16 @@ int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const
     SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_frozen_norm_bwd grid");
   }
   const int slot = profile_bracket_begin(stream);
-  if (gx && sums == 2) H_FROZEN_LAUNCH(true, 2);
-  else if (gx && sums == 1) H_FROZEN_LAUNCH(true, 1);
-  else if (gx) H_FROZEN_LAUNCH(true, 0);
-  else if (sums == 2) H_FROZEN_LAUNCH(false, 2);
-  else H_FROZEN_LAUNCH(false, 1);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    constexpr int PREC = decltype(prec)::value;
+    const bool masked = ref != nullptr;
+    const auto kernel = gx ? (sums == 2   ? h_frozen_kernel<PREC, true, 2>(masked)
+                              : sums == 1 ? h_frozen_kernel<PREC, true, 1>(masked)
+                                          : h_frozen_kernel<PREC, true, 0>(masked))
+                           : (sums == 2 ? h_frozen_kernel<PREC, false, 2>(masked) : h_frozen_kernel<PREC, false, 1>(masked));
+    hipLaunchKernelGGL(kernel, dim3(grid.CG, grid.parts), dim3(256), 0, stream, (const Slot*)s, (const Slot*)x, mean, inv_std, gamma,
+                       (const Slot*)ref, slope, (Slot*)gx, g_gamma, g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
+  });
   h_bn_bracket(slot, stream, N, C, HW, dtype, 24, grid, 1.0 + (sums == 2) + (gx != nullptr) + (gx && ref));
   return status;
 }
@@ -435,9 +421,11 @@ int srgan_h_batch_norm_stats(const void* x, float* mean, float* inv_std, float* 
   HBnGrid grid = h_bn_grid(N, C, HW, dtype);
   if (const int status = row_finish_grid(grid.CG, N, 3 * grid.group, g_h_bn_tickets, s, "srgan_h_batch_norm_stats grid", &grid)) return status;
   const int slot = profile_bracket_begin(s);
-  H_BN_LAUNCH(h_bn_stats_kernel, dtype, dim3(grid.CG, grid.parts), s, (const Slot*)x, mean, inv_std, running_mean, running_var,
-              reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_bn_stats_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, s, (const Slot*)x, mean, inv_std,
+                       running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, (int)HW,
+                       grid.per, grid.partial, grid.tickets);
+  });
   h_bn_bracket(slot, s, N, C, HW, dtype, 20, grid, 1.0);
   return status;
 }
@@ -450,9 +438,10 @@ int srgan_h_batch_norm_fwd(const void* x, const float* mean, const float* inv_st
   const HBnGrid grid = h_bn_grid(N, C, HW, dtype);
   SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_batch_norm_fwd grid");
   const int slot = profile_bracket_begin(s);
-  H_BN_LAUNCH(h_bn_fwd_kernel, dtype, dim3(grid.CG, grid.parts), s, (const Slot*)x, mean, inv_std, gamma, beta, slope, (Slot*)y, N, C,
-              (int)HW, grid.per);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_bn_fwd_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, s, (const Slot*)x, mean, inv_std,
+                       gamma, beta, slope, (Slot*)y, N, C, (int)HW, grid.per);
+  });
   h_bn_bracket(slot, s, N, C, HW, dtype, 21, grid, 2.0);
   return status;
 }
@@ -465,9 +454,10 @@ int srgan_h_batch_norm_bwd_reduce(const void* s, const void* x, const float* mea
   HBnGrid grid = h_bn_grid(N, C, HW, dtype);
   if (const int status = row_finish_grid(grid.CG, N, 2 * grid.group, g_h_bn_tickets, st, "srgan_h_batch_norm_bwd_reduce grid", &grid)) return status;
   const int slot = profile_bracket_begin(st);
-  H_BN_LAUNCH(h_bn_bwd_reduce_kernel, dtype, dim3(grid.CG, grid.parts), st, (const Slot*)s, (const Slot*)x, mean, inv_std, sums, g_gamma,
-              g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_bn_bwd_reduce_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, st, (const Slot*)s,
+                       (const Slot*)x, mean, inv_std, sums, g_gamma, g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
+  });
   h_bn_bracket(slot, st, N, C, HW, dtype, 22, grid, 2.0);
   return status;
 }
@@ -483,9 +473,10 @@ int srgan_h_batch_norm_bwd_apply(const void* s, const void* x, const float* mean
   SRGAN_REQUIRE(grid.parts <= 65535, SRGAN_ERANGE, "srgan_h_batch_norm_bwd_apply grid");
   const float inv_count = (float)(1.0 / ((double)N * (double)HW));
   const int slot = profile_bracket_begin(st);
-  H_BN_LAUNCH(h_bn_bwd_apply_kernel, dtype, dim3(grid.CG, grid.parts), st, (const Slot*)s, (const Slot*)x, mean, inv_std, gamma, sums,
-              (const Slot*)ref, slope, (Slot*)gx, N, C, (int)HW, grid.per, inv_count);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_bn_bwd_apply_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, st, (const Slot*)s,
+                       (const Slot*)x, mean, inv_std, gamma, sums, (const Slot*)ref, slope, (Slot*)gx, N, C, (int)HW, grid.per, inv_count);
+  });
   h_bn_bracket(slot, st, N, C, HW, dtype, 23, grid, 3.0);
   return status;
 }

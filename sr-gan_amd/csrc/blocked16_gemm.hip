@@ -296,10 +296,7 @@ __global__ __launch_bounds__(256, 2) void hlinear_wgrad_kernel(const HLinearWgra
   }
 }
 
-static int check_dtype_g(int dtype) {
-  SRGAN_REQUIRE(dtype == 1 || dtype == 2, SRGAN_EINVAL, "blocked 16-bit tensors are bf16 (1) or fp16 (2)");
-  return SRGAN_OK;
-}
+static const char* const H16_ONLY = "blocked 16-bit tensors are bf16 (1) or fp16 (2)";
 
 }  // namespace srgan
 
@@ -314,21 +311,21 @@ int srgan_h_pack_matrix(const float* src, void* out, int64_t rows, int64_t cols,
                         int64_t row_stride, int64_t col_stride, int32_t row_plane, int32_t col_plane, int dtype,
                         void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_g(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(src && out && rows > 0 && cols > 0, SRGAN_EINVAL, "srgan_h_pack_matrix arguments");
   const int64_t row_slots = (cols + 7) / 8, slots = rows * row_slots;
   SRGAN_REQUIRE(row_slots < ((int64_t)1 << 31), SRGAN_ERANGE, "srgan_h_pack_matrix row length");
   if (row_stride == 1 && col_stride != 1) {
     const int tiles_r = (int)((rows + 63) / 64), tiles_c = (int)((row_slots * 8 + 63) / 64);
     const dim3 tgrid((unsigned)(tiles_r * tiles_c));
-    if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<1>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
-    else hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<2>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
-    return launch_status();
+    return launch_for_precision<1, 2>(dtype, [&](auto prec) {
+      hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<decltype(prec)::value>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
+    });
   }
   const dim3 grid((unsigned)((slots + 255) / 256));
-  if (dtype == 1) hipLaunchKernelGGL(h_pack_matrix_kernel<1>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
-  else hipLaunchKernelGGL(h_pack_matrix_kernel<2>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
-  return launch_status();
+  return launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(h_pack_matrix_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
+  });
 }
 
 // out[N][M'] = epi(B[N][K] * A[M][K]^T [+ bias]) on 16-bit row-major matrices (pitches = ceil(. / 8) slots); M' = out_cols.
@@ -336,7 +333,7 @@ int srgan_h_pack_matrix(const float* src, void* out, int64_t rows, int64_t cols,
 int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* ref, float slope, int epi, void* out, int32_t M,
                  int32_t N, int32_t K, int32_t out_cols, int32_t bias_entries, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_g(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(a && b && out && M > 0 && N > 0 && K > 0 && out_cols > 0 && epi >= 0 && epi <= 2 && (epi != 2 || ref), SRGAN_EINVAL,
                 "srgan_h_gemm arguments");
   HGemmParams p;
@@ -373,9 +370,9 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
   }
   const dim3 grid((unsigned)tiles, (unsigned)split);
   const int slot = profile_bracket_begin(s);
-  if (dtype == 1) hipLaunchKernelGGL(hgemm_kernel<1>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(hgemm_kernel<2>, grid, dim3(256), 0, s, p);
-  const int status = launch_status();
+  const int status = launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(hgemm_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, p);
+  });
   profile_bracket_end_bytes(slot, s, M, N, K, 16, 128, 128, split,
                             2.0 * ((double)M * K + (double)N * K + (double)N * out_cols * (epi == 2 ? 2 : 1)), dtype);
   return status;
@@ -386,7 +383,7 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
 int srgan_h_linear_wgrad(const void* s, const void* x, float* gw, int32_t N, int32_t M, int32_t K, int64_t M_real, int64_t K_real,
                          int64_t ldw_m, int64_t ldw_k, int32_t row_plane, int32_t col_plane, int dtype, void* stream) {
   hipStream_t hs = (hipStream_t)stream;
-  if (const int status = check_dtype_g(dtype)) return status;
+  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
   SRGAN_REQUIRE(s && x && gw && N > 0 && M > 0 && K > 0, SRGAN_EINVAL, "srgan_h_linear_wgrad arguments");
   HLinearWgradParams p;
   p.s = (const Slot*)s; p.x = (const Slot*)x; p.gw = gw;
@@ -397,9 +394,9 @@ int srgan_h_linear_wgrad(const void* s, const void* x, float* gw, int32_t N, int
   const int tiles_k = (p.KS + 15) / 16;
   const dim3 grid((unsigned)(p.tiles_m * tiles_k));
   const int slot = profile_bracket_begin(hs);
-  if (dtype == 1) hipLaunchKernelGGL(hlinear_wgrad_kernel<1>, grid, dim3(256), 0, hs, p);
-  else hipLaunchKernelGGL(hlinear_wgrad_kernel<2>, grid, dim3(256), 0, hs, p);
-  const int status = launch_status();
+  const int status = launch_for_precision<1, 2>(dtype, [&](auto prec) {
+    hipLaunchKernelGGL(hlinear_wgrad_kernel<decltype(prec)::value>, grid, dim3(256), 0, hs, p);
+  });
   profile_bracket_end_bytes(slot, hs, M, K, N, 17, 128, 128, 1, 2.0 * (double)N * (M + K) + 8.0 * (double)M * K, dtype);
   return status;
 }

@@ -19,7 +19,6 @@
 //                          transpose-read fragments, partial blocks + ordered finish
 //   h_pack_k4s2_weights    the operand shadows: "down" [chunk = group][tap][parity][rows], "up" [class][chunk][tap][group][rows]
 #include <type_traits>
-#include <atomic>
 #include <stdlib.h>
 #include "blocked16.h"
 #include "launchers.h"
@@ -273,15 +272,8 @@ static int hconv2_launch_one(const HConv2Params& p, dim3 grid, hipStream_t strea
   constexpr int PATCH_I = (K4_CK * IMG * PLANE + 63) / 64, T = PATCH_I + K4_TAPS * K4_CK * BM / 64, TP = (T + 3) / 4 * 4;
   constexpr int bytes = 2 * TP * 64 * 16;
   static_assert(bytes <= 80 * 1024, "two workgroups per CU");
-  auto kernel = hconv2x2_kernel<BM, NI, TW, ROWS, PREC>;
-  static std::atomic<uint64_t> configured_devices{0};
-  int device = 0;
-  SRGAN_HIP(hipGetDevice(&device));
-  const uint64_t bit = (uint64_t)1 << (device & 63);
-  if (!(configured_devices.load(std::memory_order_acquire) & bit)) {
-    SRGAN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    configured_devices.fetch_or(bit, std::memory_order_release);
-  }
+  constexpr auto kernel = hconv2x2_kernel<BM, NI, TW, ROWS, PREC>;
+  SRGAN_HIP(allow_dynamic_lds<kernel>(bytes));
   hipLaunchKernelGGL(kernel, grid, dim3(256), bytes, stream, p, h_zero_slots());
   return SRGAN_OK;
 }
@@ -299,14 +291,19 @@ static int hconv2_launch(const HConv2Params& p, int ni, int tw, dim3 grid, hipSt
   return hconv2_launch_one<BM, 1, 4, 4, PREC>(p, grid, stream);
 }
 
-// One launch of the 2x2-tap kernel over a GH x GW grid of output positions.
-static int hconv2_run(HConv2Params& p, int dtype, int64_t flops_k, hipStream_t stream) {
-  // tile width: the one of {32, 16, 8, 4} that covers GW with the fewest dead columns (ties: the wider)
+// Tile width of this family: the one of {32, 16, 8, 4} that covers a row of `columns` with the fewest dead columns (ties: the wider)
+static int k4_tile_width(int columns) {
   int tw = 32, best = 1 << 30;
   for (int candidate : {32, 16, 8, 4}) {
-    const int covered = (p.GW + candidate - 1) / candidate * candidate;
+    const int covered = (columns + candidate - 1) / candidate * candidate;
     if (covered < best) { best = covered; tw = candidate; }
   }
+  return tw;
+}
+
+// One launch of the 2x2-tap kernel over a GH x GW grid of output positions.
+static int hconv2_run(HConv2Params& p, int dtype, int64_t flops_k, hipStream_t stream) {
+  const int tw = k4_tile_width(p.GW);
   const int bm = p.CO > 32 ? 64 : 32;
   p.tiles_m = (p.CO + bm - 1) / bm;
   auto rows_of = [&](int ni) { return tw == 32 ? 4 * ni : (tw == 16 ? 8 * ni : tw); };
@@ -325,9 +322,12 @@ static int hconv2_run(HConv2Params& p, int dtype, int64_t flops_k, hipStream_t s
   p.xcd_remap = (blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
   const dim3 grid((unsigned)blocks, p.down ? 1u : 4u);
   const int slot = profile_bracket_begin(stream);
-  int launched;
-  if (bm == 64) launched = dtype == 0 ? hconv2_launch<64, 0>(p, ni, tw, grid, stream) : (dtype == 1 ? hconv2_launch<64, 1>(p, ni, tw, grid, stream) : hconv2_launch<64, 2>(p, ni, tw, grid, stream));
-  else launched = dtype == 0 ? hconv2_launch<32, 0>(p, ni, tw, grid, stream) : (dtype == 1 ? hconv2_launch<32, 1>(p, ni, tw, grid, stream) : hconv2_launch<32, 2>(p, ni, tw, grid, stream));
+  int launched = SRGAN_OK;
+  if (!for_precision<0, 1, 2>(dtype, [&](auto prec) {
+        constexpr int PREC = decltype(prec)::value;
+        launched = bm == 64 ? hconv2_launch<64, PREC>(p, ni, tw, grid, stream) : hconv2_launch<32, PREC>(p, ni, tw, grid, stream);
+      }))
+    launched = check_precision<>(dtype, "k4s2 convolution launch");
   if (launched != SRGAN_OK) return launched;
   const int status = launch_status();
   const double positions = (double)p.N * p.GH * p.GW * (p.down ? 1 : 4);       // output pixels
@@ -660,11 +660,13 @@ __global__ __launch_bounds__(256) void hwgrad4x4s2_finish_kernel(const float* __
   }
 }
 
-static int check_dtype_k(int dtype) {
-  SRGAN_REQUIRE(dtype >= 0 && dtype <= 2, SRGAN_EINVAL, "blocked tensors are fp32 (0: four channels per slot), bf16 (1) or fp16 (2)");
-  return SRGAN_OK;
+template <int TW, int ROWS, int ROWS_F32, int PREC>
+static void hwgrad4_launch(const HWgrad4Params& p, dim3 grid, hipStream_t stream) {
+  if constexpr (PREC == 0) hipLaunchKernelGGL((hwgrad4x4s2_f32_kernel<TW, ROWS_F32>), grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((hwgrad4x4s2_kernel<TW, ROWS, PREC>), grid, dim3(256), 0, stream, p);
 }
-static inline int group_of(int dtype) { return dtype == 0 ? 4 : 8; }
+
+static const char* const H_ANY = "blocked tensors are fp32 (0: four channels per slot), bf16 (1) or fp16 (2)";
 
 }  // namespace srgan
 
@@ -675,35 +677,25 @@ extern "C" {
 // 16-byte slots of one operand of a [A][B][4][4] weight tensor: direction 0 "down" (rows = A: the strided convolution's forward /
 // a transposed convolution's data gradient), 1 "up" (rows = B, all four output parity classes, class-major).
 int64_t srgan_h_k4s2_weight_slots(int32_t A, int32_t B, int direction, int dtype) {
-  const int g = group_of(dtype);
-  if (direction == 0) return (int64_t)((B + g - 1) / g) * K4_TAPS * K4_CK * A;
-  return (int64_t)4 * (((A + g - 1) / g + K4_CK - 1) / K4_CK) * K4_TAPS * K4_CK * B;
+  if (direction == 0) return (int64_t)channel_groups(B, dtype) * K4_TAPS * K4_CK * A;
+  return (int64_t)4 * ((channel_groups(A, dtype) + K4_CK - 1) / K4_CK) * K4_TAPS * K4_CK * B;
 }
 
 int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B, int direction, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_k(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H_ANY)) return status;
   SRGAN_REQUIRE(w && packed && A > 0 && B > 0 && (direction == 0 || direction == 1), SRGAN_EINVAL, "srgan_h_pack_k4s2_weights arguments");
-#define K4_PACK(...)                                                                                                     \
-  do {                                                                                                                  \
-    if (dtype == 0) hipLaunchKernelGGL(h_pack_k4s2_weights_kernel<0>, __VA_ARGS__);                                     \
-    else if (dtype == 1) hipLaunchKernelGGL(h_pack_k4s2_weights_kernel<1>, __VA_ARGS__);                                \
-    else hipLaunchKernelGGL(h_pack_k4s2_weights_kernel<2>, __VA_ARGS__);                                                \
-  } while (0)
-  if (direction == 0) {
-    const int64_t slots = srgan_h_k4s2_weight_slots(A, B, 0, dtype);
-    const dim3 grid((unsigned)((slots + 255) / 256));
-    K4_PACK(grid, dim3(256), 0, s, w, (Slot*)packed, slots, A, B, (int64_t)B * 16, (int64_t)16, 0);
-    return launch_status();
-  }
-  const int64_t per_class = srgan_h_k4s2_weight_slots(A, B, 1, dtype) / 4;
-  const dim3 grid((unsigned)((per_class + 255) / 256));
-  for (int cls = 0; cls < 4; ++cls) {
-    Slot* into = (Slot*)packed + cls * per_class;
-    K4_PACK(grid, dim3(256), 0, s, w, into, per_class, B, A, (int64_t)16, (int64_t)B * 16, 1 + cls);
-  }
-#undef K4_PACK
-  return launch_status();
+  // "down": one operand of rows A; "up": the four parity classes, rows B each
+  const int classes = direction ? 4 : 1;
+  const int64_t slots = srgan_h_k4s2_weight_slots(A, B, direction, dtype) / classes;
+  const dim3 grid((unsigned)((slots + 255) / 256));
+  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    auto kernel = h_pack_k4s2_weights_kernel<decltype(prec)::value>;
+    if (direction == 0) hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w, (Slot*)packed, slots, A, B, (int64_t)B * 16, (int64_t)16, 0);
+    else
+      for (int cls = 0; cls < 4; ++cls)
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w, (Slot*)packed + cls * slots, slots, B, A, (int64_t)16, (int64_t)B * 16, 1 + cls);
+  });
 }
 
 // "down": out[N, rows, H/2, W/2] = epi(conv2d 4x4 / stride 2 / pad 1 of x[N, C_in, H, W]) with the direction-0 operand of
@@ -711,23 +703,22 @@ int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B
 int srgan_h_conv4x4s2(const void* x, const void* packed, const float* bias, const void* ref, float slope, int epi, void* out,
                       int32_t N, int32_t C_in, int32_t rows, int32_t H, int32_t W, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_k(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H_ANY)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && rows > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && epi >= 0 &&
                 epi <= 2 && (epi != 2 || ref), SRGAN_EINVAL, "srgan_h_conv4x4s2 arguments (even planes)");
   HConv2Params p;
   p.in = (const Slot*)x; p.wp = (const Slot*)packed; p.out = (Slot*)out; p.bias = bias; p.ref = (const Slot*)ref;
   p.slope = slope; p.epi = epi;
-  const int g = group_of(dtype);
-  p.N = N; p.CGI = (C_in + g - 1) / g; p.IH = H; p.IW = W;
+  p.N = N; p.CGI = channel_groups(C_in, dtype); p.IH = H; p.IW = W;
   p.down = 1; p.oy = -1; p.ox = -1;
   p.GH = H / 2; p.GW = W / 2;
-  p.CGO = (rows + g - 1) / g; p.OH = H / 2; p.OW = W / 2; p.dsy = p.dsx = 1; p.doy = p.dox = 0;
+  p.CGO = channel_groups(rows, dtype); p.OH = H / 2; p.OW = W / 2; p.dsy = p.dsx = 1; p.doy = p.dox = 0;
   p.CO = rows; p.C_real = rows;
   p.chunks = p.CGI;
   p.class_stride = 0;
   SRGAN_REQUIRE((int64_t)N * p.CGI * H * W < ((int64_t)1 << 31) && (int64_t)N * p.CGO * p.OH * p.OW < ((int64_t)1 << 31), SRGAN_ERANGE,
                 "srgan_h_conv4x4s2 tensor size");
-  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 16, s);
+  return hconv2_run(p, dtype, (int64_t)p.CGI * slot_channels(dtype) * 16, s);
 }
 
 // "up": out[N, rows, 2h, 2w] = epi(conv_transpose2d 4x4 / stride 2 / pad 1 of x[N, C_in, h, w]) with the direction-1 operand
@@ -736,23 +727,22 @@ int srgan_h_conv_transpose4x4s2(const void* x, const void* packed, const float* 
                                 void* out, int32_t N, int32_t C_in, int32_t rows, int32_t h, int32_t w, int dtype,
                                 void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_k(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H_ANY)) return status;
   SRGAN_REQUIRE(x && packed && out && N > 0 && C_in > 0 && rows > 0 && h > 0 && w > 0 && epi >= 0 && epi <= 2 && (epi != 2 || ref),
                 SRGAN_EINVAL, "srgan_h_conv_transpose4x4s2 arguments");
-  const int g = group_of(dtype);
   HConv2Params p;
   p.in = (const Slot*)x; p.wp = (const Slot*)packed; p.out = (Slot*)out; p.bias = bias; p.ref = (const Slot*)ref;
   p.slope = slope; p.epi = epi;
-  p.N = N; p.CGI = (C_in + g - 1) / g; p.IH = h; p.IW = w;
+  p.N = N; p.CGI = channel_groups(C_in, dtype); p.IH = h; p.IW = w;
   p.down = 0; p.oy = p.ox = -1;                                  // (set per class in the kernel)
   p.GH = h; p.GW = w;
-  p.CGO = (rows + g - 1) / g; p.OH = 2 * h; p.OW = 2 * w; p.dsy = p.dsx = 2; p.doy = p.dox = 0;
+  p.CGO = channel_groups(rows, dtype); p.OH = 2 * h; p.OW = 2 * w; p.dsy = p.dsx = 2; p.doy = p.dox = 0;
   p.CO = rows; p.C_real = rows;
   p.chunks = (p.CGI + K4_CK - 1) / K4_CK;
   p.class_stride = srgan_h_k4s2_weight_slots(C_in, rows, 1, dtype) / 4;
   SRGAN_REQUIRE((int64_t)N * p.CGI * h * w < ((int64_t)1 << 31) && (int64_t)N * p.CGO * p.OH * p.OW < ((int64_t)1 << 31), SRGAN_ERANGE,
                 "srgan_h_conv_transpose4x4s2 tensor size");
-  return hconv2_run(p, dtype, (int64_t)p.CGI * g * 4, s);
+  return hconv2_run(p, dtype, (int64_t)p.CGI * slot_channels(dtype) * 4, s);
 }
 
 // gw (fp32 [A][B][4][4] in torch's layout) += the weight gradient of the 4x4 / stride 2 / pad 1 pair from `small` [N, C_small, H/2,
@@ -761,18 +751,13 @@ int srgan_h_conv_transpose4x4s2(const void* x, const void* packed, const float* 
 int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N, int32_t C_big, int32_t C_small, int32_t H, int32_t W,
                        int small_is_rows, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_dtype_k(dtype)) return status;
+  if (const int status = check_precision<0, 1, 2>(dtype, H_ANY)) return status;
   SRGAN_REQUIRE(big && small && gw && N > 0 && C_big > 0 && C_small > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, SRGAN_EINVAL,
                 "srgan_h_k4s2_wgrad arguments");
   HWgrad4Params p;
-  const int g = group_of(dtype);
   p.big = (const Slot*)big; p.small = (const Slot*)small;
-  p.N = N; p.CGB = (C_big + g - 1) / g; p.CGS = (C_small + g - 1) / g; p.H = H; p.W = W; p.SH = H / 2; p.SW = W / 2;
-  int tw = 32, best = 1 << 30;
-  for (int candidate : {32, 16, 8, 4}) {
-    const int covered = (p.SW + candidate - 1) / candidate * candidate;
-    if (covered < best) { best = covered; tw = candidate; }
-  }
+  p.N = N; p.CGB = channel_groups(C_big, dtype); p.CGS = channel_groups(C_small, dtype); p.H = H; p.W = W; p.SH = H / 2; p.SW = W / 2;
+  const int tw = k4_tile_width(p.SW);
   const int pixels_per_tile = dtype == 0 ? 32 : 64;
   const int rows = pixels_per_tile / tw > 0 ? (tw == 4 ? 4 : pixels_per_tile / tw) : 1;      // 32: 2 (1) rows, 16: 4 (2), 8: 8 (4), 4: 4
   const int img = pixels_per_tile / (rows * tw);
@@ -792,21 +777,16 @@ int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N,
   SRGAN_REQUIRE(p.partial, SRGAN_EINVAL, "srgan_h_k4s2_wgrad: register a workspace for this stream first (srgan_set_workspace)");
   const dim3 grid((unsigned)blocks, (unsigned)walkers);
   const int slot = profile_bracket_begin(s);
-#define HWGRAD4_LAUNCH(TWv, ROWSv, ROWSf)                                                                              \
-  do {                                                                                                                  \
-    if (dtype == 0) hipLaunchKernelGGL((hwgrad4x4s2_f32_kernel<TWv, ROWSf>), grid, dim3(256), 0, s, p);                 \
-    else if (dtype == 1) hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 1>), grid, dim3(256), 0, s, p);             \
-    else hipLaunchKernelGGL((hwgrad4x4s2_kernel<TWv, ROWSv, 2>), grid, dim3(256), 0, s, p);                             \
-  } while (0)
-  if (tw == 32) HWGRAD4_LAUNCH(32, 2, 1);
-  else if (tw == 16) HWGRAD4_LAUNCH(16, 4, 2);
-  else if (tw == 8) HWGRAD4_LAUNCH(8, 8, 4);
-  else HWGRAD4_LAUNCH(4, 4, 4);
-#undef HWGRAD4_LAUNCH
   const int64_t sk = small_is_rows ? (int64_t)C_big * 16 : 16, sc = small_is_rows ? 16 : (int64_t)C_small * 16;
-  hipLaunchKernelGGL(hwgrad4x4s2_finish_kernel, dim3((unsigned)(blocks * 64)), dim3(256), 0, s, p.partial, gw, C_small, C_big,
-                     p.tiles_c, walkers, sk, sc);
-  const int status = launch_status();
+  const int status = launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
+    constexpr int PREC = decltype(prec)::value;          // (TW, rows of the 64-pixel tile, rows of the fp32 kernel's 32-pixel tile)
+    if (tw == 32) hwgrad4_launch<32, 2, 1, PREC>(p, grid, s);
+    else if (tw == 16) hwgrad4_launch<16, 4, 2, PREC>(p, grid, s);
+    else if (tw == 8) hwgrad4_launch<8, 8, 4, PREC>(p, grid, s);
+    else hwgrad4_launch<4, 4, 4, PREC>(p, grid, s);
+    hipLaunchKernelGGL(hwgrad4x4s2_finish_kernel, dim3((unsigned)(blocks * 64)), dim3(256), 0, s, p.partial, gw, C_small, C_big,
+                       p.tiles_c, walkers, sk, sc);
+  });
   const double pixels = (double)N * p.SH * p.SW;
   profile_bracket_end_bytes(slot, s, C_small, (int64_t)C_big * 16, (int64_t)pixels, 19, 64, 32, walkers,
                             2.0 * (pixels * p.CGS * 8 + 4.0 * pixels * p.CGB * 8) + 8.0 * (double)C_small * C_big * 16, dtype);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 // The C ABI: every extern "C" definition is compiled against its declaration here.
 #include "../../include/srgan_hip.h"
 
@@ -37,6 +38,23 @@ inline int launch_status() {
     return (int)e;
   }
   return SRGAN_OK;
+}
+
+// More than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize -- once per kernel AND per device (the
+// attribute belongs to the device's copy of the function).  KERNEL is a template argument so that every kernel has its own
+// record: a bit per device ordinal, set with an atomic OR, so that two host threads launching for the first time together at
+// worst both set the (idempotent) attribute.  Returns the HIP status of what it had to call.  (static: the record stays a
+// local symbol of the kernel's translation unit, not an export of the library.)
+template <auto KERNEL>
+static hipError_t allow_dynamic_lds(int bytes) {
+  static std::atomic<uint64_t> configured{0};
+  int device = 0;
+  hipError_t status = hipGetDevice(&device);
+  const uint64_t bit = (uint64_t)1 << (device & 63);
+  if (status != hipSuccess || (configured.load(std::memory_order_acquire) & bit)) return status;
+  status = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (status == hipSuccess) configured.fetch_or(bit, std::memory_order_release);
+  return status;
 }
 
 // Zero-fills are kernels of this library, not hipMemsetAsync: a memset NODE of a captured HIP graph replayed wrongly for

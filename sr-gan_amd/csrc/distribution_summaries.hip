@@ -4,7 +4,6 @@
 // shows them (coefficient/presentation.py:19-55).  Summary-step work of a few thousand values: one workgroup sorts, the other
 // kernels are gathers; nothing here is tuned beyond coalesced loads and stores.  Every fp32 operation whose rounding the tests'
 // restatement repeats is spelled with the _rn intrinsics, so that the compiler does not contract it into an fma.
-#include <atomic>
 #include <cmath>
 
 #include "bn_train.h"
@@ -209,16 +208,7 @@ __global__ __launch_bounds__(256) void curve_frame_kernel(const float* __restric
 int wasserstein_run(const float* u, int32_t n, const float* v, int32_t m, float* out, hipStream_t stream) {
   int P = 2;
   while (P < n + m) P <<= 1;
-  // More than 64 KB of dynamic LDS needs the attribute, once per device (as in pointwise_ring.hip).
-  static std::atomic<uint64_t> configured_devices{0};
-  int device = 0;
-  SRGAN_HIP(hipGetDevice(&device));
-  const uint64_t bit = (uint64_t)1 << (device & 63);
-  if (!(configured_devices.load(std::memory_order_acquire) & bit)) {
-    SRGAN_HIP(hipFuncSetAttribute((const void*)wasserstein_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  wasserstein_lds_bytes(SRGAN_WASSERSTEIN_MAX_VALUES)));
-    configured_devices.fetch_or(bit, std::memory_order_release);
-  }
+  SRGAN_HIP(allow_dynamic_lds<wasserstein_kernel>(wasserstein_lds_bytes(SRGAN_WASSERSTEIN_MAX_VALUES)));
   hipLaunchKernelGGL(wasserstein_kernel, dim3(1), dim3(WASSERSTEIN_THREADS), wasserstein_lds_bytes(P), stream, u, n, v, m, P, out);
   return launch_status();
 }

@@ -30,7 +30,6 @@
 #include "launchers.h"
 #include "lds_dma.h"
 #include "split_finish.h"
-#include <atomic>
 #include <stdlib.h>
 #include <string.h>
 
@@ -576,19 +575,6 @@ static bool pointwise_wgrad_lds_shape(int32_t CI, int32_t CO, int32_t HW) {
   return CI >= min_ci && HW % 32 == 0 && (int64_t)(CI > CO ? CI : CO) * HW * 4 < ((int64_t)1 << 32);
 }
 
-// (72 KB of dynamic LDS is beyond the 64 KB a launch gets without the attribute: set once per kernel and device, see pointwise_ring.hip)
-template <typename Kernel>
-static int pointwise_wgrad_lds_configure(Kernel kernel, std::atomic<uint64_t>& configured_devices) {
-  int device = 0;
-  SRGAN_HIP(hipGetDevice(&device));
-  const uint64_t bit = (uint64_t)1 << (device & 63);
-  if (!(configured_devices.load(std::memory_order_acquire) & bit)) {
-    SRGAN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PWL_LDS_BYTES));
-    configured_devices.fetch_or(bit, std::memory_order_release);
-  }
-  return SRGAN_OK;
-}
-
 static bool pointwise_wgrad_ragged(const float* x, int64_t x_bs, const float* gy, int64_t gy_bs, int32_t HW) {
   return HW % 32 != 0 || x_bs % 4 != 0 || gy_bs % 4 != 0 || (((uintptr_t)x | (uintptr_t)gy) & 15) != 0;
 }
@@ -613,11 +599,9 @@ int pointwise_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t g
   p.partial = nullptr; p.split = split;
   if (split > 1 && !split_atomics_forced()) p.partial = partial_workspace((size_t)tiles * split * tile_floats * sizeof(float), stream);
   dim3 grid((unsigned)tiles, (unsigned)split, 1);
-  if (staged) {
-    static std::atomic<uint64_t> configured_plain{0}, configured_bn{0};
-    if (const int status = bn ? pointwise_wgrad_lds_configure(pointwise_wgrad_lds_kernel<true>, configured_bn)
-                              : pointwise_wgrad_lds_configure(pointwise_wgrad_lds_kernel<false>, configured_plain)) return status;
-  }
+  if (staged)       // (72 KB of dynamic LDS)
+    SRGAN_HIP(bn ? allow_dynamic_lds<pointwise_wgrad_lds_kernel<true>>(PWL_LDS_BYTES)
+                 : allow_dynamic_lds<pointwise_wgrad_lds_kernel<false>>(PWL_LDS_BYTES));
   const int profile_slot = profile_bracket_begin(stream);
   if (staged && bn) hipLaunchKernelGGL(pointwise_wgrad_lds_kernel<true>, grid, dim3(256), PWL_LDS_BYTES, stream, p);
   else if (staged) hipLaunchKernelGGL(pointwise_wgrad_lds_kernel<false>, grid, dim3(256), PWL_LDS_BYTES, stream, p);
@@ -684,12 +668,9 @@ int pointwise_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, i
   SRGAN_REQUIRE(rounds * 8 * grid_x < ((int64_t)1 << 31), SRGAN_ERANGE, "grouped pointwise wgrad grid");
   dim3 grid((unsigned)(rounds * 8 * grid_x), 1, 1);
   const PwWgradJob* table = reinterpret_cast<const PwWgradJob*>(jobs);
-  if (staged) {
-    static std::atomic<uint64_t> configured_plain{0}, configured_bn{0};
-    if (const int status = fused_bn ? pointwise_wgrad_lds_configure(pointwise_wgrad_lds_grouped_kernel<true>, configured_bn)
-                                    : pointwise_wgrad_lds_configure(pointwise_wgrad_lds_grouped_kernel<false>, configured_plain))
-      return status;
-  }
+  if (staged)
+    SRGAN_HIP(fused_bn ? allow_dynamic_lds<pointwise_wgrad_lds_grouped_kernel<true>>(PWL_LDS_BYTES)
+                       : allow_dynamic_lds<pointwise_wgrad_lds_grouped_kernel<false>>(PWL_LDS_BYTES));
   const int profile_slot = profile_bracket_begin(stream);
 #define SRGAN_PWG_LAUNCH(PRO, RAG) hipLaunchKernelGGL((pointwise_wgrad_grouped_kernel<PRO, RAG>), grid, dim3(256), 0, stream, \
                                                       table, x_base, gy_base, gw_base, grid_x, grid_y, count, partial_base)
