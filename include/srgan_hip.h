@@ -631,7 +631,18 @@ int srgan_broadcast(void* comm, void* buffer, int64_t count, int32_t dtype, int3
  * the DCGAN stacks' `leaky_relu(conv)` (age/models.py:48-50,70-73).
  * epi (epilogue of a contraction): 0 = store; 1 = + bias (may be NULL), then leaky_relu with `slope` (0 = relu, 1 = identity);
  * 2 = multiply by the derivative of the activation that produced `ref` (1 where ref > 0, `slope` elsewhere; ref has the
- * output's shape): the gradient with respect to the PRE-activation tensor leaves the kernel, the un-masked one never exists. */
+ * output's shape): the gradient with respect to the PRE-activation tensor leaves the kernel, the un-masked one never exists.
+ * Rounding: every 16-bit store is ONE round to nearest even of the fp32 value (ties to the even neighbour, beyond the largest
+ * finite value to inf), fp32 subnormal inputs and 16-bit subnormal results included: nothing is flushed to zero, and
+ * srgan_h_unpack is the exact conversion of all 65536 bit patterns.  srgan_h_add is one fp32 addition and one such rounding.
+ * NaN and mask rule: "ref > 0" is decided per storage type.  The 16-bit forms (dtype 1 / 2) test the stored BITS -- sign bit
+ * clear and not zero ((int16_t)bits > 0) -- in srgan_h_pack's mask, every contraction's epi 2, the blocked batch norm and
+ * srgan_h_maxpool2_bwd's `masked` (on the pooled value): positive subnormals and +inf are positive, +-0 and everything with
+ * the sign bit set are not, and a NaN counts as positive exactly when its sign bit is clear.  dtype 0 (fp32 slots) tests
+ * `ref > 0.f` like the fp32 kernels above: a NaN of either sign is not positive.  The 2x2 max-pool takes the FIRST maximum in
+ * scan order (0,0), (0,1), (1,0), (1,1) under `>`: torch's choice for every window without a NaN (+0 and -0 tie: the first
+ * wins).  A NaN never beats the running maximum and is never beaten: a NaN at window position (0,0) is the result and the
+ * arg-max, a NaN at one of the other three positions is skipped (torch propagates a NaN from every position). */
 int srgan_h_pack(const float* x_nchw, void* out, const void* mask_ref, float slope, int32_t N, int32_t C, int64_t HW, int dtype,
                  void* stream);                                /* fp32 NCHW -> blocked (times mask(ref) when mask_ref != NULL) */
 int srgan_h_unpack(const void* x, float* out_nchw, int32_t N, int32_t C, int64_t HW, int dtype, void* stream);
@@ -639,7 +650,8 @@ int srgan_h_add(const void* a, const void* b, void* out, int64_t slots, int dtyp
 int srgan_h_channel_sums(const void* x, float* out, int32_t N, int32_t C, int64_t HW, int dtype, void* stream);   /* out[c] += ... (bias gradient) */
 /* mode 0: out = max_pool2d(x, 2, 2); mode 2: out = g (shape of x) gathered at the arg-max of x.  planes = N * groups. */
 int srgan_h_maxpool2(const void* x, const void* g, void* out, int64_t planes, int32_t H, int32_t W, int mode, int dtype, void* stream);
-/* gx (shape of x) = gp placed at the arg-max of x (first maximum in scan order, torch's rule), times mask(x, slope) if masked */
+/* gx (shape of x) = gp placed at the arg-max of x (first maximum in scan order: torch's rule without a NaN in the window, the
+ * NaN rule above with one), zeros at the other three positions, times mask(pooled x, slope) if masked */
 int srgan_h_maxpool2_bwd(const void* x, const void* gp, void* gx, int64_t planes, int32_t H, int32_t W, int masked, float slope,
                          int dtype, void* stream);
 /* The 16-bit shadow of conv2d weights w[K][C][R][S] in operand slots; transposed = 1: the data-gradient operand (rows = C,

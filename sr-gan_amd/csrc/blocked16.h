@@ -64,6 +64,8 @@ __device__ __forceinline__ float h_hi(uint32_t u) {
 }
 // [value > 0] of a 16-bit float given its bits (bf16 and fp16 alike: sign clear, not zero; NaN counts as positive)
 __device__ __forceinline__ bool h_positive(uint32_t bits16) { return (int16_t)(uint16_t)bits16 > 0; }
+// the same answer from the float h_lo / h_hi made of those bits (the conversion keeps the sign, zero stays zero, NaN stays NaN)
+__device__ __forceinline__ bool h_positive_unpacked(float value) { return (int32_t)__float_as_uint(value) > 0; }
 
 template <int PREC>
 __device__ __forceinline__ void h_unpack8(const Slot& s, float (&f)[8]) {

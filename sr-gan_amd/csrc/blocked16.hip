@@ -144,7 +144,9 @@ __global__ __launch_bounds__(256) void h_channel_sums_finish_kernel(const float*
 }
 
 // 2x2 / stride 2 max-pool (reference age/vgg.py:76).  The arg-max is not stored: every kernel that needs it finds the FIRST
-// window position (scan order (0,0), (0,1), (1,0), (1,1): torch's tie rule) that holds the maximum.
+// window position (scan order (0,0), (0,1), (1,0), (1,1): torch's tie rule) that holds the maximum.  With a NaN in the window
+// this is NOT torch (which propagates it): `v > m` is false for a NaN on either side, so a NaN at position 0 stays and a NaN at
+// positions 1 .. 3 is skipped (include/srgan_hip.h, NaN and mask rule; pinned by tests/test_blocked_streaming_gpu.py).
 template <int PREC>
 __device__ __forceinline__ void h_pool_window(const Slot* __restrict__ x, int64_t base, int32_t W, float (&m)[8], int (&at)[8]) {
   float v[4][8];
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(256) void h_maxpool_bwd_kernel(const Slot* __restri
     h_unpack8<PREC>(gp[s], g);
     if (masked) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) g[j] *= m[j] > 0.f ? 1.f : slope;
+      for (int j = 0; j < 8; ++j) g[j] *= h_positive_unpacked(m[j]) ? 1.f : slope;
     }
     float r[4][8];
 #pragma unroll

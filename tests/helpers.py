@@ -128,3 +128,57 @@ class profiled:
         if split:
             assert any(line[3] in reach and line[6] > 1 for line in self.lines), \
                 f'{what}: no launch of {sorted(reach)} with split > 1\nM N K kind bm bn split ...\n{self.text}'
+
+
+# ---- device buffers of the per-element kernel tests (test_streaming_ops_gpu.py, test_blocked_streaming_gpu.py) -------------
+GUARD = 64
+PATTERN = 0x4B3C2D1E            # the guard floats' bits (a finite fp32, 12332318.0)
+
+
+class Guarded:
+    """`n` elements `offset` floats past a 16-byte boundary inside a device buffer, GUARD pattern words on each side."""
+
+    def __init__(self, n, init=float('nan'), offset=0, dtype=torch.float32):
+        self.n, self.lo = int(n), GUARD + offset
+        self.buffer = torch.full((self.lo + self.n + GUARD,), PATTERN, dtype=torch.int32, device='cuda')
+        assert self.buffer.data_ptr() % 16 == 0
+        self.window = self.buffer.view(dtype)[self.lo:self.lo + self.n]
+        if torch.is_tensor(init):
+            self.window.copy_(init.reshape(-1).to(dtype))
+        else:
+            self.window.fill_(init)
+
+    @property
+    def ptr(self):
+        return self.window.data_ptr()
+
+    def at(self, element):
+        return self.window.data_ptr() + 4 * int(element)
+
+    def halves(self):
+        """The window as 16-bit words (two per element): a window of blocked bf16 / fp16 slots."""
+        return self.window.view(torch.int16)
+
+    def result(self, what, shape=None):
+        """The window after the call; the guards must be bit-unchanged."""
+        torch.cuda.synchronize()
+        bits = self.buffer.cpu()
+        for name, band in (('below', bits[:self.lo]), ('above', bits[self.lo + self.n:])):
+            touched = (band != PATTERN).nonzero().flatten().tolist()
+            assert not touched, f'{what}: {len(touched)} guard words {name} the window were written, first at {touched[:8]}'
+        return self.window.reshape(shape) if shape is not None else self.window
+
+
+def device(t, offset=0):
+    """A device copy (fp32) that starts `offset` floats past a 16-byte boundary; None stays None."""
+    if t is None:
+        return None
+    holder = torch.empty(t.numel() + 4, device='cuda')
+    assert holder.data_ptr() % 16 == 0
+    view = holder[offset:offset + t.numel()]
+    view.copy_(t.reshape(-1).float())
+    return view
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()

@@ -58,13 +58,11 @@ import pytest
 import torch
 
 import streaming_cases as S
-from helpers import assert_exact
+from helpers import PATTERN, Guarded, assert_exact, device, ptr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float('nan')
-GUARD = 64
-PATTERN = 0x4B3C2D1E            # the guard floats' bits (a finite fp32, 12332318.0)
 
 
 @pytest.fixture(scope='module')
@@ -83,51 +81,6 @@ def check(status, what):
 def stream():
     from srgan_amd import _lib
     return _lib.stream_handle()
-
-
-class Guarded:
-    """`n` elements `offset` floats past a 16-byte boundary inside a device buffer, GUARD pattern words on each side."""
-
-    def __init__(self, n, init=NAN, offset=0, dtype=torch.float32):
-        self.n, self.lo = int(n), GUARD + offset
-        self.buffer = torch.full((self.lo + self.n + GUARD,), PATTERN, dtype=torch.int32, device='cuda')
-        assert self.buffer.data_ptr() % 16 == 0
-        self.window = self.buffer.view(dtype)[self.lo:self.lo + self.n]
-        if torch.is_tensor(init):
-            self.window.copy_(init.reshape(-1).to(dtype))
-        else:
-            self.window.fill_(init)
-
-    @property
-    def ptr(self):
-        return self.window.data_ptr()
-
-    def at(self, element):
-        return self.window.data_ptr() + 4 * int(element)
-
-    def result(self, what, shape=None):
-        """The window after the call; the guards must be bit-unchanged."""
-        torch.cuda.synchronize()
-        bits = self.buffer.cpu()
-        for name, band in (('below', bits[:self.lo]), ('above', bits[self.lo + self.n:])):
-            touched = (band != PATTERN).nonzero().flatten().tolist()
-            assert not touched, f'{what}: {len(touched)} guard words {name} the window were written, first at {touched[:8]}'
-        return self.window.reshape(shape) if shape is not None else self.window
-
-
-def device(t, offset=0):
-    """A device copy (fp32) that starts `offset` floats past a 16-byte boundary; None stays None."""
-    if t is None:
-        return None
-    holder = torch.empty(t.numel() + 4, device='cuda')
-    assert holder.data_ptr() % 16 == 0
-    view = holder[offset:offset + t.numel()]
-    view.copy_(t.reshape(-1).float())
-    return view
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def tile(t, n):
