@@ -780,9 +780,11 @@ int srgan_profile_bytes(double* algorithmic_bytes_total);
  * mixed-precision bench lines price it against the 2.5 PFLOP/s dense bf16 / fp16 peak, the rest against 157.3 TFLOP/s). */
 int srgan_profile_mixed(double* flops, double* kernel_ms);
 /* Per-shape text report of the last profiled region ("M N K kind bm bn split akf bkf count ms bytes" per line; kind:
- * 0 gg_direct, 1 gg_mfma, 2 conv3x3_lds, 3 pointwise, 4 conv3x3_wgrad, 5 gg_rows, 6 pointwise_wgrad,
- * 8 pointwise_ksplit, 9 gg_dot, 10 stem7x7_fwd, 11 stem7x7_wgrad; for kind 2, akf = 1 marks a launch that staged its weights
- * from the weight image); returns the bytes needed. */
+ * 0 gg_direct, 1 gg_mfma, 2 conv3x3_lds, 3 pointwise, 4 conv3x3_wgrad, 5 gg_rows, 6 pointwise_wgrad, (7 unused,)
+ * 8 pointwise_ksplit, 9 gg_dot, 10 stem7x7_fwd, 11 stem7x7_wgrad, 12 stem7x7_bwd_data, 13 pointwise_ring, 14 hconv3x3,
+ * 15 hwgrad3x3, 16 hgemm, 17 hlinear_wgrad, 18 hconv4x4s2, 19 hwgrad4x4s2, 20 bn_stats, 21 bn_fwd, 22 bn_bwd_reduce,
+ * 23 bn_bwd_apply, 24 h_frozen_norm_bwd; for kind 2, akf = 1 marks a launch that staged its weights from the weight image);
+ * returns the bytes needed. */
 int64_t srgan_profile_report(char* buffer, int64_t capacity);
 
 #ifdef __cplusplus

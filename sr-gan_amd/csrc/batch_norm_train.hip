@@ -216,7 +216,7 @@ static int shape_status(int32_t N, int32_t C, int64_t HW, const char* what) {
 // Records of the live profile (srgan_profile_begin / _report): kinds 20 stats, 21 forward, 22 backward reduce, 23 backward
 // apply, each with its algorithmic bytes and 0 FLOP.  bench.py's legend does not name them and its workloads never launch
 // them; a profiled workload with the switch on would count their time in the bracketed kernel time.
-static int finish_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int64_t HW, int kind, int per, int parts, double tensors) {
+static int finish_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int64_t HW, LaunchKind kind, int per, int parts, double tensors) {
   return profile_bracket_end_bytes(slot, stream, C, (int64_t)N * HW, 0, kind, 256, per, parts, 4.0 * tensors * (double)N * C * (double)HW, 0);
 }
 
@@ -233,7 +233,7 @@ int bn_train_stats_run(const float* x, float* mean, float* inv_std, float* runni
     hipLaunchKernelGGL(bn_train_stats_kernel<1>, dim3(C, grid.parts), dim3(256), 0, stream, x, mean, inv_std, running_mean, running_var,
                        reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 20, grid.per, grid.parts, 1.0);
+  finish_bracket(slot, stream, N, C, HW, KIND_BN_STATS, grid.per, grid.parts, 1.0);
   return status;
 }
 
@@ -249,7 +249,7 @@ int bn_train_fwd_run(const float* x, const float* mean, const float* inv_std, co
     hipLaunchKernelGGL(bn_train_fwd_kernel<1>, dim3(C, parts), dim3(256), 0, stream, x, mean, inv_std, gamma, beta, slope, y, N, C,
                        HW, per);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 21, per, parts, 2.0);
+  finish_bracket(slot, stream, N, C, HW, KIND_BN_FWD, per, parts, 2.0);
   return status;
 }
 
@@ -266,7 +266,7 @@ int bn_train_bwd_reduce_run(const float* g, const float* x, const float* mean, c
     hipLaunchKernelGGL(bn_train_bwd_reduce_kernel<1>, dim3(C, grid.parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
                        sums, g_gamma, g_beta, N, C, HW, grid.per, grid.partial, grid.tickets);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 22, grid.per, grid.parts, 2.0);
+  finish_bracket(slot, stream, N, C, HW, KIND_BN_BWD_REDUCE, grid.per, grid.parts, 2.0);
   return status;
 }
 
@@ -284,7 +284,7 @@ int bn_train_bwd_apply_run(const float* g, const float* x, const float* mean, co
     hipLaunchKernelGGL(bn_train_bwd_apply_kernel<1>, dim3(C, parts), dim3(256), 0, stream, g, x, mean, inv_std, gamma, beta, slope,
                        sums, gx, N, C, HW, per, inv_count);
   const int status = launch_status();
-  finish_bracket(slot, stream, N, C, HW, 23, per, parts, 3.0);
+  finish_bracket(slot, stream, N, C, HW, KIND_BN_BWD_APPLY, per, parts, 3.0);
   return status;
 }
 

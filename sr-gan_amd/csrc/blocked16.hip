@@ -1293,12 +1293,12 @@ int srgan_h_conv3x3(const void* x, const void* packed, const float* bias, const 
       }))
     launched = check_precision<>(dtype, "srgan_h_conv3x3 launch");
   if (launched != SRGAN_OK) {
-    profile_bracket_end(slot, s, 0, 0, 0, 14, plan.bm, plan.ni * 128, split);      // close the bracket this call opened
+    profile_bracket_end(slot, s, 0, 0, 0, KIND_HCONV3X3, plan.bm, plan.ni * 128, split);      // close the bracket this call opened
     return launched;
   }
   const int status = launch_status();
   const double pixels = (double)N * H * W;
-  profile_bracket_end_bytes(slot, s, rows_needed, (int64_t)pixels, (int64_t)p.CGI * 8 * 9, 14, plan.bm, plan.ni * 128, split,
+  profile_bracket_end_bytes(slot, s, rows_needed, (int64_t)pixels, (int64_t)p.CGI * 8 * 9, KIND_HCONV3X3, plan.bm, plan.ni * 128, split,
                             2.0 * (pixels * p.CGI * 8 + pixels * p.CGO * 8 * (epi == 2 ? 2 : 1) + (double)rows * p.CGI * 8 * 9), dtype);
   return status;
 }
@@ -1352,7 +1352,7 @@ int srgan_h_conv3x3_wgrad(const void* x, const void* gy, float* gw, int32_t N, i
                        C_out, C_in, p.tiles_ci, walkers, 32 * mb);
   });
   const double pixels = (double)N * H * W;
-  profile_bracket_end_bytes(slot, s, C_out, (int64_t)C_in * 9, (int64_t)pixels, 15, 32 * mb, 64, walkers,
+  profile_bracket_end_bytes(slot, s, C_out, (int64_t)C_in * 9, (int64_t)pixels, KIND_HWGRAD3X3, 32 * mb, 64, walkers,
                             2.0 * pixels * (p.CGX + p.CGY) * 8 + 8.0 * (double)elements, dtype);
   return status;
 }

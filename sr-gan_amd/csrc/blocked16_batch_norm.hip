@@ -355,7 +355,7 @@ static HBnGrid h_bn_grid(int32_t N, int32_t C, int64_t HW, int32_t dtype) {
 
 // Records of the live profile: kinds 20 .. 23 as batch_norm_train.hip, 24 the frozen backward; the algorithmic bytes from the
 // element size.
-static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int64_t HW, int32_t dtype, int kind, const HBnGrid& grid,
+static int h_bn_bracket(int slot, hipStream_t stream, int32_t N, int32_t C, int64_t HW, int32_t dtype, LaunchKind kind, const HBnGrid& grid,
                         double tensors) {
   const double element = dtype == 0 ? 4.0 : 2.0;
   return profile_bracket_end_bytes(slot, stream, C, (int64_t)N * HW, 0, kind, 256, grid.per, grid.parts,
@@ -402,7 +402,7 @@ int h_frozen_norm_bwd_run(const void* s, const void* x, const float* mean, const
     hipLaunchKernelGGL(kernel, dim3(grid.CG, grid.parts), dim3(256), 0, stream, (const Slot*)s, (const Slot*)x, mean, inv_std, gamma,
                        (const Slot*)ref, slope, (Slot*)gx, g_gamma, g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
   });
-  h_bn_bracket(slot, stream, N, C, HW, dtype, 24, grid, 1.0 + (sums == 2) + (gx != nullptr) + (gx && ref));
+  h_bn_bracket(slot, stream, N, C, HW, dtype, KIND_H_FROZEN_NORM_BWD, grid, 1.0 + (sums == 2) + (gx != nullptr) + (gx && ref));
   return status;
 }
 
@@ -426,7 +426,7 @@ int srgan_h_batch_norm_stats(const void* x, float* mean, float* inv_std, float* 
                        running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), momentum, eps, N, C, (int)HW,
                        grid.per, grid.partial, grid.tickets);
   });
-  h_bn_bracket(slot, s, N, C, HW, dtype, 20, grid, 1.0);
+  h_bn_bracket(slot, s, N, C, HW, dtype, KIND_BN_STATS, grid, 1.0);
   return status;
 }
 
@@ -442,7 +442,7 @@ int srgan_h_batch_norm_fwd(const void* x, const float* mean, const float* inv_st
     hipLaunchKernelGGL(h_bn_fwd_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, s, (const Slot*)x, mean, inv_std,
                        gamma, beta, slope, (Slot*)y, N, C, (int)HW, grid.per);
   });
-  h_bn_bracket(slot, s, N, C, HW, dtype, 21, grid, 2.0);
+  h_bn_bracket(slot, s, N, C, HW, dtype, KIND_BN_FWD, grid, 2.0);
   return status;
 }
 
@@ -458,7 +458,7 @@ int srgan_h_batch_norm_bwd_reduce(const void* s, const void* x, const float* mea
     hipLaunchKernelGGL(h_bn_bwd_reduce_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, st, (const Slot*)s,
                        (const Slot*)x, mean, inv_std, sums, g_gamma, g_beta, N, C, (int)HW, grid.per, grid.partial, grid.tickets);
   });
-  h_bn_bracket(slot, st, N, C, HW, dtype, 22, grid, 2.0);
+  h_bn_bracket(slot, st, N, C, HW, dtype, KIND_BN_BWD_REDUCE, grid, 2.0);
   return status;
 }
 
@@ -477,7 +477,7 @@ int srgan_h_batch_norm_bwd_apply(const void* s, const void* x, const float* mean
     hipLaunchKernelGGL(h_bn_bwd_apply_kernel<decltype(prec)::value>, dim3(grid.CG, grid.parts), dim3(256), 0, st, (const Slot*)s,
                        (const Slot*)x, mean, inv_std, gamma, sums, (const Slot*)ref, slope, (Slot*)gx, N, C, (int)HW, grid.per, inv_count);
   });
-  h_bn_bracket(slot, st, N, C, HW, dtype, 23, grid, 3.0);
+  h_bn_bracket(slot, st, N, C, HW, dtype, KIND_BN_BWD_APPLY, grid, 3.0);
   return status;
 }
 

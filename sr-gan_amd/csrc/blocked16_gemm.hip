@@ -373,7 +373,7 @@ int srgan_h_gemm(const void* a, const void* b, const float* bias, const void* re
   const int status = launch_for_precision<1, 2>(dtype, [&](auto prec) {
     hipLaunchKernelGGL(hgemm_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, p);
   });
-  profile_bracket_end_bytes(slot, s, M, N, K, 16, 128, 128, split,
+  profile_bracket_end_bytes(slot, s, M, N, K, KIND_HGEMM, 128, 128, split,
                             2.0 * ((double)M * K + (double)N * K + (double)N * out_cols * (epi == 2 ? 2 : 1)), dtype);
   return status;
 }
@@ -397,7 +397,7 @@ int srgan_h_linear_wgrad(const void* s, const void* x, float* gw, int32_t N, int
   const int status = launch_for_precision<1, 2>(dtype, [&](auto prec) {
     hipLaunchKernelGGL(hlinear_wgrad_kernel<decltype(prec)::value>, grid, dim3(256), 0, hs, p);
   });
-  profile_bracket_end_bytes(slot, hs, M, K, N, 17, 128, 128, 1, 2.0 * (double)N * (M + K) + 8.0 * (double)M * K, dtype);
+  profile_bracket_end_bytes(slot, hs, M, K, N, KIND_HLINEAR_WGRAD, 128, 128, 1, 2.0 * (double)N * (M + K) + 8.0 * (double)M * K, dtype);
   return status;
 }
 

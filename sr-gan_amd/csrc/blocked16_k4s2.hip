@@ -331,7 +331,7 @@ static int hconv2_run(HConv2Params& p, int dtype, int64_t flops_k, hipStream_t s
   if (launched != SRGAN_OK) return launched;
   const int status = launch_status();
   const double positions = (double)p.N * p.GH * p.GW * (p.down ? 1 : 4);       // output pixels
-  profile_bracket_end_bytes(slot, stream, p.CO, (int64_t)positions, flops_k, 18, bm, ni * 128, 1,
+  profile_bracket_end_bytes(slot, stream, p.CO, (int64_t)positions, flops_k, KIND_HCONV4X4S2, bm, ni * 128, 1,
                             16.0 * ((double)p.N * p.CGI * p.IH * p.IW + positions * p.CGO * (p.epi == 2 ? 2 : 1)), dtype);
   return status;
 }
@@ -788,7 +788,7 @@ int srgan_h_k4s2_wgrad(const void* big, const void* small, float* gw, int32_t N,
                        p.tiles_c, walkers, sk, sc);
   });
   const double pixels = (double)N * p.SH * p.SW;
-  profile_bracket_end_bytes(slot, s, C_small, (int64_t)C_big * 16, (int64_t)pixels, 19, 64, 32, walkers,
+  profile_bracket_end_bytes(slot, s, C_small, (int64_t)C_big * 16, (int64_t)pixels, KIND_HWGRAD4X4S2, 64, 32, walkers,
                             2.0 * (pixels * p.CGS * 8 + 4.0 * pixels * p.CGB * 8) + 8.0 * (double)C_small * C_big * 16, dtype);
   return status;
 }

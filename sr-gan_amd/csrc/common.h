@@ -12,7 +12,8 @@ namespace srgan {
 // Status convention of the C ABI (include/srgan_hip.h): 0 ok, <0 argument/shape error, >0 hipError_t.
 enum { SRGAN_OK = 0, SRGAN_EINVAL = -1, SRGAN_EUNSUPPORTED = -2, SRGAN_ERANGE = -3 };
 
-void set_error(const char* fmt, ...);
+void set_error(const char* fmt, ...);      // runtime.hip: the thread-local message behind srgan_last_error()
+const char* last_error();
 
 #define SRGAN_HIP(expr)                                                                  \
   do {                                                                                   \

@@ -877,10 +877,10 @@ int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int
 
 // out = conv3x3(in, w) (+ bias), generic weight strides (forward and flipped-tap data gradient share the kernel).
 // The caller guarantees dense-or-strided NCHW, 3x3 / stride 1 / pad 1.  `accumulate` adds into out.
-int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, int32_t w_so, int32_t w_si, int32_t w_skh,
-                int32_t w_skw, const float* bias, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t H,
-                int32_t W, int accumulate, hipStream_t stream, const float* const* bn, const BnBackwardEpilogue* epilogue,
-                int precision, const Conv3Placement* placement, const float* w_image) {
+int conv3x3_run(const float* in, int64_t in_bs, const Conv3Weights& weights, const float* bias, float* out, int64_t out_bs, int32_t N,
+                int32_t CI, int32_t CO, int32_t H, int32_t W, int accumulate, hipStream_t stream, const float* const* bn,
+                const BnBackwardEpilogue* epilogue, int precision, const Conv3Placement* placement) {
+  const float* w_image = weights.image;
   // SRGAN_NO_CONV3_IMAGE=1 (read once): the weight image is ignored and the weights are gathered from w, so that a test or
   // bench.py reaches the reference path through the same calls
   static const bool no_image = getenv("SRGAN_NO_CONV3_IMAGE") != nullptr && atoi(getenv("SRGAN_NO_CONV3_IMAGE")) == 1;
@@ -898,14 +898,14 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
                 "conv3x3 tap subsets / strided output: plain kernel only");
   SRGAN_REQUIRE(precision == 0 || (bn == nullptr && epilogue == nullptr), SRGAN_EUNSUPPORTED,
                 "conv3x3 mixed precision: the fused batch-norm forms are fp32");
-  p.in = in; p.w = w; p.out = out; p.bias = bias;
+  p.in = in; p.w = weights.w; p.out = out; p.bias = bias;
   p.bn_mean = bn ? bn[0] : nullptr; p.bn_inv = bn ? bn[1] : nullptr;
   p.bn_gamma = bn ? bn[2] : nullptr; p.bn_beta = bn ? bn[3] : nullptr;
   p.epi_x = nullptr; p.epi_x_bs = 0; p.epi_partial = nullptr; p.epi_tiles = 0; p.w_packed = nullptr;
   SRGAN_REQUIRE(bn == nullptr || CI <= CONV3_PRO_MAX_CI, SRGAN_EUNSUPPORTED, "conv3x3 fused batch-norm channel count");
   p.N = N; p.CI = CI; p.CO = CO; p.H = H; p.W = W;
   p.in_bs = in_bs; p.out_bs = out_bs;
-  p.w_so = w_so; p.w_si = w_si; p.w_skh = w_skh; p.w_skw = w_skw; p.w_base = w_base;
+  p.w_so = weights.so; p.w_si = weights.si; p.w_skh = weights.skh; p.w_skw = weights.skw; p.w_base = weights.base;
   const Conv3Plan plan = conv3x3_plan(N, CI, CO, H, W, epilogue == nullptr, precision, placement == nullptr);   // (the epilogue needs whole sums per workgroup)
   const int bm = plan.bm, th = plan.th, tw = plan.tw, split = plan.split;
   p.tiles_x = plan.tiles_x; p.tiles_y = plan.tiles_y; p.tiles_m = plan.tiles_m;
@@ -975,7 +975,7 @@ int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, 
   const int status = launch_status();
   const int64_t pixels3 = (int64_t)N * H * W;       // (+ x read by the fused batch-norm backward epilogue)
   // (the report's akf column: 1 = the weights were staged from the weight image)
-  profile_bracket_end(profile_slot, stream, CO, pixels3, (int64_t)CI * __builtin_popcount((unsigned)p.taps), 2, bm, th * 32, split,
+  profile_bracket_end(profile_slot, stream, CO, pixels3, (int64_t)CI * __builtin_popcount((unsigned)p.taps), KIND_CONV3X3_LDS, bm, th * 32, split,
                       (precision == 0 && p.w_packed) ? 1 : 0, 0,
                       (int64_t)CI * pixels3 + (epilogue ? (int64_t)CO * pixels3 : 0), precision);
   return status;

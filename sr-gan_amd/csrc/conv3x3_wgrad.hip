@@ -494,7 +494,7 @@ int conv3x3_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
     hipLaunchKernelGGL(conv3x3_wgrad_finish_kernel, dim3(WG3_FINISH_SLABS, (unsigned)(ci_chunks * co_chunks)), dim3(256), 0, stream, p,
                        walkers, ci_chunks);
   const int status = launch_status();
-  profile_bracket_end(profile_slot, stream, CO, (int64_t)CI * 9, (int64_t)N * H * W, 4, th, WG3_TW, walkers, 0, 0, 0, precision);
+  profile_bracket_end(profile_slot, stream, CO, (int64_t)CI * 9, (int64_t)N * H * W, KIND_CONV3X3_WGRAD, th, WG3_TW, walkers, 0, 0, 0, precision);
   return status;
 }
 
@@ -546,7 +546,7 @@ int conv3x3_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, int
     hipLaunchKernelGGL(conv3x3_wgrad_grouped_finish_kernel, dim3(WG3_FINISH_SLABS, (unsigned)grid_y, (unsigned)count), dim3(256), 0, stream,
                        reinterpret_cast<const Wgrad3Job*>(jobs), gw_base, partial_base);
   const int status = launch_status();
-  profile_bracket_end(profile_slot, stream, 1, flops_mn, pixels, 4, 4, WG3_TW, grid_x, 0, 0, elements > pixels ? elements - pixels : 0);
+  profile_bracket_end(profile_slot, stream, 1, flops_mn, pixels, KIND_CONV3X3_WGRAD, 4, WG3_TW, grid_x, 0, 0, elements > pixels ? elements - pixels : 0);
   return status;
 }
 

@@ -1,4 +1,6 @@
-// gather_gemm_kernels.hip -- the MFMA contraction kernel behind every convolution / linear pass.
+// gather_gemm_kernels.hip -- the MFMA contraction kernel behind every convolution / linear pass that has no kernel of its
+// own, its VALU siblings for skinny shapes, their launcher (gg_run_group) and srgan_gemm.  The convolution entry points that
+// route to it are in conv_dispatch.hip.
 //
 // One 256-thread workgroup (4 wavefronts of 64) owns a BM x BN tile of C.  Per K-step of 16 the tile's A
 // (BM x 16) and B (16 x BN) slices are gathered from HBM into registers (next step's loads are issued
@@ -14,29 +16,11 @@
 #include "gather_gemm.h"
 #include "conv_plan.h"
 #include "launchers.h"
-#include <stdarg.h>
-#include <string.h>
 #include <stdlib.h>
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <type_traits>
-#include <utility>
+#include <vector>
 
 namespace srgan {
-
-static thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof(g_error), fmt, ap);
-  va_end(ap);
-}
-
-const char* last_error() { return g_error; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -575,78 +559,31 @@ __global__ __launch_bounds__(256) void gg_reduce_partials_wide_kernel(const Gath
 
 __device__ unsigned int g_gg_split_tickets[SPLIT_TICKET_SETS * SPLIT_TICKET_TILES];
 
-// Partial sums that a second small kernel combines go through a workspace the CALLER owns (srgan_set_workspace: one
-// block per (device, stream), at least srgan_workspace_bytes() long; launches on one stream are ordered, so reuse is
-// safe): the K-slices of split-K launches with a tiny output (M*N < 512 outputs x at most 1024 slices x 4 B = 2 MiB) and
-// the per-workgroup batch-norm parameter sums of the fused data-gradient epilogues (2 x column blocks x channels x 4 B =
-// at most 1/32 of the gradient tensor's bytes: 64 MiB covers tensors of up to 2^29 elements; larger ones report "unsupported"
-// from srgan_conv2d_bnrelu_supported and take the two-kernel form).  The library never allocates device memory.
-constexpr size_t WORKSPACE_BYTES = (size_t)256 << 20;     // (round 5: 256 MiB -- the partial tiles of every K split / grouped weight gradient live here)
-struct WorkspaceSlot { float* ptr = nullptr; size_t bytes = 0; int index = -1; };
-static std::mutex g_workspace_mutex;
-static std::map<std::pair<int, hipStream_t>, WorkspaceSlot> g_workspaces;
-static int g_workspace_count[16] = {};        // ticket sets handed out, per device (the ticket arrays are per-device symbols)
-
-// Unregistering (ptr == NULL) keeps the slot and its ticket-set index: a stream that registers again -- a caller that tears its
-// workspace down between phases -- gets the SAME set back, so the 64 sets per device are not used up by re-registration (ADVICE
-// r5: the index used to be re-drawn, and past 64 the ordered finish silently fell back to fp32 atomics).  A stream beyond the
-// 64th of a device has index >= SPLIT_TICKET_SETS and srgan_split_is_ordered() reports 0 for it.
-int workspace_register(float* ptr, size_t bytes, hipStream_t stream) {
-  int device = 0;
-  SRGAN_HIP(hipGetDevice(&device));
-  std::lock_guard<std::mutex> lock(g_workspace_mutex);
-  WorkspaceSlot& slot = g_workspaces[{device, stream}];
-  slot.ptr = ptr; slot.bytes = ptr ? bytes : 0;
-  if (slot.index < 0 && ptr != nullptr) slot.index = g_workspace_count[device & 15]++;
-  return SRGAN_OK;
-}
-
-// A small integer per registered (device, stream): kernels that keep a few words of device-global state between the
-// workgroups of ONE launch (reduce.hip's row tickets) index it by this, so that streams never share a set.
-int workspace_index(hipStream_t stream) {
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return -1;
-  std::lock_guard<std::mutex> lock(g_workspace_mutex);
-  auto found = g_workspaces.find({device, stream});
-  return (found == g_workspaces.end() || found->second.ptr == nullptr) ? -1 : found->second.index;
-}
-
-size_t workspace_capacity() { return WORKSPACE_BYTES; }
-
-float* partial_workspace(size_t bytes, hipStream_t stream) {
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(g_workspace_mutex);
-  auto found = g_workspaces.find({device, stream});
-  if (found == g_workspaces.end() || found->second.ptr == nullptr || found->second.bytes < bytes) return nullptr;
-  return found->second.ptr;
-}
-
 // ------------------------------------------------------------------------------------------- launcher
-struct GGConfig { int kind; int bm, bn; int tiles; };   // kind 0 direct, 1 mfma
+// (GGConfig, gg_prepare and gg_launch are private to this file: other translation units go through gg_run_group)
+namespace { struct GGConfig { LaunchKind kind; int bm, bn; int tiles; }; }   // kind: one of the four KIND_GG_*
 constexpr int GG_TILE_TARGET = 1024;      // workgroups a launch aims for (4 per CU): choose_config's tile, choose_split's K split
-constexpr int CONV3_MIN_WIDTH = 7;        // narrowest plane of the LDS-halo 3x3 kernel (the 14- and 7-wide planes at 224)
 
 static GGConfig choose_config(const GatherGemm& p, int force) {
   GGConfig c;
   // M <= 2 (single-channel map heads, count layers): the direct form; from 3 rows up (RGB image gradients, generator
   // output) the MFMA tile wins even at 3/32 row utilisation because the direct form is VALU/latency bound.
   if ((p.M <= 2 && force != 2) || force == 1) {
-    c.kind = 0; c.bm = 1; c.bn = 256;
+    c.kind = KIND_GG_DIRECT; c.bm = 1; c.bn = 256;
     c.tiles = p.M * ((p.N + 255) / 256);
     return c;
   }
-  if (force == 0 && p.M <= 8 && p.N <= 8 && p.K >= 65536) {     // kind 9: lanes along K
-    c.kind = 9; c.bm = 8; c.bn = 8;
+  if (force == 0 && p.M <= 8 && p.N <= 8 && p.K >= 65536) {     // lanes along K
+    c.kind = KIND_GG_DOT; c.bm = 8; c.bn = 8;
     c.tiles = 1;
     return c;
   }
-  if (force == 0 && p.M <= 8 && p.N >= 4096) {     // kind 5: the few-rows kernel
-    c.kind = 5; c.bm = p.M <= 4 ? 4 : 8; c.bn = 256;
+  if (force == 0 && p.M <= 8 && p.N >= 4096) {     // the few-rows kernel
+    c.kind = KIND_GG_ROWS; c.bm = p.M <= 4 ? 4 : 8; c.bn = 256;
     c.tiles = (p.N + 255) / 256;
     return c;
   }
-  c.kind = 1;
+  c.kind = KIND_GG_MFMA;
   // Largest tile that still yields >= target workgroups (4 per CU: staging of one hides under the MFMAs of the
   // others); otherwise the smallest tile of the class, topped up by split-K in choose_split.
   static const int candidates[3][3][2] = {{{128, 128}, {128, 64}, {64, 64}},     // M > 64
@@ -684,12 +621,13 @@ static void choose_split(GatherGemm& p, const GGConfig& c, bool allow_split) {
   p.split_k = (p.K + per - 1) / per;
 }
 
-template <int BM, int BN, int WGM, bool VEC>
-static void launch_mfma_v(const GatherGemm& p, dim3 grid, hipStream_t stream) {
-  if (p.a_kfast && p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, true, VEC>), grid, dim3(256), 0, stream, p);
-  else if (p.a_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, false, VEC>), grid, dim3(256), 0, stream, p);
-  else if (p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, true, VEC>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, false, VEC>), grid, dim3(256), 0, stream, p);
+// The staging orders of one tile and operand type: lanes along k or along m / n, per operand.
+template <int BM, int BN, int WGM, bool VEC, int PREC>
+static void launch_mfma_staged(const GatherGemm& p, dim3 grid, hipStream_t stream) {
+  if (p.a_kfast && p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, true, VEC, PREC>), grid, dim3(256), 0, stream, p);
+  else if (p.a_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, false, VEC, PREC>), grid, dim3(256), 0, stream, p);
+  else if (p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, true, VEC, PREC>), grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, false, VEC, PREC>), grid, dim3(256), 0, stream, p);
 }
 
 // Can a Dec3 be walked in aligned groups of 4 consecutive indices with unit element stride?
@@ -716,34 +654,24 @@ static bool vec_eligible(const GatherGemm& p) {
   return a && b && p.K % 4 == 0;
 }
 
-template <int BM, int BN, int WGM, int PREC>
-static void launch_mfma_mixed(const GatherGemm& p, dim3 grid, hipStream_t stream) {
-  if (p.a_kfast && p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, true, false, PREC>), grid, dim3(256), 0, stream, p);
-  else if (p.a_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, true, false, false, PREC>), grid, dim3(256), 0, stream, p);
-  else if (p.b_kfast) hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, true, false, PREC>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((gg_mfma_kernel<BM, BN, WGM, false, false, false, PREC>), grid, dim3(256), 0, stream, p);
-}
-
 template <int BM, int BN, int WGM>
 static void launch_mfma(const GatherGemm& p, dim3 grid, hipStream_t stream) {
-  if (p.precision == 1) launch_mfma_mixed<BM, BN, WGM, 1>(p, grid, stream);        // (scalar staging only)
-  else if (p.precision == 2) launch_mfma_mixed<BM, BN, WGM, 2>(p, grid, stream);
-  else if (vec_eligible(p)) launch_mfma_v<BM, BN, WGM, true>(p, grid, stream);
-  else launch_mfma_v<BM, BN, WGM, false>(p, grid, stream);
+  if (p.precision == 1) launch_mfma_staged<BM, BN, WGM, false, 1>(p, grid, stream);        // (scalar staging only)
+  else if (p.precision == 2) launch_mfma_staged<BM, BN, WGM, false, 2>(p, grid, stream);
+  else if (vec_eligible(p)) launch_mfma_staged<BM, BN, WGM, true, 0>(p, grid, stream);
+  else launch_mfma_staged<BM, BN, WGM, false, 0>(p, grid, stream);
 }
 
-// Plans one launch: fills split_k / k_per_split; returns whether the launch needs a zeroed (or live) C because
-// it combines K-slices with atomics.
 // The launch's accumulators per workgroup for the ordered finish (see gg_mfma_kernel: MI x NI fragments of 16 per lane).
 static int64_t mfma_tile_floats(const GGConfig& c) { return (int64_t)c.bm * c.bn; }
 
 // Plans one launch: fills split_k / k_per_split and how its K slices are combined (p.use_partial, a SplitCombine); returns
 // whether the launch needs a zeroed (or live) C because it combines them with fp32 atomics -- only when the stream has
 // no workspace (or SRGAN_ATOMIC_SPLIT=1): otherwise the slices meet in a fixed order, through the workspace.
-bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
+static bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
   p.tickets = nullptr;
   GGConfig c = choose_config(p, force);
-  if (c.kind == 9) {                       // workgroups of 256 k-lanes, ~16 k per thread
+  if (c.kind == KIND_GG_DOT) {             // workgroups of 256 k-lanes, ~16 k per thread
     int groups = (p.K + 4095) / 4096;
     if (groups > 1024) groups = 1024;
     p.split_k = groups; p.k_per_split = p.K;
@@ -754,9 +682,9 @@ bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
   p.use_partial = GG_COMBINE_ATOMIC;
   if (p.split_k <= 1) return false;
   const int64_t mn = (int64_t)p.M * p.N;
-  const bool fits = (size_t)mn * p.split_k * sizeof(float) <= WORKSPACE_BYTES;
+  const bool fits = (size_t)mn * p.split_k * sizeof(float) <= workspace_capacity();
   // (up to 4096 outputs: at 960 outputs x 1024 slices the atomics still serialised -- 310 us for 36 MB of operands)
-  if (c.kind == 1 && p.split_k >= 16 && mn <= 4096 && fits) {
+  if (c.kind == KIND_GG_MFMA && p.split_k >= 16 && mn <= 4096 && fits) {
     p.use_partial = GG_COMBINE_PARTIAL_TINY;
     return false;
   }
@@ -765,162 +693,17 @@ bool gg_prepare(GatherGemm& p, int force, GGConfig* out, hipStream_t stream) {
     // few slices of an MFMA launch: the tile's last workgroup adds them (one launch); many slices, or the VALU kernels:
     // partial outputs + a second kernel that adds the slices of every output in slice order
     int set = -1;
-    if (c.kind == 1 && p.split_k <= 16 &&
+    if (c.kind == KIND_GG_MFMA && p.split_k <= 16 &&
         split_workspace(c.tiles, p.split_k, mfma_tile_floats(c), 0, stream, &set) != nullptr) {
       p.use_partial = GG_COMBINE_ORDERED;
       return false;
     }
     if (fits) {
-      p.use_partial = (c.kind == 1 && mn <= 4096) ? GG_COMBINE_PARTIAL_TINY : GG_COMBINE_PARTIAL_WIDE;
+      p.use_partial = (c.kind == KIND_GG_MFMA && mn <= 4096) ? GG_COMBINE_PARTIAL_TINY : GG_COMBINE_PARTIAL_WIDE;
       return false;
     }
   }
   return true;
-}
-
-// ---- optional live timing of every contraction launch with HIP events on the launch stream -------------------
-// (bench.py: roofline.achieved = sum of logical 2*M*N*K over launches / sum of their event-timed durations)
-struct ProfileRecord { int32_t M, N, K, kind, bm, bn, split, akf, bkf; double bytes; int32_t precision; };
-// Algorithmic HBM bytes of one contraction launch: every operand element once, 4 B each.  `taps` = how many times the
-// gather visits one element of the big operand (9 for a 3x3 kernel, R*S of a strided one divided over its classes).
-static double algorithmic_bytes(double M, double N, double K, int kind) {
-  if (kind == 2) return 4.0 * (M * N + M * K + (K / 9.0) * N);     // conv3x3: K = CI * 9 taps over one input plane
-  if (kind == 4) return 4.0 * (M * N + M * K + (N / 9.0) * K);     // conv3x3 weight gradient: N = CI * 9
-  return 4.0 * (M * N + M * K + K * N);
-}
-struct ProfileState {
-  std::atomic<bool> enabled{false};
-  std::mutex mutex;                   // guards every other member (launches may come from several host threads)
-  std::vector<hipEvent_t> events;     // two per slot: start, stop
-  std::vector<ProfileRecord> records; // one per slot (M < 0: begun, not ended)
-  size_t slots = 0;
-  double flops = 0.0, mfma_flops = 0.0, bytes = 0.0;
-  int64_t launches = 0;
-};
-static ProfileState g_profile;
-
-static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStream_t stream);
-
-// Event bracket around one contraction launch (also called from the other translation units).  begin() reserves a slot
-// and records its start event on the launch stream; returns -1 when profiling is off.
-int profile_bracket_begin(hipStream_t stream) {
-  if (!g_profile.enabled.load(std::memory_order_acquire)) return -1;
-  hipEvent_t start;
-  int slot;
-  {
-    std::lock_guard<std::mutex> lock(g_profile.mutex);
-    slot = (int)g_profile.slots++;
-    while (g_profile.events.size() < 2 * g_profile.slots) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) { --g_profile.slots; return -1; }
-      g_profile.events.push_back(e);
-    }
-    g_profile.records.resize(g_profile.slots, ProfileRecord{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0});
-    start = g_profile.events[2 * slot];
-  }
-  if (hipEventRecord(start, stream) != hipSuccess) return -1;
-  return slot;
-}
-
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn, int split,
-                        int akf, int bkf, int64_t b_unique, int precision) {
-  if (slot < 0) return SRGAN_OK;
-  hipEvent_t stop;
-  {
-    std::lock_guard<std::mutex> lock(g_profile.mutex);
-    if ((size_t)slot >= g_profile.slots) return SRGAN_OK;          // the region was closed in between
-    stop = g_profile.events[2 * slot + 1];
-    const double f = 2.0 * (double)M * (double)N * (double)K;
-    const double bytes = b_unique > 0 ? 4.0 * ((double)M * N + (double)M * K + (double)b_unique)
-                                      : algorithmic_bytes((double)M, (double)N, (double)K, kind);
-    g_profile.records[slot] = ProfileRecord{(int32_t)M, (int32_t)N, (int32_t)K, kind, bm, bn, split, akf, bkf, bytes, precision};
-    g_profile.flops += f;
-    if (kind != 0 && kind != 5 && kind != 9 && kind != 12) g_profile.mfma_flops += f;      // direct / few-rows / lanes-along-K / stem data gradient: VALU
-    g_profile.bytes += bytes;
-    g_profile.launches += 1;
-  }
-  SRGAN_HIP(hipEventRecord(stop, stream));
-  return SRGAN_OK;
-}
-
-// The same bracket end for a launch that states its own algorithmic bytes (the 16-bit kernels of blocked16*.hip: kinds 14
-// hconv3x3, 15 hwgrad3x3, 16 hgemm, 17 hlinear_wgrad, 18 hconv4x4s2, 19 hwgrad4x4s2).
-int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn, int split,
-                              double bytes, int precision) {
-  if (slot < 0) return SRGAN_OK;
-  hipEvent_t stop;
-  {
-    std::lock_guard<std::mutex> lock(g_profile.mutex);
-    if ((size_t)slot >= g_profile.slots) return SRGAN_OK;
-    stop = g_profile.events[2 * slot + 1];
-    const double f = 2.0 * (double)M * (double)N * (double)K;
-    g_profile.records[slot] = ProfileRecord{(int32_t)M, (int32_t)N, (int32_t)K, kind, bm, bn, split, 0, 0, bytes, precision};
-    g_profile.flops += f;
-    g_profile.mfma_flops += f;
-    g_profile.bytes += bytes;
-    g_profile.launches += 1;
-  }
-  SRGAN_HIP(hipEventRecord(stop, stream));
-  return SRGAN_OK;
-}
-
-// 1x1 / stride 1 / unpadded: the register-streamed pointwise kernel (any plane size: an image's last 32-pixel group may
-// be ragged; planes of fewer than 32 pixels stay on the generic kernel).
-static bool use_pointwise(const ConvGeom& g, int out_channels, int force) {
-  const int in_channels = out_channels == g.K ? g.C : g.K;     // forward: C -> K; data gradient: K -> C
-  const bool plane_ok = g.H * g.W >= 32;       // (geom_ok: H, W >= 1)
-  return force == 0 && pointwise(g) && plane_ok && out_channels >= 8 && in_channels % 2 == 0;
-}
-
-// 3x3 / stride 1 / pad 1 with enough width to fill most of a 16-pixel tile row (two image rows share a 32-pixel MFMA
-// column block): the LDS-halo kernel.
-static bool use_conv3x3(const ConvGeom& g, int out_channels, int force) {
-  return force == 0 && g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 &&
-         g.W >= CONV3_MIN_WIDTH && out_channels >= 8;
-}
-
-// Mixed precision also takes the 4 x 4 planes (whole images side by side in a tile: conv3x3_mixed_small_kernel) and
-// fewer than 8 output channels -- the gradient with respect to a 3-channel image, which the penalty chain of the VGG / DCGAN
-// discriminators asks for (reference srgan.py:366-370): 29 of a 32-row tile's rows are padding there, and the generic
-// kernel's gather still made it six times slower (5.9 TF/s on [3 x 524 288] x 576).
-static bool use_conv3x3_mixed(const ConvGeom& g, int out_channels) {
-  if (use_conv3x3(g, out_channels, 0)) return true;
-  const bool geometry = g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1;
-  if (!geometry) return false;
-  return (g.H == 4 && g.W == 4 && out_channels >= 8) || (g.W >= CONV3_MIN_WIDTH && out_channels >= 1);
-}
-
-// Weight gradient of a 3x3 / stride 1 / pad 1 convolution with at least one wave's worth of input channels: the
-// LDS-patch kernel of conv3x3_wgrad.hip.
-// `aligned_only`: widths that are a multiple of 4 with 16-byte aligned rows (the float4 staging; the mixed-precision
-// variants have no other); otherwise the kernel's ragged variant also takes the 14- and 7-wide planes of 224 x 224.
-static bool wgrad3x3_geometry(const ConvGeom& g, int min_width = 7, bool aligned_only = false) {
-  const bool aligned = g.W % 4 == 0 && g.x_bs % 4 == 0 && g.y_bs % 4 == 0;
-  if (!aligned && aligned_only) return false;
-  return g.R == 3 && g.S == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.W >= min_width && g.C >= 32;
-}
-
-static bool use_wgrad3x3(const ConvGeom& g, const float* x, const float* gy, int force) {
-  return force == 0 && wgrad3x3_geometry(g);
-}
-
-static bool pointwise_wgrad_geometry(const ConvGeom& g) {
-  return pointwise(g) && g.H * g.W >= 32 && g.C >= 16 && g.K >= 16;
-}
-
-// Weight gradient of a 1x1 / stride 1 convolution: the register-streamed kernel of pointwise_wgrad.hip (whole 32-pixel
-// chunks with 16-byte aligned rows, or its ragged variant).
-static bool use_pointwise_wgrad(const ConvGeom& g, const float* x, const float* gy, int force) {
-  return force == 0 && pointwise_wgrad_enabled() && pointwise_wgrad_geometry(g);
-}
-
-int gg_launch(const GatherGemm& p, const GGConfig& c, hipStream_t stream) {
-  if (p.M <= 0 || p.N <= 0) return SRGAN_OK;
-  const int slot = profile_bracket_begin(stream);
-  const int status = gg_launch_unprofiled(p, c, stream);
-  profile_bracket_end(slot, stream, p.M, p.N, p.K, c.kind, c.bm, c.bn, p.split_k, p.a_kfast, p.b_kfast, p.b_unique,
-                      c.kind == 1 ? p.precision : 0);
-  return status;
 }
 
 static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStream_t stream) {
@@ -943,7 +726,7 @@ static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStrea
     return launch_status();
   }
   if (p.split_k > 1 && p.use_partial == GG_COMBINE_ORDERED) {
-    SRGAN_REQUIRE(c.kind == 1 && (p.mode == GG_STORE || p.mode == GG_ACCUMULATE), SRGAN_EINVAL, "ordered split launch mode");
+    SRGAN_REQUIRE(c.kind == KIND_GG_MFMA && (p.mode == GG_STORE || p.mode == GG_ACCUMULATE), SRGAN_EINVAL, "ordered split launch mode");
     int set = -1;
     float* ws = split_workspace(c.tiles, p.split_k, mfma_tile_floats(c), 0, stream, &set);
     unsigned int* tickets = ws ? device_tickets(g_gg_split_tickets) : nullptr;
@@ -953,7 +736,7 @@ static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStrea
     q.partial = ws; q.tickets = tickets + (size_t)set * SPLIT_TICKET_TILES; q.use_partial = GG_COMBINE_ATOMIC;
     return gg_launch_unprofiled(q, c, stream);
   }
-  if (c.kind == 0) {
+  if (c.kind == KIND_GG_DIRECT) {
     dim3 grid((p.N + 255) / 256, p.M, p.split_k);
     SRGAN_REQUIRE(p.M <= 65535 && p.split_k <= 65535, SRGAN_ERANGE, "direct gather-gemm grid");
     hipLaunchKernelGGL(gg_direct_kernel, grid, dim3(256), 0, stream, p);
@@ -961,11 +744,11 @@ static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStrea
   }
   dim3 grid(c.tiles, p.split_k, 1);
   SRGAN_REQUIRE(p.split_k <= 65535, SRGAN_ERANGE, "split-k grid");
-  if (c.kind == 9) {
+  if (c.kind == KIND_GG_DOT) {
     hipLaunchKernelGGL(gg_dot_kernel, dim3(p.split_k), dim3(256), 0, stream, p);
     return launch_status();
   }
-  if (c.kind == 5) {
+  if (c.kind == KIND_GG_ROWS) {
     if (c.bm == 4) hipLaunchKernelGGL(gg_rows_kernel<4>, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gg_rows_kernel<8>, grid, dim3(256), 0, stream, p);
     return launch_status();
@@ -979,14 +762,26 @@ static int gg_launch_unprofiled(const GatherGemm& p, const GGConfig& c, hipStrea
   return launch_status();
 }
 
-// Runs a group of plans that together define one dense output tensor of c_elems floats.  `accumulate` adds
-// into the existing contents; otherwise the output is (over)written.  force: 0 auto, 1 direct, 2 mfma.
-int gg_run_group(std::vector<GatherGemm>& plans, float* c_base, int64_t c_elems, int accumulate, int force,
-                 hipStream_t stream) {
+static int gg_launch(const GatherGemm& p, const GGConfig& c, hipStream_t stream) {
+  if (p.M <= 0 || p.N <= 0) return SRGAN_OK;
+  const int slot = profile_bracket_begin(stream);
+  const int status = gg_launch_unprofiled(p, c, stream);
+  profile_bracket_end(slot, stream, p.M, p.N, p.K, c.kind, c.bm, c.bn, p.split_k, p.a_kfast, p.b_kfast, p.b_unique,
+                      c.kind == KIND_GG_MFMA ? p.precision : 0);
+  return status;
+}
+
+// Runs a group of plans that together define one output tensor (launchers.h): c_rows rows of c_width floats, c_pitch apart.
+int gg_run_group(std::vector<GatherGemm>& plans, float* c_base, int64_t c_pitch, int64_t c_width, int64_t c_rows, int accumulate,
+                 int force, hipStream_t stream) {
   std::vector<GGConfig> configs(plans.size());
   bool any_atomic = false;
   for (size_t i = 0; i < plans.size(); ++i) any_atomic |= gg_prepare(plans[i], force, &configs[i], stream);
-  if (any_atomic && !accumulate) if (const int status = zero_floats(c_base, c_elems, stream)) return status;
+  if (any_atomic && !accumulate) {          // (a strided view -- a channel slice of a wider buffer -- is zeroed row by row)
+    const int status = c_pitch == c_width ? zero_floats(c_base, c_width * c_rows, stream)
+                                          : zero_rows(c_base, c_pitch, c_width, c_rows, stream);
+    if (status != SRGAN_OK) return status;
+  }
   for (size_t i = 0; i < plans.size(); ++i) {
     GatherGemm& p = plans[i];
     if (p.split_k > 1 && p.use_partial == GG_COMBINE_ATOMIC) p.mode = GG_ATOMIC;
@@ -1004,447 +799,6 @@ using namespace srgan;
 
 extern "C" {
 
-static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
-
-static bool to_geom(const srgan_conv_desc* d, ConvGeom& g) {
-  if (d == nullptr) return false;
-  g.N = d->N; g.C = d->C; g.H = d->H; g.W = d->W; g.K = d->K; g.R = d->R; g.S = d->S;
-  g.sh = d->stride_h; g.sw = d->stride_w; g.ph = d->pad_h; g.pw = d->pad_w; g.OH = d->OH; g.OW = d->OW;
-  g.x_bs = d->x_batch_stride; g.y_bs = d->y_batch_stride;
-  return geom_ok(g);
-}
-
-// Descriptor -> geometry with the two failure classes kept apart: a malformed descriptor (-1) and one whose tensors pass
-// the 2^31-element limit of the 32-bit offsets (-3, with the extent in the message so that the caller can split the batch).
-#define SRGAN_GEOM(desc, g, what)                                                                        \
-  do {                                                                                                   \
-    SRGAN_REQUIRE(to_geom(desc, g), SRGAN_EINVAL, what " geometry");                                     \
-    if (geom_largest_extent(g) >= ((int64_t)1 << 31)) {                                                  \
-      set_error(what ": a tensor of %lld elements (batch %d) exceeds the 2^31 - 1 element limit",       \
-                (long long)geom_largest_extent(g), (int)g.N);                                            \
-      return SRGAN_ERANGE;                                                                               \
-    }                                                                                                    \
-  } while (0)
-
-const char* srgan_last_error(void) { return last_error(); }
-
-int srgan_conv2d_fwd(const srgan_conv_desc* desc, const float* x, const float* w, const float* bias, float* y,
-                     int force_kernel, void* stream) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_fwd");
-  SRGAN_REQUIRE(x && w && y, SRGAN_EINVAL, "srgan_conv2d_fwd pointers");
-  const int dtype = desc->compute_dtype;
-  SRGAN_REQUIRE(dtype_ok(dtype), SRGAN_EINVAL, "srgan_conv2d_fwd compute_dtype");
-  if (dtype && force_kernel == 0 && use_conv3x3_mixed(g, g.K))     // mixed precision: the LDS-halo 3x3 kernel, or
-    return conv3x3_run(x, g.x_bs, w, 0, g.C * 9, 9, 3, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H, g.W, 0, (hipStream_t)stream,
-                       nullptr, nullptr, dtype);
-  if (dtype) force_kernel = 2;                                      // the generic MFMA kernel for every other geometry
-  if (use_pointwise(g, g.K, force_kernel) && ((uintptr_t)w & 15) == 0 &&
-      pointwise_ksplit_wanted(g.N, g.C, g.K, g.H * g.W, false))
-    return pointwise_ksplit_run(x, g.x_bs, w, bias, y, g.y_bs, g.N, g.C, g.K, g.H * g.W, 0, (hipStream_t)stream, nullptr);
-  if (use_pointwise(g, g.K, force_kernel))
-    return pointwise_run(x, g.x_bs, w, g.C, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H * g.W, 0, (hipStream_t)stream);
-  if (use_conv3x3(g, g.K, force_kernel))
-    return conv3x3_run(x, g.x_bs, w, 0, g.C * 9, 9, 3, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H, g.W, 0,
-                       (hipStream_t)stream);
-  if (force_kernel == 0 && dtype == 0 && bias == nullptr &&
-      stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw))
-    return stem7x7_fwd_run(x, g.x_bs, w, y, g.y_bs, g.N, g.H, g.W, g.K, g.OH, g.OW, (hipStream_t)stream);
-  std::vector<GatherGemm> plans{plan_conv_fwd(g, x, w, bias, y)};
-  plans[0].precision = dtype;
-  // A strided-batch output view (a channel slice of a wider buffer) is zeroed with a 2-D memset when the launch
-  // combines K-slices with atomics.
-  const bool dense_out = g.y_bs == (int64_t)g.K * g.OH * g.OW;
-  if (!dense_out) {
-    GGConfig c;
-    const bool atomic = gg_prepare(plans[0], force_kernel, &c, (hipStream_t)stream);
-    if (atomic) {
-      if (const int status = zero_rows(y, g.y_bs, (int64_t)g.K * g.OH * g.OW, g.N, (hipStream_t)stream)) return status;
-      plans[0].mode = GG_ATOMIC;
-    } else {
-      plans[0].mode = GG_STORE;
-    }
-    return gg_launch(plans[0], c, (hipStream_t)stream);
-  }
-  return gg_run_group(plans, y, (int64_t)g.N * g.y_bs, 0, force_kernel, (hipStream_t)stream);
-}
-
-int srgan_conv2d_bwd_data(const srgan_conv_desc* desc, const float* gy, const float* w, const float* bias,
-                          float* gx, int accumulate, int force_kernel, void* stream) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_bwd_data");
-  SRGAN_REQUIRE(gy && w && gx, SRGAN_EINVAL, "srgan_conv2d_bwd_data pointers");
-  SRGAN_REQUIRE(g.x_bs == (int64_t)g.C * g.H * g.W, SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data dense gx");
-  const int dtype = desc->compute_dtype;
-  SRGAN_REQUIRE(dtype_ok(dtype), SRGAN_EINVAL, "srgan_conv2d_bwd_data compute_dtype");
-  if (dtype && force_kernel == 0 && use_conv3x3_mixed(g, g.C))
-    return conv3x3_run(gy, g.y_bs, w, 8, 9, g.C * 9, -3, -1, bias, gx, g.x_bs, g.N, g.K, g.C, g.H, g.W, accumulate,
-                       (hipStream_t)stream, nullptr, nullptr, dtype);
-  if (force_kernel == 0 && dtype == 0 && bias == nullptr && !accumulate &&
-      stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw) && (g.W & 1) == 0 && (((uintptr_t)gx) & 7) == 0)
-    return stem7x7_bwd_data_run(gy, g.y_bs, w, gx, g.x_bs, g.N, g.H, g.W, g.K, g.OH, g.OW, (hipStream_t)stream);
-  // k4 / s2 / p1 (the DCGAN generators' transposed convolutions, reference crowd/models.py:132-136, age/models.py:37-41,
-  // as forward passes; the discriminators' strided convolutions as data gradients): output pixel (2q + a, 2r + b) only
-  // meets the 2x2 taps kh = 3 + a - 2i, kw = 3 + b - 2j of the input pixels (q - 1 + i, r - 1 + j), i in {a, a + 1},
-  // j in {b, b + 1} -- four 2x2 sub-windows of the LDS-halo 3x3 kernel with strided stores, instead of four gathered
-  // GEMMs on the generic kernel (50 TF/s).
-  if (force_kernel == 0 && g.R == 4 && g.S == 4 && g.sh == 2 && g.sw == 2 && g.ph == 1 &&
-      g.pw == 1 && g.H == 2 * g.OH && g.W == 2 * g.OW && g.OW >= 8 && (g.C >= 8 || dtype) && !accumulate) {   // (mixed: also the 3-channel image gradient)
-    // small problems split the input channels over the grid and add with atomics: the output is zeroed once for all classes
-    // (only when the split adds with atomics: with a workspace the slices meet in a fixed order and the sums are stored)
-    const bool split = conv3x3_splits(g.N, g.K, g.C, g.OH, g.OW, dtype) > 1 && !srgan_split_is_ordered(stream);
-    if (split) if (const int status = zero_floats(gx, (int64_t)g.N * g.x_bs, (hipStream_t)stream)) return status;
-    for (int a = 0; a < 2; ++a)
-      for (int b = 0; b < 2; ++b) {
-        Conv3Placement placement;
-        placement.taps = (0x01B << (3 * a)) << b;
-        placement.out_plane = g.H * g.W; placement.out_sy = 2 * g.W; placement.out_sx = 2; placement.out_off = a * g.W + b;
-        const int status = conv3x3_run(gy, g.y_bs, w, (3 + a) * 4 + (3 + b), 16, g.C * 16, -8, -2, bias, gx, g.x_bs, g.N, g.K,
-                                       g.C, g.OH, g.OW, split ? 2 : 0, (hipStream_t)stream, nullptr, nullptr, dtype, &placement);
-        if (status != SRGAN_OK) return status;
-      }
-    return SRGAN_OK;
-  }
-  if (dtype) force_kernel = 2;
-  if (use_pointwise(g, g.C, force_kernel))   // the data gradient of a 1x1 convolution is the 1x1 convolution with W^T
-    return pointwise_run(gy, g.y_bs, w, 1, g.C, bias, gx, g.x_bs, g.N, g.K, g.C, g.H * g.W, accumulate,
-                         (hipStream_t)stream);
-  if (use_conv3x3(g, g.C, force_kernel))     // the data gradient is the same convolution with flipped taps
-    return conv3x3_run(gy, g.y_bs, w, 8, 9, g.C * 9, -3, -1, bias, gx, g.x_bs, g.N, g.K, g.C, g.H, g.W, accumulate,
-                       (hipStream_t)stream);
-  std::vector<GatherGemm> plans = plan_conv_bwd_data(g, gy, w, bias, gx);
-  for (GatherGemm& plan : plans) plan.precision = dtype;
-  return gg_run_group(plans, gx, (int64_t)g.N * g.x_bs, accumulate, force_kernel, (hipStream_t)stream);
-}
-
-int srgan_conv2d_bwd_weight(const srgan_conv_desc* desc, const float* x, const float* gy, float* gw,
-                            int accumulate, int force_kernel, void* stream) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_bwd_weight");
-  SRGAN_REQUIRE(x && gy && gw, SRGAN_EINVAL, "srgan_conv2d_bwd_weight pointers");
-  const int dtype = desc->compute_dtype;
-  SRGAN_REQUIRE(dtype_ok(dtype), SRGAN_EINVAL, "srgan_conv2d_bwd_weight compute_dtype");
-  // (mixed precision also takes 8-wide planes on the 16-wide tile: half of the columns are dead, but the alternative is
-  // the gather-bound generic kernel)
-  if (dtype && force_kernel == 0 && wgrad3x3_geometry(g, 8, true) &&
-      (((uintptr_t)x | (uintptr_t)gy) & 15) == 0)
-    return conv3x3_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H, g.W, accumulate, (hipStream_t)stream, nullptr,
-                             dtype);
-  if (dtype) force_kernel = 2;
-  if (use_pointwise_wgrad(g, x, gy, force_kernel))
-    return pointwise_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H * g.W, accumulate, (hipStream_t)stream);
-  if (force_kernel == 0 && dtype == 0 && stem7x7_geometry(g.C, g.K, g.R, g.S, g.sh, g.sw, g.ph, g.pw))
-    return stem7x7_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.H, g.W, g.K, g.OH, g.OW, accumulate, (hipStream_t)stream);
-  if (use_wgrad3x3(g, x, gy, force_kernel))
-    return conv3x3_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H, g.W, accumulate, (hipStream_t)stream);
-  std::vector<GatherGemm> plans{plan_conv_bwd_weight(g, x, gy, gw)};
-  plans[0].precision = dtype;
-  return gg_run_group(plans, gw, (int64_t)g.K * g.C * g.R * g.S, accumulate, force_kernel, (hipStream_t)stream);
-}
-
-// ---- convolutions whose input is relu(batch_norm_eval(x)) evaluated on the fly (DenseNet norm -> relu -> conv)
-static bool bn_ok(const srgan_bn_relu* bn) { return bn && bn->mean && bn->inv_std && bn->gamma && bn->beta; }
-
-int srgan_conv2d_bnrelu_supported(const srgan_conv_desc* desc, int pass) {
-  ConvGeom g;
-  if (desc && desc->compute_dtype != 0) return 0;       // the fused forms are fp32 kernels
-  if (!to_geom(desc, g) || geom_largest_extent(g) >= ((int64_t)1 << 31)) return 0;
-  if (pass == 0) {
-    if (pointwise(g)) return use_pointwise(g, g.K, 0) ? 1 : 0;
-    return (use_conv3x3(g, g.K, 0) && g.C <= 512) ? 1 : 0;
-  }
-  if (pass == 1) {
-    // the epilogue's per-workgroup parameter sums must fit the caller's workspace (<= 1/32 of the gradient tensor's bytes)
-    if ((size_t)g.N * g.H * g.W * g.C / 8 > WORKSPACE_BYTES) return 0;
-    if (pointwise(g)) return use_pointwise(g, g.C, 0) ? 1 : 0;
-    return (use_conv3x3(g, g.C, 0) && conv3x3_epilogue_supported(g.N, g.K, g.C, g.H, g.W)) ? 1 : 0;
-  }
-  if (pass == 2) {
-    if (pointwise(g)) return pointwise_wgrad_geometry(g) ? 1 : 0;
-    return wgrad3x3_geometry(g) ? 1 : 0;
-  }
-  return 0;
-}
-
-// y_state: 0 = y holds anything (stored over), 2 = y is already zero where the convolution writes (a kernel that splits
-// K over the grid then skips its own zero-fill launch; see srgan_conv2d_fwd_bnrelu_splits).
-static int fwd_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w, const float* bias,
-                      float* y, int y_state, int* plan_only_split, void* stream, const float* image = nullptr) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_fwd_bnrelu");
-  SRGAN_REQUIRE(plan_only_split || (x && w && y && bn_ok(bn)), SRGAN_EINVAL, "srgan_conv2d_fwd_bnrelu pointers");
-  SRGAN_REQUIRE(srgan_conv2d_bnrelu_supported(desc, 0), SRGAN_EUNSUPPORTED, "srgan_conv2d_fwd_bnrelu geometry support");
-  const float* const coefficients[4] = {bn ? bn->mean : nullptr, bn ? bn->inv_std : nullptr, bn ? bn->gamma : nullptr,
-                                        bn ? bn->beta : nullptr};
-  SRGAN_REQUIRE(image == nullptr || !pointwise(g), SRGAN_EUNSUPPORTED, "srgan_conv2d_fwd_bnrelu_image: 3x3 convolutions");
-  if (pointwise(g) && (plan_only_split || ((uintptr_t)w & 15) == 0) &&
-      pointwise_ksplit_wanted(g.N, g.C, g.K, g.H * g.W, true)) {
-    if (plan_only_split) { *plan_only_split = 1; return SRGAN_OK; }
-    return pointwise_ksplit_run(x, g.x_bs, w, bias, y, g.y_bs, g.N, g.C, g.K, g.H * g.W, 0, (hipStream_t)stream,
-                                coefficients);
-  }
-  if (pointwise(g))
-    return pointwise_run(x, g.x_bs, w, g.C, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H * g.W, y_state, (hipStream_t)stream,
-                         coefficients, nullptr, plan_only_split);
-  if (plan_only_split) { *plan_only_split = conv3x3_splits(g.N, g.C, g.K, g.H, g.W); return SRGAN_OK; }
-  return conv3x3_run(x, g.x_bs, w, 0, g.C * 9, 9, 3, 1, bias, y, g.y_bs, g.N, g.C, g.K, g.H, g.W, y_state,
-                     (hipStream_t)stream, coefficients, nullptr, 0, nullptr, image);
-}
-
-int srgan_conv2d_fwd_bnrelu_image(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
-                                  const float* image, const float* bias, float* y, void* stream) {
-  SRGAN_REQUIRE(image != nullptr, SRGAN_EINVAL, "srgan_conv2d_fwd_bnrelu_image: the weight image");
-  return fwd_bnrelu(desc, x, bn, w, bias, y, 0, nullptr, stream, image);
-}
-
-int srgan_conv2d_fwd_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
-                            const float* bias, float* y, void* stream) {
-  return fwd_bnrelu(desc, x, bn, w, bias, y, 0, nullptr, stream);
-}
-
-int srgan_conv2d_fwd_bnrelu_into_zeros(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* w,
-                                       const float* bias, float* y, void* stream) {
-  return fwd_bnrelu(desc, x, bn, w, bias, y, 2, nullptr, stream);
-}
-
-int srgan_conv2d_fwd_bnrelu_splits(const srgan_conv_desc* desc) {
-  int split = 0;
-  return fwd_bnrelu(desc, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &split, nullptr) == SRGAN_OK ? split : -1;
-}
-
-static int bwd_data_bnrelu(const srgan_conv_desc* desc, const float* gy, const float* w, const srgan_bn_relu* bn, const float* x,
-                          float* gx, float* g_gamma, float* g_beta, float* partials, int accumulate, void* stream,
-                          const float* image = nullptr) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_bwd_data_bnrelu");
-  SRGAN_REQUIRE(gy && w && x && gx && bn_ok(bn), SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu pointers");
-  SRGAN_REQUIRE((g_gamma == nullptr) == (g_beta == nullptr), SRGAN_EINVAL,
-                "srgan_conv2d_bwd_data_bnrelu parameter gradients (both or neither)");
-  SRGAN_REQUIRE(srgan_conv2d_bnrelu_supported(desc, 1), SRGAN_EUNSUPPORTED,
-                "srgan_conv2d_bwd_data_bnrelu geometry support");
-  BnBackwardEpilogue epilogue;
-  epilogue.x = x; epilogue.x_bs = g.x_bs;
-  epilogue.bn[0] = bn->mean; epilogue.bn[1] = bn->inv_std; epilogue.bn[2] = bn->gamma; epilogue.bn[3] = bn->beta;
-  epilogue.g_gamma = g_gamma; epilogue.g_beta = g_beta; epilogue.partial_out = partials;
-  SRGAN_REQUIRE(image == nullptr || !pointwise(g), SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu_image: 3x3 convolutions");
-  if (pointwise(g))
-    return pointwise_run(gy, g.y_bs, w, 1, g.C, nullptr, gx, g.x_bs, g.N, g.K, g.C, g.H * g.W, accumulate,
-                         (hipStream_t)stream, nullptr, &epilogue);
-  SRGAN_REQUIRE(!accumulate, SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu 3x3: gx is stored, not accumulated");
-  return conv3x3_run(gy, g.y_bs, w, 8, 9, g.C * 9, -3, -1, nullptr, gx, g.x_bs, g.N, g.K, g.C, g.H, g.W, 0,
-                     (hipStream_t)stream, nullptr, &epilogue, 0, nullptr, image);
-}
-
-int srgan_conv2d_bwd_data_bnrelu_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
-                                       const srgan_bn_relu* bn, const float* x, float* gx, float* g_gamma, float* g_beta,
-                                       int accumulate, void* stream) {
-  SRGAN_REQUIRE(image != nullptr, SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu_image: the weight image");
-  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, g_gamma, g_beta, nullptr, accumulate, stream, image);
-}
-
-int srgan_conv2d_bwd_data_bnrelu_partials_image(const srgan_conv_desc* desc, const float* gy, const float* w, const float* image,
-                                                const srgan_bn_relu* bn, const float* x, float* gx, float* partials,
-                                                int accumulate, void* stream) {
-  SRGAN_REQUIRE(partials != nullptr && image != nullptr, SRGAN_EINVAL,
-                "srgan_conv2d_bwd_data_bnrelu_partials_image: the partial-sum region and the weight image");
-  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, nullptr, nullptr, partials, accumulate, stream, image);
-}
-
-int srgan_conv2d_bwd_data_bnrelu(const srgan_conv_desc* desc, const float* gy, const float* w, const srgan_bn_relu* bn,
-                                 const float* x, float* gx, float* g_gamma, float* g_beta, int accumulate, void* stream) {
-  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, g_gamma, g_beta, nullptr, accumulate, stream);
-}
-
-int64_t srgan_conv2d_bwd_data_bnrelu_tiles(const srgan_conv_desc* desc) {
-  ConvGeom g;
-  if (!to_geom(desc, g) || !srgan_conv2d_bnrelu_supported(desc, 1)) return -1;
-  return pointwise(g) ? pointwise_epilogue_tiles(g.N, g.H * g.W) : conv3x3_epilogue_tiles(g.N, g.K, g.C, g.H, g.W);
-}
-
-int srgan_conv2d_bwd_data_bnrelu_partials(const srgan_conv_desc* desc, const float* gy, const float* w, const srgan_bn_relu* bn,
-                                          const float* x, float* gx, float* partials, int accumulate, void* stream) {
-  SRGAN_REQUIRE(partials != nullptr, SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu_partials: the partial-sum region");
-  return bwd_data_bnrelu(desc, gy, w, bn, x, gx, nullptr, nullptr, partials, accumulate, stream);
-}
-
-int srgan_bn_partial_reduce_batched(const srgan_bn_reduce_job* jobs_device, int32_t count, int32_t max_channels, int32_t max_tiles,
-                                    const float* scratch, void* stream) {
-  SRGAN_REQUIRE(jobs_device && scratch && count > 0 && max_channels > 0 && max_tiles > 0, SRGAN_EINVAL,
-                "srgan_bn_partial_reduce_batched arguments");
-  SRGAN_REQUIRE(count <= 65535, SRGAN_ERANGE, "srgan_bn_partial_reduce_batched job count");
-  return bn_partial_reduce_batched_run(jobs_device, count, max_channels, max_tiles, scratch, (hipStream_t)stream);
-}
-
-int srgan_conv2d_bwd_weight_bnrelu(const srgan_conv_desc* desc, const float* x, const srgan_bn_relu* bn, const float* gy,
-                                   float* gw, int accumulate, void* stream) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_conv2d_bwd_weight_bnrelu");
-  SRGAN_REQUIRE(x && gy && gw && bn_ok(bn), SRGAN_EINVAL, "srgan_conv2d_bwd_weight_bnrelu pointers");
-  SRGAN_REQUIRE(srgan_conv2d_bnrelu_supported(desc, 2), SRGAN_EUNSUPPORTED,
-                "srgan_conv2d_bwd_weight_bnrelu geometry support");
-  const float* const coefficients[4] = {bn->mean, bn->inv_std, bn->gamma, bn->beta};
-  if (pointwise(g))
-    return pointwise_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H * g.W, accumulate, (hipStream_t)stream,
-                               coefficients);
-  return conv3x3_wgrad_run(x, g.x_bs, gy, g.y_bs, gw, g.N, g.C, g.K, g.H, g.W, accumulate, (hipStream_t)stream,
-                           coefficients);
-}
-
-// ---- grouped weight gradients: all the norm -> relu -> conv weight gradients of a dense block's backward in two launches
-int srgan_wgrad_group_plan(const srgan_conv_desc* desc, const srgan_bn_relu* bn, int64_t x_offset, int64_t gy_offset, float* gw,
-                           int64_t gw_offset, int32_t group_size, int64_t group_weights, int64_t partial_offset, void* job, int32_t* grid_x,
-                           int32_t* grid_y, int32_t* ragged, int64_t* partial_floats) {
-  ConvGeom g;
-  SRGAN_GEOM(desc, g, "srgan_wgrad_group_plan");
-  SRGAN_REQUIRE(job && grid_x && grid_y && ragged && partial_floats && (bn == nullptr || bn_ok(bn)) && x_offset >= 0 &&
-                gy_offset >= 0 && gw_offset >= 0 && partial_offset >= 0 && group_size >= 1 && group_weights >= 0, SRGAN_EINVAL,
-                "srgan_wgrad_group_plan arguments");
-  SRGAN_REQUIRE(srgan_conv2d_bnrelu_supported(desc, 2), SRGAN_EUNSUPPORTED, "srgan_wgrad_group_plan geometry support");
-  const float* const coefficients[4] = {bn ? bn->mean : nullptr, bn ? bn->inv_std : nullptr, bn ? bn->gamma : nullptr,
-                                        bn ? bn->beta : nullptr};
-  const float* const* fused = bn ? coefficients : nullptr;
-  if (pointwise(g))
-    return pointwise_wgrad_group_plan(x_offset, g.x_bs, gy_offset, g.y_bs, gw, gw_offset, g.N, g.C, g.K, g.H * g.W, fused,
-                                      group_size, group_weights, partial_offset, job, grid_x, grid_y, ragged, partial_floats);
-  return conv3x3_wgrad_group_plan(x_offset, g.x_bs, gy_offset, g.y_bs, gw, gw_offset, g.N, g.C, g.K, g.H, g.W, fused, group_size,
-                                  partial_offset, job, grid_x, grid_y, ragged, partial_floats);
-}
-
-int srgan_wgrad_group_run(const void* jobs, int32_t count, int32_t kernel_size, int32_t grid_x, int32_t grid_y, int32_t ragged,
-                          int32_t fused_bn, const float* x_base, const float* gy_base, float* gw_base, int64_t sum_co_ci_taps,
-                          int64_t pixels, int64_t operand_elements, int64_t partial_floats, void* stream) {
-  SRGAN_REQUIRE(jobs && x_base && gy_base && count >= 1 && grid_x >= 1 && grid_y >= 1 && (kernel_size == 1 || kernel_size == 3) &&
-                partial_floats >= 0, SRGAN_EINVAL, "srgan_wgrad_group_run arguments");
-  if (kernel_size == 1)
-    return pointwise_wgrad_group_run(jobs, count, grid_x, grid_y, ragged, fused_bn, x_base, gy_base, gw_base, sum_co_ci_taps,
-                                     pixels, operand_elements, partial_floats, (hipStream_t)stream);
-  return conv3x3_wgrad_group_run(jobs, count, grid_x, grid_y, ragged, x_base, gy_base, gw_base, sum_co_ci_taps, pixels,
-                                 operand_elements, partial_floats, (hipStream_t)stream);
-}
-
-int srgan_profile_begin(void) {
-  std::lock_guard<std::mutex> lock(g_profile.mutex);
-  g_profile.slots = 0;
-  g_profile.records.clear();
-  g_profile.flops = g_profile.mfma_flops = g_profile.bytes = 0.0;
-  g_profile.launches = 0;
-  g_profile.enabled.store(true, std::memory_order_release);
-  return SRGAN_OK;
-}
-
-int srgan_profile_end(double* kernel_ms, double* flops, double* mfma_flops, int64_t* launches) {
-  g_profile.enabled.store(false, std::memory_order_release);
-  std::lock_guard<std::mutex> lock(g_profile.mutex);
-  double total = 0.0;
-  for (size_t i = 0; i < g_profile.slots; ++i) {
-    if (g_profile.records[i].M < 0) continue;
-    SRGAN_HIP(hipEventSynchronize(g_profile.events[2 * i + 1]));
-    float ms = 0.f;
-    SRGAN_HIP(hipEventElapsedTime(&ms, g_profile.events[2 * i], g_profile.events[2 * i + 1]));
-    total += ms;
-  }
-  if (kernel_ms) *kernel_ms = total;
-  if (flops) *flops = g_profile.flops;
-  if (mfma_flops) *mfma_flops = g_profile.mfma_flops;
-  if (launches) *launches = g_profile.launches;
-  return SRGAN_OK;
-}
-
-int srgan_profile_bytes(double* algorithmic_bytes_total) {
-  std::lock_guard<std::mutex> lock(g_profile.mutex);
-  if (algorithmic_bytes_total) *algorithmic_bytes_total = g_profile.bytes;
-  return SRGAN_OK;
-}
-
-// The part of the profiled region that ran with bf16 / fp16 MFMA operands: its logical FLOPs and its summed kernel time.
-int srgan_profile_mixed(double* flops, double* kernel_ms) {
-  std::lock_guard<std::mutex> lock(g_profile.mutex);
-  double f = 0.0, total = 0.0;
-  for (size_t i = 0; i < g_profile.slots; ++i) {
-    const ProfileRecord& r = g_profile.records[i];
-    if (r.M < 0 || r.precision == 0) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_profile.events[2 * i], g_profile.events[2 * i + 1]) != hipSuccess) continue;
-    total += ms;
-    f += 2.0 * (double)r.M * (double)r.N * (double)r.K;
-  }
-  if (flops) *flops = f;
-  if (kernel_ms) *kernel_ms = total;
-  return SRGAN_OK;
-}
-
-// Per-shape breakdown of the last profiled region as text lines "M N K kind bm bn split akf bkf count ms bytes"
-// (kind: 0 direct, 1 gg_mfma, 2 conv3x3_lds, 3 pointwise, 13 pointwise_ring, 4 conv3x3_wgrad, 5 gg_rows, 6 pointwise_wgrad,
-// 8 pointwise_ksplit, 9 gg_dot, 10 stem7x7_fwd, 11 stem7x7_wgrad; bytes = algorithmic HBM bytes of all `count` launches; call after srgan_profile_end).
-// Returns the number of bytes needed.
-int64_t srgan_profile_report(char* buffer, int64_t capacity) {
-  struct Key { int32_t v[9]; bool operator<(const Key& o) const { return memcmp(v, o.v, sizeof(v)) < 0; } };
-  struct Acc { int64_t count = 0; double ms = 0.0, bytes = 0.0; };
-  std::map<Key, Acc> table;
-  std::lock_guard<std::mutex> lock(g_profile.mutex);
-  for (size_t i = 0; i < g_profile.slots; ++i) {
-    const ProfileRecord& r = g_profile.records[i];
-    if (r.M < 0) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, g_profile.events[2 * i], g_profile.events[2 * i + 1]) != hipSuccess) continue;
-    Key k{{r.M, r.N, r.K, r.kind, r.bm, r.bn, r.split, r.akf, r.bkf}};
-    Acc& a = table[k];
-    a.count += 1;
-    a.ms += ms;
-    a.bytes += r.bytes;
-  }
-  std::string out;
-  char line[200];
-  for (const auto& kv : table) {
-    const int32_t* v = kv.first.v;
-    snprintf(line, sizeof(line), "%d %d %d %d %d %d %d %d %d %lld %.4f %.0f\n", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7],
-             v[8], (long long)kv.second.count, kv.second.ms, kv.second.bytes);
-    out += line;
-  }
-  if (buffer && capacity > 0) {
-    const size_t n = out.size() < (size_t)capacity - 1 ? out.size() : (size_t)capacity - 1;
-    memcpy(buffer, out.data(), n);
-    buffer[n] = 0;
-  }
-  return (int64_t)out.size() + 1;
-}
-
-// ---- caller-owned workspace, capabilities -----------------------------------------------------------------------
-int64_t srgan_workspace_bytes(void) { return (int64_t)WORKSPACE_BYTES; }
-
-int srgan_set_workspace(void* workspace, int64_t bytes, void* stream) {
-  SRGAN_REQUIRE(workspace == nullptr || bytes >= (int64_t)WORKSPACE_BYTES, SRGAN_EINVAL,
-                "srgan_set_workspace: at least srgan_workspace_bytes() bytes");
-  SRGAN_REQUIRE(((uintptr_t)workspace & 15) == 0, SRGAN_EINVAL, "srgan_set_workspace: 16-byte alignment");
-  return workspace_register((float*)workspace, (size_t)(bytes > 0 ? bytes : 0), (hipStream_t)stream);
-}
-
-// 1 when a K split on this stream is finished in a fixed order through the registered workspace (split_finish.h): such a
-// launch stores whole sums -- no zero-filled output needed, the same bits every run; 0: fp32 atomics into a zeroed output.
-int srgan_split_is_ordered(void* stream) {
-  if (split_atomics_forced()) return 0;
-  const int set = workspace_index((hipStream_t)stream);
-  return set >= 0 && set < SPLIT_TICKET_SETS ? 1 : 0;
-}
-
-int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
-  SRGAN_REQUIRE(out != nullptr && out_bytes >= (int32_t)sizeof(srgan_capabilities_t), SRGAN_EINVAL,
-                "srgan_capabilities: output struct");
-  memset(out, 0, sizeof(*out));
-  out->abi_version = srgan_version();
-  out->struct_bytes = (int32_t)sizeof(*out);
-  snprintf(out->arch, sizeof(out->arch), "gfx950");
-  out->dtypes = SRGAN_DTYPE_F32 | SRGAN_DTYPE_BF16 | SRGAN_DTYPE_F16;
-  out->features = SRGAN_FEATURE_FUSED_BNRELU | SRGAN_FEATURE_SPLITK_WORKSPACE | SRGAN_FEATURE_LIVE_PROFILE |
-                  SRGAN_FEATURE_BLOCKED16 | SRGAN_FEATURE_BATCHED_SHADOWS | SRGAN_FEATURE_CROWD_FULL_IMAGE |
-                  SRGAN_FEATURE_IMAGE_BATCHES | SRGAN_FEATURE_BATCH_NORM_TRAIN | SRGAN_FEATURE_BLOCKED_BATCH_NORM |
-                  SRGAN_FEATURE_BLOCKED_FROZEN_NORM | SRGAN_FEATURE_DEVICE_DRAWS | SRGAN_FEATURE_IMAGE_SUMMARIES |
-                  SRGAN_FEATURE_DISTRIBUTION_SUMMARIES | SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE;
-  out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
-  out->max_tensor_elements = ((int64_t)1 << 31) - 1;
-  return SRGAN_OK;
-}
-
 int srgan_gemm_f32(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int64_t sak, const float* B,
                    int64_t sbk, int64_t sbj, float* C, int64_t sci, int64_t scj, const float* bias,
                    int32_t bias_on_columns, int accumulate, int force_kernel, void* stream) {
@@ -1455,7 +809,7 @@ int srgan_gemm(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int
                int64_t sbk, int64_t sbj, float* C, int64_t sci, int64_t scj, const float* bias,
                int32_t bias_on_columns, int accumulate, int force_kernel, int compute_dtype, void* stream) {
   SRGAN_REQUIRE(M > 0 && N > 0 && K >= 0 && A && B && C, SRGAN_EINVAL, "srgan_gemm_f32 arguments");
-  SRGAN_REQUIRE(dtype_ok(compute_dtype), SRGAN_EINVAL, "srgan_gemm compute_dtype");
+  SRGAN_REQUIRE(compute_dtype >= 0 && compute_dtype <= 2, SRGAN_EINVAL, "srgan_gemm compute_dtype");
   if (compute_dtype) force_kernel = 2;
   const int64_t lim = (int64_t)1 << 31;
   SRGAN_REQUIRE(M * sai + K * sak < lim && K * sbk + N * sbj < lim && M * sci + N * scj < lim, SRGAN_ERANGE,
@@ -1470,7 +824,7 @@ int srgan_gemm(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int
   }
   p.precision = compute_dtype;
   std::vector<GatherGemm> plans{p};
-  return gg_run_group(plans, C, (int64_t)M * N, accumulate, force_kernel, (hipStream_t)stream);
+  return gg_run_group(plans, C, (int64_t)M * N, (int64_t)M * N, 1, accumulate, force_kernel, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,30 +1,103 @@
-// launchers.h -- the host functions one translation unit defines and another calls, declared once.  Default arguments
-// live here only.  (The workspace registry -- partial_workspace, workspace_index -- is in split_finish.h, the zero-fills
-// in common.h and h_zero_slots in blocked16.h.)
+// launchers.h -- the host functions one translation unit defines and another calls, declared once, with the names they
+// share: the launch kinds of the live profile (LaunchKind) and the operands of a convolution route (Conv3Weights, the
+// batch-norm helpers).  Default arguments live here only.  (The workspace registry -- partial_workspace, workspace_index,
+// workspace_register, workspace_capacity -- is in split_finish.h, the error string and the zero-fills in common.h and
+// h_zero_slots in blocked16.h.)
 #pragma once
+#include <vector>
 #include "common.h"
+#include "gather_gemm.h"
 
 namespace srgan {
 
-// gather_gemm_kernels.hip: the bench's live event bracket around a contraction launch (-1 from begin(): profiling off).
-// The _bytes form states the launch's algorithmic bytes itself.
+// The `kind` column of srgan_profile_report, one entry per kernel family that brackets its launches.  The numbers are part
+// of the report's format (bench.py and tests/contraction_cases.py print them by number): they never change.
+enum LaunchKind {
+  KIND_GG_DIRECT = 0,           // gather_gemm_kernels.hip: one thread per output (M <= 2)
+  KIND_GG_MFMA = 1,             //   the generic MFMA tile
+  KIND_CONV3X3_LDS = 2,         // conv3x3.hip (also the k4 / s2 classes)
+  KIND_POINTWISE = 3,           // pointwise.hip
+  KIND_CONV3X3_WGRAD = 4,       // conv3x3_wgrad.hip, single and grouped
+  KIND_GG_ROWS = 5,             // gather_gemm_kernels.hip: a few output rows over a wide N
+  KIND_POINTWISE_WGRAD = 6,     // pointwise_wgrad.hip, single and grouped
+  // 7 is unused (a retired kernel's number; kept free so that old reports stay readable)
+  KIND_POINTWISE_KSPLIT = 8,    // pointwise_ksplit.hip
+  KIND_GG_DOT = 9,              // gather_gemm_kernels.hip: lanes along K
+  KIND_STEM7X7_FWD = 10,        // stem7x7.hip
+  KIND_STEM7X7_WGRAD = 11,
+  KIND_STEM7X7_BWD_DATA = 12,
+  KIND_POINTWISE_RING = 13,     // pointwise_ring.hip
+  KIND_HCONV3X3 = 14,           // blocked16.hip: forward and data gradient
+  KIND_HWGRAD3X3 = 15,
+  KIND_HGEMM = 16,              // blocked16_gemm.hip
+  KIND_HLINEAR_WGRAD = 17,
+  KIND_HCONV4X4S2 = 18,         // blocked16_k4s2.hip
+  KIND_HWGRAD4X4S2 = 19,
+  KIND_BN_STATS = 20,           // batch_norm_train.hip and blocked16_batch_norm.hip: 0 FLOP, algorithmic bytes only
+  KIND_BN_FWD = 21,
+  KIND_BN_BWD_REDUCE = 22,
+  KIND_BN_BWD_APPLY = 23,
+  KIND_H_FROZEN_NORM_BWD = 24,  // blocked16_batch_norm.hip
+};
+
+// Kernels that do their FLOPs on the vector unit: everything else counts towards the profile's MFMA FLOPs.
+inline bool launch_kind_is_valu(LaunchKind kind) {
+  return kind == KIND_GG_DIRECT || kind == KIND_GG_ROWS || kind == KIND_GG_DOT || kind == KIND_STEM7X7_BWD_DATA;
+}
+
+// profile.hip: the bench's live event bracket around a contraction launch (-1 from begin(): profiling off).
+// The _bytes form states the launch's algorithmic bytes itself (and counts its FLOPs as MFMA FLOPs whatever the kind).
 int profile_bracket_begin(hipStream_t stream);
-int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn, int split,
+int profile_bracket_end(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, LaunchKind kind, int bm, int bn, int split,
                         int akf = 0, int bkf = 0, int64_t b_unique = 0, int precision = 0);
-int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, int kind, int bm, int bn, int split,
+int profile_bracket_end_bytes(int slot, hipStream_t stream, int64_t M, int64_t N, int64_t K, LaunchKind kind, int bm, int bn, int split,
                               double bytes, int precision);
+
+// gather_gemm_kernels.hip: runs a group of plans that together define one output tensor of `c_rows` rows of `c_width` floats,
+// `c_pitch` floats apart (dense: pitch == width).  `accumulate` adds into the existing contents; otherwise the output is
+// (over)written, and zeroed first where a plan adds its K slices with atomics.  force: 0 auto, 1 direct, 2 mfma.
+int gg_run_group(std::vector<GatherGemm>& plans, float* c_base, int64_t c_pitch, int64_t c_width, int64_t c_rows, int accumulate,
+                 int force, hipStream_t stream);
+
+// The four coefficient vectors of a fused norm -> relu prologue, in the order the kernels take them; and the batch-norm
+// backward epilogue of a data gradient (common.h) from the same struct.
+struct BnVectors { const float* v[4]; };
+inline BnVectors bn_vectors(const srgan_bn_relu* bn) {
+  return bn ? BnVectors{{bn->mean, bn->inv_std, bn->gamma, bn->beta}} : BnVectors{{nullptr, nullptr, nullptr, nullptr}};
+}
+inline BnBackwardEpilogue bn_backward_epilogue(const srgan_bn_relu* bn, const float* x, int64_t x_bs, float* g_gamma, float* g_beta,
+                                               float* partial_out) {
+  return BnBackwardEpilogue{x, x_bs, {bn->mean, bn->inv_std, bn->gamma, bn->beta}, g_gamma, g_beta, partial_out};
+}
 
 // conv3x3.hip: 3x3 / stride 1 / pad 1, the LDS-halo kernel.
 // A stride-2 class of a k4 / s2 / p1 transposed convolution as a 2x2 sub-window of the 3x3 kernel (see conv3x3_run).
 struct Conv3Placement { int32_t taps, out_plane, out_sy, out_sx, out_off; };
+constexpr int CONV3_MIN_WIDTH = 7;        // narrowest plane of the kernel (the 14- and 7-wide planes at 224)
+// How the kernel walks its weights: element (o, i, kh, kw) of the 3x3 window at w[base + o * so + i * si + kh * skh + kw * skw];
+// `image`: the operand's weight image (blocked16.h), fused fp32 forms only.
+struct Conv3Weights { const float* w; int32_t base, so, si, skh, skw; const float* image; };
+// The forward taps of a [K, C, 3, 3] weight (o = k, i = c).
+inline Conv3Weights conv3_forward_taps(const float* w, int32_t C, const float* image = nullptr) {
+  return Conv3Weights{w, 0, C * 9, 9, 3, 1, image};
+}
+// The flipped taps of the same weight for the data gradient (o = c, i = k).
+inline Conv3Weights conv3_flipped_taps(const float* w, int32_t C, const float* image = nullptr) {
+  return Conv3Weights{w, 8, 9, C * 9, -3, -1, image};
+}
+// The stride class (a, b) of the data gradient of a [K, C, 4, 4] k4 / s2 / p1 weight: output pixel (2q + a, 2r + b) of the
+// H x W gradient meets the taps kh = 3 + a - 2i, kw = 3 + b - 2j only -- a 2x2 sub-window of the 3x3 kernel, stored with
+// stride 2.  Fills the class's placement.
+inline Conv3Weights conv3_k4s2_class(const float* w, int32_t C, int a, int b, int32_t H, int32_t W, Conv3Placement* placement) {
+  *placement = Conv3Placement{(0x01B << (3 * a)) << b, H * W, 2 * W, 2, a * W + b};
+  return Conv3Weights{w, (3 + a) * 4 + (3 + b), 16, C * 16, -8, -2, nullptr};
+}
 int conv3x3_splits(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W, int precision = 0);
 bool conv3x3_epilogue_supported(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
 int64_t conv3x3_epilogue_tiles(int32_t N, int32_t CI, int32_t CO, int32_t H, int32_t W);
-int conv3x3_run(const float* in, int64_t in_bs, const float* w, int32_t w_base, int32_t w_so, int32_t w_si, int32_t w_skh,
-                int32_t w_skw, const float* bias, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t CO, int32_t H,
-                int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
-                const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const Conv3Placement* placement = nullptr,
-                const float* w_image = nullptr);      // w_image: the operand's weight image (blocked16.h), fused fp32 forms only
+int conv3x3_run(const float* in, int64_t in_bs, const Conv3Weights& weights, const float* bias, float* out, int64_t out_bs, int32_t N,
+                int32_t CI, int32_t CO, int32_t H, int32_t W, int accumulate, hipStream_t stream, const float* const* bn = nullptr,
+                const BnBackwardEpilogue* epilogue = nullptr, int precision = 0, const Conv3Placement* placement = nullptr);
 
 // A grouped weight-gradient launch (conv3x3_wgrad.hip, pointwise_wgrad.hip) asks for this many times the resident
 // workgroups, shared out over its problems.

@@ -585,7 +585,7 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
     int32_t rows_done = 0;
     if (const int status = pointwise_ring_run(in, in_bs, w, w_so, w_si, out, out_bs, N, CI, CO, HW, accumulate, stream, bn,
                                               epilogue, epi_partial, (int32_t)col_blocks128, ring_pixels, &rows_done)) {
-      profile_bracket_end(profile_slot, stream, 0, 0, 0, 13, 128, ring_pixels, 1);      // close the bracket this call opened
+      profile_bracket_end(profile_slot, stream, 0, 0, 0, KIND_POINTWISE_RING, 128, ring_pixels, 1);      // close the bracket this call opened
       return status;
     }
     // (the ring kernel covers every row: its last 128-row tile may be partial)
@@ -596,7 +596,7 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
     const int64_t pixels = (int64_t)N * HW;
     const int64_t b_elements = (int64_t)CI * pixels + (epilogue ? (int64_t)CO * pixels * (accumulate == 1 ? 2 : 1) : 0) +
                                ((!epilogue && accumulate == 1) ? (int64_t)CO * pixels : 0);
-    profile_bracket_end(profile_slot, stream, CO, pixels, CI, 13, 128, ring_pixels, 1, 0, 0, b_elements);      // kind 13: pointwise_ring_kernel
+    profile_bracket_end(profile_slot, stream, CO, pixels, CI, KIND_POINTWISE_RING, 128, ring_pixels, 1, 0, 0, b_elements);
     return status;
   }
 
@@ -674,7 +674,7 @@ int pointwise_run(const float* in, int64_t in_bs, const float* w, int32_t w_so, 
   const int64_t pixels = (int64_t)N * HW;
   const int64_t b_elements = (int64_t)CI * pixels + (epilogue ? (int64_t)CO * pixels * (p.mode == 1 ? 2 : 1) : 0) +
                              ((!epilogue && p.mode == 1) ? (int64_t)CO * pixels : 0);
-  profile_bracket_end(profile_slot, stream, CO, pixels, CI, 3, mi * 32, 128, split, 0, 0, b_elements);
+  profile_bracket_end(profile_slot, stream, CO, pixels, CI, KIND_POINTWISE, mi * 32, 128, split, 0, 0, b_elements);
   return status;
 }
 

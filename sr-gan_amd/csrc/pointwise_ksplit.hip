@@ -172,7 +172,7 @@ int pointwise_ksplit_run(const float* in, int64_t in_bs, const float* w, const f
   if (bn) hipLaunchKernelGGL(pointwise_ksplit_kernel<true>, grid, dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(pointwise_ksplit_kernel<false>, grid, dim3(256), 0, stream, p);
   const int status = launch_status();
-  profile_bracket_end(profile_slot, stream, M, (int64_t)N * HW, K, 8, PKS_MI * 32, 32, 4);
+  profile_bracket_end(profile_slot, stream, M, (int64_t)N * HW, K, KIND_POINTWISE_KSPLIT, PKS_MI * 32, 32, 4);
   return status;
 }
 

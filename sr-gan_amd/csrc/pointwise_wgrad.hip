@@ -614,7 +614,7 @@ int pointwise_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t g
   else if (p.partial)
     hipLaunchKernelGGL(pointwise_wgrad_finish_kernel<PWG_MI * 32>, dim3(PWG_FINISH_SLABS, (unsigned)tiles), dim3(256), 0, stream, p);
   const int status = launch_status();
-  profile_bracket_end(profile_slot, stream, CO, CI, (int64_t)N * HW, 6, staged ? PWL_TILE : PWG_MI * 32, staged ? PWL_TILE : PWG_NI * 32, split);
+  profile_bracket_end(profile_slot, stream, CO, CI, (int64_t)N * HW, KIND_POINTWISE_WGRAD, staged ? PWL_TILE : PWG_MI * 32, staged ? PWL_TILE : PWG_NI * 32, split);
   return status;
 }
 
@@ -694,7 +694,7 @@ int pointwise_wgrad_group_run(const void* jobs, int32_t count, int32_t grid_x, i
                        stream, table, gw_base, partial_base);
   const int status = launch_status();
   // logical shape of the group: M x (sum of the input widths) x pixels, i.e. flops_mn = sum CO * CI
-  profile_bracket_end(profile_slot, stream, 1, flops_mn, pixels, 6, staged ? PWL_TILE : PWG_MI * 32, staged ? PWL_TILE : PWG_NI * 32, grid_y, 0, 0,
+  profile_bracket_end(profile_slot, stream, 1, flops_mn, pixels, KIND_POINTWISE_WGRAD, staged ? PWL_TILE : PWG_MI * 32, staged ? PWL_TILE : PWG_NI * 32, grid_y, 0, 0,
                       elements > pixels ? elements - pixels : 0);
   return status;
 }

@@ -171,8 +171,12 @@ constexpr int ROW_FINISH_ROWS = 4096;       // output rows (channels / examples)
 
 // Host side: the workspace region and the ticket row of a split launch, or nullptr when the ordered finish cannot be used
 // (no workspace registered for the stream, too many tiles / bytes, or SRGAN_ATOMIC_SPLIT=1: the round-4 atomics).
+// (runtime.hip: the registry of caller-owned workspaces, one per device and stream; workspace_capacity() = the bytes
+// srgan_set_workspace asks for)
 float* partial_workspace(size_t bytes, hipStream_t stream);
 int workspace_index(hipStream_t stream);
+int workspace_register(float* ptr, size_t bytes, hipStream_t stream);
+size_t workspace_capacity();
 
 // The device address of a ticket array (per device: the symbol has one copy on each).  The cache is keyed by the SYMBOL'S
 // ADDRESS, not by its type: several translation units declare arrays of one type (unsigned[64 * 2048]), and a cache per template

@@ -406,7 +406,7 @@ int stem7x7_fwd_run(const float* x, int64_t x_bs, const float* w, float* y, int6
   if (K > 32) hipLaunchKernelGGL(stem7x7_fwd_kernel<2>, dim3(grid), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(stem7x7_fwd_kernel<1>, dim3(grid), dim3(256), 0, stream, p);
   const int status = launch_status();
-  profile_bracket_end(slot, stream, K, (int64_t)N * OH * OW, 147, 10, K > 32 ? 64 : 32, 128, 1, 0, 0, (int64_t)N * 3 * H * W);
+  profile_bracket_end(slot, stream, K, (int64_t)N * OH * OW, 147, KIND_STEM7X7_FWD, K > 32 ? 64 : 32, 128, 1, 0, 0, (int64_t)N * 3 * H * W);
   return status;
 }
 
@@ -428,7 +428,7 @@ int stem7x7_wgrad_run(const float* x, int64_t x_bs, const float* gy, int64_t gy_
   if (partial)
     hipLaunchKernelGGL(stem7x7_wgrad_finish_kernel, dim3((32 * 147 + 255) / 256, co_blocks), dim3(256), 0, stream, partial, gw, K, grid);
   const int status = launch_status();
-  profile_bracket_end(slot, stream, K, 147, (int64_t)N * OH * OW, 11, 32, 160, grid, 0, 0, (int64_t)N * 3 * H * W);
+  profile_bracket_end(slot, stream, K, 147, (int64_t)N * OH * OW, KIND_STEM7X7_WGRAD, 32, 160, grid, 0, 0, (int64_t)N * 3 * H * W);
   return status;
 }
 
@@ -445,7 +445,7 @@ int stem7x7_bwd_data_run(const float* gy, int64_t gy_bs, const float* w, float* 
   hipLaunchKernelGGL(stem7x7_bwd_data_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
   const int status = launch_status();
   // logical work: 3 x (N * H * W) outputs, K * 49 / 4 taps each on average
-  profile_bracket_end(slot, stream, 3, (int64_t)N * H * W, (int64_t)K * 49 / 4, 12, 4, 256, 1, 0, 0, (int64_t)N * K * OH * OW);
+  profile_bracket_end(slot, stream, 3, (int64_t)N * H * W, (int64_t)K * 49 / 4, KIND_STEM7X7_BWD_DATA, 4, 256, 1, 0, 0, (int64_t)N * K * OH * OW);
   return status;
 }
 
