@@ -192,6 +192,23 @@ int srgan_conv2d_bwd_data_bnrelu_partials(const srgan_conv_desc* desc, const flo
                                           const float* x, float* gx, float* partials, int accumulate, void* stream);
 int srgan_bn_partial_reduce_batched(const srgan_bn_reduce_job* jobs_device, int32_t count, int32_t max_channels, int32_t max_tiles,
                                     const float* scratch, void* stream);
+/* Two consecutive layers of a dense block, A (desc_a: C rows) and B (desc_b: C - 32 rows, otherwise the same descriptor),
+ * accumulate their 1x1 data gradients (srgan_conv2d_bwd_data_bnrelu_partials with accumulate = 1, same x and gx) into
+ * almost the same rows.  Where srgan_conv2d_bwd_data_bnrelu_pair_supported answers 1 (both on the LDS-DMA kernel, K = 128,
+ * B's C >= 128, H * W a multiple of 128, N * H * W >= 16384, equal batch strides) the two calls can be replaced by
+ *   srgan_conv2d_bwd_data_bnrelu_strip: A's contribution to its last 32 rows [C - 32, C), which B's 3x3 data gradient
+ *     reads (issued where A's call stood), and
+ *   srgan_conv2d_bwd_data_bnrelu_pair: A's and then B's contribution to the rows [0, C - 32) in ONE pass over x and gx
+ *     (issued where B's call stood),
+ * with BIT-IDENTICAL gx and partial-sum regions (partials_a / partials_b: each layer's own region as above; both NULL =
+ * no parameter sums).  Pointers the kernel cannot take (16-byte alignment): SRGAN_EUNSUPPORTED. */
+int srgan_conv2d_bwd_data_bnrelu_pair_supported(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b);
+int srgan_conv2d_bwd_data_bnrelu_strip(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b, const float* gy, const float* w,
+                                       const srgan_bn_relu* bn, const float* x, float* gx, float* partials, void* stream);
+int srgan_conv2d_bwd_data_bnrelu_pair(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b, const float* gy_a,
+                                      const float* w_a, const srgan_bn_relu* bn_a, float* partials_a, const float* gy_b,
+                                      const float* w_b, const srgan_bn_relu* bn_b, float* partials_b, const float* x, float* gx,
+                                      void* stream);
 /* The 3x3 / stride 1 / padding 1 cases of the three calls above with the operand's WEIGHT IMAGE next to w
  * (SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE): fp32, 16-byte aligned, srgan_conv3x3_image_floats(CI, CO) floats,
  *   image[(ci * 9 + tap) * CO_pad + o], CO_pad = CO rounded up to 64, ci up to CI rounded up to 8, zeros where o >= CO or ci >= CI,

@@ -50,6 +50,11 @@ SIGNATURES = {
     'srgan_conv2d_bwd_data_bnrelu_tiles': ([ctypes.POINTER(ConvDesc)], ctypes.c_int64),
     'srgan_conv2d_bwd_data_bnrelu_partials': ([ctypes.POINTER(ConvDesc), vp, vp, ctypes.POINTER(BnRelu), vp, vp, vp,
                                                ctypes.c_int, vp], ctypes.c_int),
+    'srgan_conv2d_bwd_data_bnrelu_pair_supported': ([ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc)], ctypes.c_int),
+    'srgan_conv2d_bwd_data_bnrelu_strip': ([ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), vp, vp, ctypes.POINTER(BnRelu), vp,
+                                            vp, vp, vp], ctypes.c_int),
+    'srgan_conv2d_bwd_data_bnrelu_pair': ([ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), vp, vp, ctypes.POINTER(BnRelu), vp, vp,
+                                           vp, ctypes.POINTER(BnRelu), vp, vp, vp, vp], ctypes.c_int),
     'srgan_conv3x3_image_floats': ([i32, i32], ctypes.c_int64),
     'srgan_conv2d_fwd_bnrelu_image': ([ctypes.POINTER(ConvDesc), vp, ctypes.POINTER(BnRelu), vp, vp, vp, vp, vp], ctypes.c_int),
     'srgan_conv2d_bwd_data_bnrelu_image': ([ctypes.POINTER(ConvDesc), vp, vp, vp, ctypes.POINTER(BnRelu), vp, vp, vp, vp,

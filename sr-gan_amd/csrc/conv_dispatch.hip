@@ -304,6 +304,49 @@ int srgan_conv2d_bwd_data_bnrelu_partials(const srgan_conv_desc* desc, const flo
   return bwd_data_bnrelu(desc, gy, w, bn, x, gx, nullptr, nullptr, partials, accumulate, stream);
 }
 
+// ---- the 1x1 data gradients of two consecutive dense layers A (C rows) and B (C - 32 rows) with one pass over B's rows
+static bool pair_geometry(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b, ConvGeom& a, ConvGeom& b) {
+  if (!srgan_conv2d_bnrelu_supported(desc_a, 1) || !srgan_conv2d_bnrelu_supported(desc_b, 1)) return false;
+  if (!to_geom(desc_a, a) || !to_geom(desc_b, b) || !pointwise(a) || !pointwise(b)) return false;
+  return a.N == b.N && a.H == b.H && a.W == b.W && a.K == b.K && a.x_bs == b.x_bs && a.y_bs == b.y_bs;
+}
+
+int srgan_conv2d_bwd_data_bnrelu_pair_supported(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b) {
+  ConvGeom a, b;
+  if (!pair_geometry(desc_a, desc_b, a, b)) return 0;
+  return pointwise_ring_pair_eligible(nullptr, nullptr, a.y_bs, nullptr, nullptr, nullptr, a.x_bs, nullptr, a.x_bs, a.N, a.K, a.C,
+                                      b.C, a.H * a.W) ? 1 : 0;
+}
+
+int srgan_conv2d_bwd_data_bnrelu_strip(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b, const float* gy, const float* w,
+                                       const srgan_bn_relu* bn, const float* x, float* gx, float* partials, void* stream) {
+  ConvGeom a, b;
+  SRGAN_REQUIRE(gy && w && x && gx && bn_ok(bn), SRGAN_EINVAL, "srgan_conv2d_bwd_data_bnrelu_strip pointers");
+  SRGAN_REQUIRE(pair_geometry(desc_a, desc_b, a, b) &&
+                pointwise_ring_pair_eligible(gy, gy, a.y_bs, w, w, x, a.x_bs, gx, a.x_bs, a.N, a.K, a.C, b.C, a.H * a.W),
+                SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu_strip: not a pair (srgan_conv2d_bwd_data_bnrelu_pair_supported)");
+  const BnBackwardEpilogue epilogue = bn_backward_epilogue(bn, x, a.x_bs, nullptr, nullptr, partials);
+  return pointwise_ring_strip_run(gy, a.y_bs, w, gx, a.x_bs, a.N, a.K, a.C, b.C, a.H * a.W, epilogue, (hipStream_t)stream);
+}
+
+int srgan_conv2d_bwd_data_bnrelu_pair(const srgan_conv_desc* desc_a, const srgan_conv_desc* desc_b, const float* gy_a,
+                                      const float* w_a, const srgan_bn_relu* bn_a, float* partials_a, const float* gy_b,
+                                      const float* w_b, const srgan_bn_relu* bn_b, float* partials_b, const float* x, float* gx,
+                                      void* stream) {
+  ConvGeom a, b;
+  SRGAN_REQUIRE(gy_a && w_a && gy_b && w_b && x && gx && bn_ok(bn_a) && bn_ok(bn_b), SRGAN_EINVAL,
+                "srgan_conv2d_bwd_data_bnrelu_pair pointers");
+  SRGAN_REQUIRE((partials_a == nullptr) == (partials_b == nullptr), SRGAN_EINVAL,
+                "srgan_conv2d_bwd_data_bnrelu_pair partial-sum regions (both or neither)");
+  SRGAN_REQUIRE(pair_geometry(desc_a, desc_b, a, b) &&
+                pointwise_ring_pair_eligible(gy_a, gy_b, a.y_bs, w_a, w_b, x, a.x_bs, gx, a.x_bs, a.N, a.K, a.C, b.C, a.H * a.W),
+                SRGAN_EUNSUPPORTED, "srgan_conv2d_bwd_data_bnrelu_pair: not a pair (srgan_conv2d_bwd_data_bnrelu_pair_supported)");
+  const BnBackwardEpilogue epilogue_a = bn_backward_epilogue(bn_a, x, a.x_bs, nullptr, nullptr, partials_a);
+  const BnBackwardEpilogue epilogue_b = bn_backward_epilogue(bn_b, x, a.x_bs, nullptr, nullptr, partials_b);
+  return pointwise_ring_pair_run(gy_a, w_a, a.C, epilogue_a, gy_b, w_b, b.C, epilogue_b, a.y_bs, gx, a.x_bs, a.N, a.K, a.H * a.W,
+                                 (hipStream_t)stream);
+}
+
 int srgan_bn_partial_reduce_batched(const srgan_bn_reduce_job* jobs_device, int32_t count, int32_t max_channels, int32_t max_tiles,
                                     const float* scratch, void* stream) {
   SRGAN_REQUIRE(jobs_device && scratch && count > 0 && max_channels > 0 && max_tiles > 0, SRGAN_EINVAL,

@@ -133,6 +133,16 @@ int pointwise_ring_run(const float* in, int64_t in_bs, const float* w, int32_t w
                        int32_t N, int32_t CI, int32_t CO, int32_t HW, int accumulate, hipStream_t stream,
                        const float* const* bn, const BnBackwardEpilogue* epilogue, float* epi_partial, int32_t epi_cols,
                        int tile_pixels, int32_t* rows_done);
+// Two consecutive dense layers' fused data gradients in one pass over their common rows (pointwise_ring.hip): layer A's
+// rows [row0, CO) on their own (the strip), then A and B together on B's rows (the pair).
+bool pointwise_ring_pair_eligible(const float* in_a, const float* in_b, int64_t in_bs, const float* w_a, const float* w_b,
+                                  const float* x, int64_t x_bs, const float* out, int64_t out_bs, int32_t N, int32_t CI,
+                                  int32_t rows_a, int32_t rows_b, int32_t HW);
+int pointwise_ring_strip_run(const float* in, int64_t in_bs, const float* w, float* out, int64_t out_bs, int32_t N, int32_t CI,
+                             int32_t CO, int32_t row0, int32_t HW, const BnBackwardEpilogue& epilogue, hipStream_t stream);
+int pointwise_ring_pair_run(const float* in_a, const float* w_a, int32_t rows_a, const BnBackwardEpilogue& epilogue_a,
+                            const float* in_b, const float* w_b, int32_t rows_b, const BnBackwardEpilogue& epilogue_b,
+                            int64_t in_bs, float* out, int64_t out_bs, int32_t N, int32_t CI, int32_t HW, hipStream_t stream);
 
 // pointwise_ksplit.hip: the pointwise convolution for few pixels and many input channels (K split over the grid).
 bool pointwise_ksplit_wanted(int32_t N, int32_t K, int32_t M, int32_t HW, bool fused_bn);

@@ -266,6 +266,10 @@ def _block_parameters(layers):
 
 
 WEIGHT_IMAGE = True  # the 3x3 convolutions stage their weights from per-step packed images (tests flip this)
+# The 1x1 data gradients of two consecutive layers l + 1, l of a block with ONE pass over the rows they share (x and the
+# gradient buffer through HBM once instead of twice; bit-identical): layer l + 1's last 32 rows -- which layer l's 3x3
+# data gradient reads -- in a strip launch of their own, everything else in the pair launch.  Tests flip this.
+PAIRED_DGRAD = True
 
 
 def _weight_images(layers):
@@ -429,6 +433,16 @@ def dense_block(x, layers):
             alive = []                            # tensors the side stream still reads
         else:
             wstream = stream
+        # layers whose 1x1 data gradient runs as a pair, from the top of the block down: first[a] = b, second[b] = a
+        # (partial sums for both or for neither: the direct g_gamma / g_beta form stays per layer)
+        first, second, pending = {}, {}, None
+        if PAIRED_DGRAD and epilogue1 and (plan is not None or not want_params):
+            bottleneck = layers[0].conv1.out_channels
+            for a in range(len(layers) - 1, 0, -2):
+                desc_a = _desc(n, c0 + a * growth, h, w, bottleneck, 1, 1, 1, 0, buffer_bs, 0)
+                desc_b = _desc(n, c0 + (a - 1) * growth, h, w, bottleneck, 1, 1, 1, 0, buffer_bs, 0)
+                if lib.srgan_conv2d_bwd_data_bnrelu_pair_supported(desc_a, desc_b):
+                    first[a], second[a - 1] = (desc_a, desc_b), a
         for index in range(len(layers) - 1, -1, -1):
             layer = layers[index]
             t1, b1, t2 = saved[index]
@@ -486,7 +500,22 @@ def dense_block(x, layers):
             elif want_params:
                 F._call('srgan_conv2d_bwd_weight', desc1, t1.data_ptr(), g_b1.data_ptr(),
                         layer.conv1.weight.grad.data_ptr(), 1, 0, stream)
-            if epilogue1 and plan is not None:
+            if index in first:
+                # the rows the next layer's 3x3 data gradient reads; the rest with that layer's own gradient, below
+                desc_a, desc_b = first[index]
+                partials = _ptr(scratch, plan['offsets'][index][1]) if plan is not None else None
+                F._call('srgan_conv2d_bwd_data_bnrelu_strip', desc_a, desc_b, g_b1.data_ptr(), layer.conv1.weight.data_ptr(),
+                        bn_struct(layer.norm1), buffer.data_ptr(), gbuf.data_ptr(), partials, stream)
+                pending = (g_b1, layer, partials)
+            elif index in second:
+                desc_a, desc_b = first[second[index]]
+                g_b1_a, layer_a, partials_a = pending
+                F._call('srgan_conv2d_bwd_data_bnrelu_pair', desc_a, desc_b, g_b1_a.data_ptr(), layer_a.conv1.weight.data_ptr(),
+                        bn_struct(layer_a.norm1), partials_a, g_b1.data_ptr(), layer.conv1.weight.data_ptr(),
+                        bn_struct(layer.norm1), _ptr(scratch, plan['offsets'][index][1]) if plan is not None else None,
+                        buffer.data_ptr(), gbuf.data_ptr(), stream)
+                pending = None
+            elif epilogue1 and plan is not None:
                 F._call('srgan_conv2d_bwd_data_bnrelu_partials', _desc(n, cin, h, w, width, 1, 1, 1, 0, buffer_bs, 0),
                         g_b1.data_ptr(), layer.conv1.weight.data_ptr(), bn_struct(layer.norm1), buffer.data_ptr(),
                         gbuf.data_ptr(), _ptr(scratch, plan['offsets'][index][1]), 1, stream)
