@@ -79,6 +79,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE 0x2000u /* ABI 1.1, additive: srgan_conv3x3_image_floats / srgan_h_pack_conv3x3_image /
                                                       srgan_h_pack_job_conv3x3_image and the *_image forms of the fused fp32 3x3
                                                       calls (weights staged from a per-step packed image) */
+#define SRGAN_FEATURE_DROPOUT 0x4000u /* ABI 1.1, additive: srgan_dropout (inverted dropout whose mask is regenerated from the
+                                         device draws' counter-based stream, never stored) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -441,6 +443,29 @@ int srgan_gp_interpolate(const float* unlabeled, const float* fake, const float*
 int srgan_random_fill(float* out, int64_t n, int64_t first, int32_t kind, float offset, int32_t draw, const uint32_t* state,
                       void* stream);
 int srgan_random_advance(uint32_t* state, void* stream);
+/* Inverted dropout whose mask is REGENERATED, never stored (SRGAN_FEATURE_DROPOUT; reference crowd/models.py:350-353, the
+ * F.dropout on a dense layer's new features):
+ *   y[r * y_row_stride + i] = keep(e) ? fl(x[r * x_row_stride + i] * scale) : +0.0f,  e = first + r * row_elems + i,
+ * for r < rows and i < row_elems.  keep(e) is true exactly when element e of the kind 0 (uniform) draw `draw` that
+ * srgan_random_fill defines for the iteration held in `state` -- same key, counter layout and word ownership -- is >= p.
+ * scale = 1.0f / (1.0f - p), computed once in fp32 by the host launcher; the product is rounded once.  p == 0 is a copy;
+ * p == 1 gives all zeros (the uniforms are < 1).  A dropped element is +0.0f whatever x holds (inf and NaN included).
+ * Rows are contiguous runs of row_elems floats (one example's C x H x W); the two strides (in floats) let the call write
+ * into, or read from, a channel slice of a wider NCHW tensor.  x == y is allowed when the strides are equal.  The operation is
+ * linear with a fixed mask, so the same call is the forward, the backward (x = the gradient) and the double backward.
+ * One thread per Philox block (4 elements); 16-byte loads and stores where first, the strides and the pointers allow, single
+ * floats at ragged ends and in misaligned rows, with the same results.  No workspace, no atomics.
+ * Draw ids: 0, 1, 2 are an iteration's three draws; the Python host gives every dropout call of a network's step a draw of
+ * its own from that network's range -- SRGAN_DROPOUT_DRAWS_D / SRGAN_DROPOUT_DRAWS_DNN + the call's index in the step, each
+ * range SRGAN_DROPOUT_DRAW_RANGE wide -- under a state of the network's own that is advanced once per iteration.
+ * Before any device work: NULL x / y / state, negative rows / row_elems / first (or first + rows * row_elems beyond
+ * 2^63 - 1), a stride smaller than row_elems, draw < 0, p outside [0, 1] or non-finite: SRGAN_EINVAL; rows * row_elems above
+ * max_tensor_elements: SRGAN_ERANGE.  Zero elements is a successful no-op. */
+#define SRGAN_DROPOUT_DRAWS_D 0x10000      /* the discriminator's dropout draws: [0x10000, 0x20000) */
+#define SRGAN_DROPOUT_DRAWS_DNN 0x20000    /* the DNN baseline's: [0x20000, 0x30000) */
+#define SRGAN_DROPOUT_DRAW_RANGE 0x10000
+int srgan_dropout(const float* x, float* y, int64_t rows, int64_t row_elems, int64_t x_row_stride, int64_t y_row_stride,
+                  int64_t first, float p, int32_t draw, const uint32_t* state, void* stream);
 /* rows[b] = sum_{hw} mean_c |maps[b,c,hw] - target[b,hw]| and its backward (reference crowd/srgan.py:252). */
 int srgan_crowd_map_l1_fwd(const float* maps, const float* target, float* rows, int32_t B, int32_t Cm, int64_t HW,
                            void* stream);

@@ -102,6 +102,7 @@ SIGNATURES = {
     'srgan_gp_interpolate': ([vp, vp, vp, vp, i32, i64, vp], ctypes.c_int),
     'srgan_random_fill': ([vp, i64, i64, i32, f32, i32, vp, vp], ctypes.c_int),
     'srgan_random_advance': ([vp, vp], ctypes.c_int),
+    'srgan_dropout': ([vp, vp, i64, i64, i64, i64, i64, f32, i32, vp, vp], ctypes.c_int),
     'srgan_crowd_map_l1_fwd': ([vp, vp, vp, i32, i32, i64, vp], ctypes.c_int),
     'srgan_crowd_map_l1_bwd': ([vp, vp, vp, vp, i32, i32, i64, vp], ctypes.c_int),
     'srgan_profile_begin': ([], ctypes.c_int),

@@ -16,8 +16,8 @@ class CrowdDgganExperiment(CrowdExperiment):
     def model_setup(self):
         size = self.settings.image_patch_size
         self.G = DCGenerator(image_size=size, **self.generator_norm_arguments())
-        self.D = KnnDenseNetCatDggan(image_size=size)
-        self.DNN = KnnDenseNetCatDggan(image_size=size)
+        self.D = KnnDenseNetCatDggan(image_size=size, drop_rate=self.dense_drop_rate())
+        self.DNN = KnnDenseNetCatDggan(image_size=size, drop_rate=self.dense_drop_rate())
 
     def _scores(self, examples):
         _ = self.D(examples)

@@ -8,7 +8,7 @@ class CrowdDnnExperiment(DnnExperiment, CrowdExperiment):
     """The DNN-only version of the crowd application."""
 
     def model_setup(self):
-        self.DNN = KnnDenseNetCat(image_size=self.settings.image_patch_size)
+        self.DNN = KnnDenseNetCat(image_size=self.settings.image_patch_size, drop_rate=self.dense_drop_rate())
 
     def validation_summaries(self, step):
         """The DNN's scalar epochs and, with ``settings.image_summaries``, its map comparisons ``Real`` / ``Validation`` when

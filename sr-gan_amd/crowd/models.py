@@ -68,26 +68,34 @@ class _DenseLayer(nn.Sequential):
         self.add_module('relu2', nn.ReLU(inplace=True))
         self.add_module('conv2', nn.Conv2d(bn_size * growth_rate, growth_rate, kernel_size=3, stride=1, padding=1,
                                            bias=False))
+        self.drop_rate = drop_rate
         if drop_rate:
-            raise NotImplementedError('drop_rate > 0 is never used on the hot path (crowd/models.py:1063)')
+            # the new features go through dropout before the concatenation (crowd/models.py:350-353); the mask is regenerated
+            # on the device, so the layer stores nothing for its backward passes (nn.Dropout)
+            self.add_module('dropout', nn.Dropout(drop_rate))
 
     def forward(self, x):
         # BN + ReLU are one fused kernel each (same arithmetic as running norm1, relu1, ... in sequence)
         bottleneck = self.conv1(self.norm1(x, relu=True))
-        return F.cat_channels([x, self.conv2(self.norm2(bottleneck, relu=True))])
+        new_features = self.conv2(self.norm2(bottleneck, relu=True))
+        if self.drop_rate:
+            new_features = self.dropout(new_features)
+        return F.cat_channels([x, new_features])
 
 
 class _DenseBlock(nn.Sequential):
     def __init__(self, num_layers, num_input_features, bn_size, growth_rate, drop_rate=0):
         super().__init__()
+        self.drop_rate = drop_rate
         for i in range(num_layers):
             self.add_module('denselayer%d' % (i + 1),
                             _DenseLayer(num_input_features + i * growth_rate, growth_rate, bn_size, drop_rate))
 
     def forward(self, x):
         """The whole block is one concat-free node (fused.py), first and second order (its recorded backward is
-        itself a node: the gradient penalty); ``fused.ENABLED = False`` selects the layer-by-layer primitive ops."""
-        if not fused.ENABLED:
+        itself a node: the gradient penalty); ``fused.ENABLED = False`` selects the layer-by-layer primitive ops, and so
+        does ``drop_rate > 0`` (the fused node has no mask between a layer's 3x3 convolution and the concatenation)."""
+        if not fused.ENABLED or self.drop_rate:
             return super().forward(x)
         return fused.dense_block(x, list(self.children()))
 

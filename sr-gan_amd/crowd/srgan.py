@@ -53,8 +53,8 @@ class CrowdExperiment(Experiment):
         networks are freshly initialised and a checkpoint can be loaded instead)."""
         size = self.settings.image_patch_size
         self.G = DCGenerator(image_size=size, **self.generator_norm_arguments())
-        self.D = KnnDenseNetCat(image_size=size)
-        self.DNN = KnnDenseNetCat(image_size=size)
+        self.D = KnnDenseNetCat(image_size=size, drop_rate=self.dense_drop_rate())
+        self.DNN = KnnDenseNetCat(image_size=size, drop_rate=self.dense_drop_rate())
 
     def validation_summaries(self, step):
         """The scalar summaries of reference crowd/srgan.py:98-147 when evaluation datasets are attached

@@ -6,32 +6,10 @@
 // not depend on the grid or on the stream schedule.  The stream is defined in include/srgan_hip.h (srgan_random_fill).
 #include <math.h>
 #include "common.h"
+#include "philox.h"      // the round function and unit24, shared with dropout.hip
 
 namespace srgan {
 namespace {
-
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;     // the two round multipliers
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;     // the key schedule's Weyl increments
-constexpr float TWO_POW_MINUS_24 = 5.9604644775390625e-08f;
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds on the counter c
-// under the key (k0, k1), which is bumped between rounds.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(PHILOX_M0, c[0]), lo0 = PHILOX_M0 * c[0];
-    const uint32_t hi1 = __umulhi(PHILOX_M1, c[2]), lo1 = PHILOX_M1 * c[2];
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-}
-
-// The top 24 bits of a word as a multiple of 2^-24 in [0, 1): exact in fp32.
-__device__ __forceinline__ float unit24(uint32_t w) { return (float)(w >> 8) * TWO_POW_MINUS_24; }
 
 // Box-Muller on one word pair: u1 = 1 - unit24(even) in (0, 1], u2 = unit24(odd); the even element gets r cos(2 pi u2),
 // the odd one r sin(2 pi u2).  Precise device functions only (no fast intrinsics), and every product is rounded on its
@@ -55,8 +33,8 @@ __global__ void __launch_bounds__(256) random_fill_kernel(float* __restrict__ ou
   const uint64_t blocks = (((uint64_t)first + (uint64_t)n - 1) >> 2) - first_block + 1;
   for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < blocks; b += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t block = first_block + b;
-    uint32_t w[4] = {(uint32_t)block, (uint32_t)(block >> 32), draw, iteration};
-    philox4x32_10(w, seed_lo, seed_hi);
+    uint32_t w[4];
+    draw_block_words(block, draw, iteration, seed_lo, seed_hi, w);
     float v[4];
     if (kind == 0) {
 #pragma unroll

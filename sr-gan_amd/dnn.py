@@ -21,6 +21,7 @@ class DnnExperiment(Experiment, ABC):
         self.dnn_summary_writer.steps_to_run = self.settings.steps_to_run
 
     def gpu_mode(self):
+        self.refuse_dropout_under_data_parallelism()
         if getattr(self.DNN, '_srgan_arena', None) is None:
             nn.flatten_parameters(self.DNN, current_device())
 

@@ -910,6 +910,23 @@ def random_advance(state):
     _call('srgan_random_advance', state.data_ptr(), _stream())
 
 
+def dropout(x, p, draw, state, first=0):
+    """Inverted dropout of an fp32 NCHW or ``[N, F]`` variable with a mask that is regenerated, never stored: element ``e``
+    of ``x`` is kept (and scaled by ``1 / (1 - p)``) when element ``first + e`` of uniform draw ``draw`` of the iteration in
+    ``state`` is ``>= p`` (``srgan_dropout``, include/srgan_hip.h).  Linear in ``x`` with a fixed mask: the backward is this
+    operation on the gradient -- itself a tape op, so it differentiates to any order -- and nothing is saved but
+    ``(p, draw, first)``.  ``state`` must still hold the forward's iteration when the backward launches (the dropout streams
+    of ``nn.DropoutStream`` are advanced once per iteration, behind the step's last backward)."""
+    if x.meta is not None:
+        raise NotImplementedError('dropout of a blocked (16-bit / blocked-fp32) tensor is not implemented')
+    rows = x.shape[0] if len(x.shape) else 1
+    row_elems = x.numel() // rows if rows else 0
+    data = _empty(x.shape, x.data)
+    _call('srgan_dropout', _ptr(x), data.data_ptr(), rows, row_elems, row_elems, row_elems, int(first), float(p), int(draw),
+          state.data_ptr(), _stream())
+    return _out(data, (x,), lambda g, needs: (dropout(g, p, draw, state, first),), 'dropout')
+
+
 def crowd_map_l1(maps, target):
     """rows[b] = sum_{h,w} mean_c |maps[b,c,h,w] - target[b,h,w]| (reference crowd/srgan.py:252).
     First-order differentiable in ``maps`` (it is never inside the gradient-penalty graph)."""

@@ -190,6 +190,7 @@ class CapturedIteration:
         before = [optimizer.step_count for optimizer in optimizers]
         if e.device_random_draws():
             e.device_draw_state()                             # exists before the capture: made inside it, it would be a host copy
+        e.prepare_dropout_streams()                           # (the same for the networks' dropout states, settings.drop_rate)
         static_inputs = _rebuild(inputs, iter(static))
         injected, e.injected_draws = e.injected_draws, dict(draws)
         graph = torch.cuda.CUDAGraph()

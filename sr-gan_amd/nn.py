@@ -3,6 +3,8 @@ default initialisation (same random stream) and ``state_dict`` keys are the refe
 is replaced: it takes and returns tape ``Var``s and launches HIP kernels.  torch.nn here is a parameter
 container / checkpoint format, not a compute path.
 """
+import contextlib
+
 import torch
 from torch import nn
 
@@ -154,6 +156,105 @@ class AvgPool2d(nn.Module):
 
     def forward(self, x):
         return F.avg_pool2d(x, self.kernel_size, self.stride)
+
+
+class DropoutStream:
+    """Which mask a dropout call of one network gets.  Two parts: a device state ``uint32[4] = {seed_lo, seed_hi,
+    iteration, 0}`` (the state of ``srgan_random_fill``, created at first use) and a host-side call counter.  A
+    training-mode forward of a dropout layer takes ``draw = base + counter++``; the owner resets the counter when the
+    network's step of an iteration begins (``begin_step``) and advances the state once per iteration (``advance``), on the
+    stream the step runs on, behind the last launch that reads it.  Program order then fixes the draw ids: a captured HIP
+    graph bakes in the ids of the eager iterations and replays as the next iteration each time.
+
+    A pass whose place in the host's program order depends on a side-stream setting (the penalty chain's forward, the
+    generator step's D(unlabeled)) numbers its calls in a ``section`` of its own -- a quarter of the range each, section 0 is
+    the rest of the step -- so that a run draws the same masks with the side streams on and off."""
+
+    SECTIONS = 4
+
+    def __init__(self, base, seed=0, iteration=0, draws=0x10000):
+        self.base, self.draws = int(base), int(draws)
+        self.seed, self.iteration = int(seed) & (2 ** 64 - 1), int(iteration) & 0xffffffff
+        self.counter = 0                  # the next id of the section in progress, relative to base
+        self.limit = self.draws // self.SECTIONS
+        self._resume = {}                 # section -> where its numbering goes on when it is entered again in this step
+        self._state = None
+
+    def state(self):
+        if self._state is None:
+            import numpy as np
+            from .utility import current_device
+            words = np.array([self.seed & 0xffffffff, self.seed >> 32, self.iteration, 0], dtype=np.uint32)
+            self._state = torch.from_numpy(words.view(np.int32)).to(current_device())
+        return self._state
+
+    def begin_step(self):
+        self.counter, self.limit = 0, self.draws // self.SECTIONS
+        self._resume = {}
+
+    @contextlib.contextmanager
+    def section(self, index):
+        if not 0 < index < self.SECTIONS:
+            raise ValueError(f'dropout section {index} outside 1 .. {self.SECTIONS - 1}')
+        size = self.draws // self.SECTIONS
+        outer = self.counter, self.limit
+        self.counter, self.limit = self._resume.get(index, index * size), (index + 1) * size
+        try:
+            yield self
+        finally:
+            self._resume[index] = self.counter
+            self.counter, self.limit = outer
+
+    def next_draw(self):
+        if self.counter >= self.limit:
+            raise RuntimeError(f'more than {self.draws // self.SECTIONS} dropout calls in one section of a step: the network\'s '
+                               'range of draw ids is used up')
+        draw = self.base + self.counter
+        self.counter += 1
+        return self.state(), draw
+
+    def advance(self):
+        F.random_advance(self.state())
+
+
+class Dropout(nn.Module):
+    """Inverted dropout with a mask regenerated on the device (``F.dropout``): nothing is stored, the backward and the
+    gradient penalty's double backward draw the same mask again.  In eval mode, or with ``p == 0``, the input itself is
+    returned and nothing is launched.  In training mode the layer asks its network's ``DropoutStream`` (``dropout_stream``,
+    set by ``attach_dropout_stream``) for the state and the draw id of this call."""
+
+    def __init__(self, p=0.5):
+        super().__init__()
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f'dropout probability has to be between 0 and 1, but got {p}')
+        self.p = float(p)
+        self.dropout_stream = None
+
+    def extra_repr(self):
+        return f'p={self.p}'
+
+    def forward(self, x):
+        if not self.training or self.p == 0.0:
+            return x
+        if x.meta is not None:
+            raise NotImplementedError('nn.Dropout on a blocked (16-bit / blocked-fp32) tensor is not implemented')
+        if self.dropout_stream is None:
+            raise RuntimeError('nn.Dropout in training mode needs its network\'s dropout stream (nn.attach_dropout_stream)')
+        state, draw = self.dropout_stream.next_draw()
+        return F.dropout(x, self.p, draw, state)
+
+
+def active_dropout_layers(module):
+    """The dropout layers of ``module`` that do something in training mode (``p > 0``)."""
+    return [layer for layer in module.modules() if isinstance(layer, Dropout) and layer.p > 0.0] if module is not None else []
+
+
+def attach_dropout_stream(module, stream):
+    """Hands ``stream`` to every active dropout layer of ``module``; returns how many there are."""
+    layers = active_dropout_layers(module)
+    for layer in layers:
+        layer.dropout_stream = stream
+    return len(layers)
 
 
 Sequential = nn.Sequential

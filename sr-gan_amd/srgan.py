@@ -17,6 +17,7 @@ Differences from the reference that are deliberate (each keeps results identical
   (``finish_update``): the DNN's exchange runs under the whole GAN step, D's under the generator forward, G's under
   the next iteration's DNN step.  The arithmetic is unchanged.
 """
+import contextlib
 import datetime
 import os
 import re
@@ -96,6 +97,14 @@ def examples_on_gpu():
 
 
 DRAW_Z_D, DRAW_ALPHA, DRAW_Z_G = 0, 1, 2      # the draw ids of an iteration's three device draws (settings.device_random_draws)
+# The draw ids of the dropout masks (settings.drop_rate; SRGAN_DROPOUT_DRAWS_* in include/srgan_hip.h): call k of a network's
+# step of an iteration takes base + k under that network's own state.  Two disjoint ranges, clear of the draws above and of
+# the summary draws 8 and 9.
+DROPOUT_DRAWS_D, DROPOUT_DRAWS_DNN, DROPOUT_DRAW_RANGE = 0x10000, 0x20000, 0x10000
+DROPOUT_DRAW_BASES = {'D': DROPOUT_DRAWS_D, 'DNN': DROPOUT_DRAWS_DNN}
+# Passes of D whose place in the host's program order depends on a side-stream setting number their dropout calls in a section
+# of D's range of their own (nn.DropoutStream.section), so the masks do not depend on the stream settings.
+DROPOUT_SECTION_PENALTY, DROPOUT_SECTION_GENERATOR_UNLABELED = 1, 2
 
 
 def device_draw_window(global_rows, columns, world_size=1, rank=0):
@@ -145,6 +154,7 @@ class Experiment(ABC):
         self.injected_draws = None     # tests: dict with 'z_d', 'z_g', 'alpha' device/CPU tensors, used once
         self.last_losses = {}          # device scalars of the latest step (no host sync)
         self._draw_state = None        # settings.device_random_draws: device int32 x 4 {seed_lo, seed_hi, iteration, 0}
+        self._dropout_streams = {}     # 'D' / 'DNN' -> (network, its nn.DropoutStream or None), made at the first training step
 
     @property
     def parallel(self):
@@ -422,10 +432,18 @@ class Experiment(ABC):
             # per-rank statistics and unsynchronised running buffers would silently differ from one device on the global batch
             raise NotImplementedError('a generator with batch-statistics normalisation (settings.generator_batch_norm) runs on '
                                       'one device only: statistics synchronised across the data-parallel ranks are future work')
+        self.refuse_dropout_under_data_parallelism()
         device = current_device()
         for module in (self.D, self.DNN, self.G):
             if getattr(module, '_srgan_arena', None) is None:
                 nn.flatten_parameters(module, device)
+
+    def refuse_dropout_under_data_parallelism(self):
+        if self.dp is not None and self.dp.world_size > 1 and \
+                any(nn.active_dropout_layers(getattr(self, name, None)) for name in DROPOUT_DRAW_BASES):
+            # a rank would have to mask its rows of the GLOBAL batch's activations (a `first` per call and per layer)
+            raise NotImplementedError('a network with dropout layers (settings.drop_rate > 0) runs on one device only: masks '
+                                      'windowed over the data-parallel ranks are future work')
 
     def cpu_mode(self):
         raise RuntimeError('the MI355X training step has no CPU mode')
@@ -541,6 +559,43 @@ class Experiment(ABC):
         if alpha is None and self.device_random_draws():
             return self._device_draw(DRAW_ALPHA, batch_size, None, 0)
         return as_var((self.draw_interpolation_alpha(batch_size) if alpha is None else alpha).reshape(-1), staged=True)
+
+    # ``settings.drop_rate`` (read with getattr, default 0: no dropout layer exists and none of this runs): dropout on the new
+    # features of every dense layer of D and DNN (reference crowd/models.py:336-353).  The masks come from the counter-based
+    # stream of the device draws and are never stored: a network owns a ``nn.DropoutStream`` -- a device state {seed, iteration}
+    # of its own (seed: ``settings.device_random_seed``; iteration: ``starting_step`` at first use, so a resumed run continues
+    # its masks) and a host-side call counter.  The counter is reset when the network's step of an iteration begins, each
+    # training-mode dropout call takes the next draw id of the network's range, and the state is advanced once per iteration
+    # behind the last launch that reads it (the ordering edges).  The draws' own state is untouched.
+    def dense_drop_rate(self):
+        return float(getattr(self.settings, 'drop_rate', 0) or 0)
+
+    def dropout_stream(self, name):
+        """The dropout stream of network ``name`` ('D' / 'DNN'), or None when it has no active dropout layer."""
+        network = getattr(self, name, None)
+        streams = self.__dict__.setdefault('_dropout_streams', {})
+        known = streams.get(name)
+        if known is None or known[0] is not network:
+            stream = None
+            if nn.active_dropout_layers(network):
+                stream = nn.DropoutStream(DROPOUT_DRAW_BASES[name], getattr(self.settings, 'device_random_seed', 0),
+                                          self.starting_step, DROPOUT_DRAW_RANGE)
+                nn.attach_dropout_stream(network, stream)
+            known = streams[name] = (network, stream)
+        return known[1]
+
+    def dropout_section(self, name, index):
+        """Context manager: the dropout calls of network ``name`` inside it take their draw ids from section ``index``."""
+        stream = self.dropout_stream(name)
+        return contextlib.nullcontext() if stream is None else stream.section(index)
+
+    def prepare_dropout_streams(self):
+        """The device states exist (a HIP graph capture must not be the first to need them: made inside it, a state would be
+        a copy from the host)."""
+        for name in DROPOUT_DRAW_BASES:
+            stream = self.dropout_stream(name)
+            if stream is not None:
+                stream.state()
 
     # ------------------------------------------------------------------------------------------ batch reductions
     def _global_batch(self, local):
@@ -733,10 +788,17 @@ class Experiment(ABC):
         self.dnn_summary_writer.step = step
         self.finish_update('DNN')
         self.dnn_optimizer.zero_grad()
+        dropout = self.dropout_stream('DNN')
+        if dropout is not None:
+            dropout.begin_step()
         exchange = self.gradient_exchange(self.DNN)
         with self.precision():
             dnn_loss = self.dnn_loss_calculation(examples, labels)
             self.scaled_backward(dnn_loss, grad_ready=exchange)
+        if dropout is not None:
+            # the DNN's masks of this iteration are all drawn: every launch that reads the state -- the forward's and the
+            # backward's dropout kernels -- is on this stream, in front of this line
+            dropout.advance()
         self.start_update('DNN', self.dnn_optimizer, exchange)       # finished at the end of gan_training_step
         self.last_losses['dnn_loss'] = dnn_loss
         if self.dnn_summary_writer.is_summary_step():
@@ -755,6 +817,9 @@ class Experiment(ABC):
         self.gan_summary_writer.step = step
         self.finish_update('G', 'D')         # the previous iteration's generator update (its exchange ran under the DNN step)
         self.d_optimizer.zero_grad()
+        dropout = self.dropout_stream('D')
+        if dropout is not None:
+            dropout.begin_step()
         batch_size = unlabeled_examples.shape[0]
         penalty_stream = None
         with self.precision():
@@ -818,6 +883,14 @@ class Experiment(ABC):
             # previous advance) before its chain started and which this stream waited for above, before the arenas were
             # added; the DNN chain and the auxiliary forward draw nothing.  A captured step holds the same edges.
             F.random_advance(self.device_draw_state())
+        if dropout is not None:
+            # ONE advance of D's dropout state per iteration, on the main stream, behind every launch that reads it: the
+            # stacked pass, D(fake) of the generator step and their backwards run on this stream; the penalty chain (forward,
+            # recorded backward, double backward) runs on the penalty stream, which waited for this stream (behind the
+            # previous advance) before it started and which this stream waited for before the arenas were added; D(u) of
+            # the generator step runs on the auxiliary stream between its wait for this stream and this stream's wait for it
+            # (generator_loss_calculation).  A captured step holds the same edges.
+            dropout.advance()
         self.finish_update('D', 'DNN')
         self.last_losses.update(labeled_loss=labeled_loss, unlabeled_loss=unlabeled_loss, fake_loss=fake_loss,
                                 gradient_penalty=gradient_penalty, generator_loss=generator_loss)
@@ -952,7 +1025,8 @@ class Experiment(ABC):
         expected = settings.batch_size if self.dp is None else self.dp.local_batch(settings.batch_size)
         alpha = self.sample_interpolation_alpha(expected)
         interpolates = F.gp_interpolate(unlabeled_examples.detach(), fake_examples.detach(), alpha)
-        interpolates_loss = self.interpolate_loss_calculation(interpolates)
+        with self.dropout_section('D', DROPOUT_SECTION_PENALTY):
+            interpolates_loss = self.interpolate_loss_calculation(interpolates)
         gradients, = backward(interpolates_loss, grad=F.full_like(interpolates_loss, 1.0), inputs=[interpolates],
                               create_graph=True)
         gradient_norm = F.row_norm(F.flatten2d(gradients))
@@ -974,7 +1048,7 @@ class Experiment(ABC):
             if side is None:
                 _ = self.D(fake_examples)
                 self.fake_features = self.D.features
-                with no_grad():
+                with no_grad(), self.dropout_section('D', DROPOUT_SECTION_GENERATOR_UNLABELED):
                     _ = self.D(unlabeled_examples)
                     detached_unlabeled_features = self.D.features.detach()
             else:
@@ -982,7 +1056,7 @@ class Experiment(ABC):
                 # run on a second stream next to D(fake)'s, which on their own cannot fill the GPU on the small planes
                 main = torch.cuda.current_stream()
                 side.wait_stream(main)                   # the discriminator update and the batch are enqueued on main
-                with torch.cuda.stream(side), no_grad():
+                with torch.cuda.stream(side), no_grad(), self.dropout_section('D', DROPOUT_SECTION_GENERATOR_UNLABELED):
                     _ = self.D(unlabeled_examples)
                     detached_unlabeled_features = self.D.features.detach()
                 detached_unlabeled_features.data.record_stream(main)
