@@ -81,6 +81,9 @@ const char* srgan_last_error(void);
                                                       calls (weights staged from a per-step packed image) */
 #define SRGAN_FEATURE_DROPOUT 0x4000u /* ABI 1.1, additive: srgan_dropout (inverted dropout whose mask is regenerated from the
                                          device draws' counter-based stream, never stored) */
+#define SRGAN_FEATURE_FEATURE_LOSSES 0x8000u /* ABI 1.1, additive: srgan_feature_corrcoef_l1_fwd / _bwd / _scratch_bytes (the
+                                                correlation-matrix feature loss, fused) and unary ops 20-22 (acos, clamp,
+                                                in_range) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -271,7 +274,8 @@ int srgan_gemm(int32_t M, int32_t N, int32_t K, const float* A, int64_t sai, int
 /* ---- elementwise ------------------------------------------------------------------------------------------
  * Unary op codes: 0 copy, 1 neg, 2 abs, 3 sign, 4 sqrt, 5 exp, 6 log, 7 log1p, 8 square, 9 reciprocal, 10 tanh,
  * 11 relu, 12 step (x > 0), 13 affine (p0*x + p1), 14 pow (x^p0), 15 leaky_relu (slope p0), 16 sigmoid,
- * 17 softplus, 18 one_minus_square, 19 rsqrt.
+ * 17 softplus, 18 one_minus_square, 19 rsqrt, 20 acos, 21 clamp (to [p0, p1]; by comparisons, so a NaN stays a NaN as in
+ * torch.clamp), 22 in_range (1 where p0 <= x <= p1, else 0 -- NaN included: the gradient mask of clamp, edges inclusive).
  * Binary op codes: 0 add, 1 sub, 2 mul, 3 div, 4 div_safe (0 where b == 0), 5 max,
  * 6 leaky_mask_mul (a where b > 0 else p0*a: the backward of leaky_relu / relu), 7 axpy (a + p0*b).
  * tanh is exactly +-1 from |x| = 9 on (1 - tanh(9) = 3.0e-8 is below the fp32 spacing 2^-24 under 1: at most 0.51 ulp off).
@@ -466,6 +470,34 @@ int srgan_random_advance(uint32_t* state, void* stream);
 #define SRGAN_DROPOUT_DRAW_RANGE 0x10000
 int srgan_dropout(const float* x, float* y, int64_t rows, int64_t row_elems, int64_t x_row_stride, int64_t y_row_stride,
                   int64_t first, float p, int32_t draw, const uint32_t* state, void* stream);
+/* The correlation-matrix feature loss without its F x F matrices (SRGAN_FEATURE_FEATURE_LOSSES; reference srgan.py:511-535,
+ * feature_covariance_loss).  base / other: features [B, F], fp32, row-major, contiguous.  Per side, with n = B:
+ *   m_i = mean of column i, xm = x - m, s_i^2 = sum_b xm_bi^2 / (n - 1),
+ *   C_ij = clamp(sum_b xm_bi xm_bj / ((n - 1) s_i s_j), -1, 1),          loss[0] = sum_{i != j} |Cb_ij - Co_ij|.
+ * Evaluated as C = Z Z^T with z_i = xm_i / ||xm_i|| on the fp32 MFMA (v_mfma_f32_32x32x2_f32, K = batch); no entry of C is
+ * ever stored.  THE DIAGONAL CONTRIBUTES EXACTLY 0: C_ii = 1 on both sides in exact arithmetic (the reference's fp32 diagonal
+ * differs from that by at most an ulp per feature).  An entry whose unclamped value lies strictly outside [-1, 1] is clamped
+ * and passes no gradient (on that side).  A feature with zero variance gives NaN for the loss and for every gradient element.
+ * loss(x, x) is exactly 0.  No atomics and no meeting of workgroups inside a launch: sums are taken in a fixed order, two calls
+ * on the same inputs give the same bits.  No host synchronisation, no allocation, no use of the stream's workspace.
+ *   saved    [2][3][F] floats written by _fwd, read by _bwd: per side (0 base, 1 other) and feature the mean, 1 / ||xm_i|| and
+ *            r_i = sum_{j != i} G_ij C_ij with G_ij = sign(Cb_ij - Co_ij) (negated on the other side), 0 where the side's
+ *            entry was clamped
+ *   scratch  srgan_feature_corrcoef_l1_scratch_bytes(B, F) bytes of the CALLER's, 16-byte aligned: the normalised, transposed,
+ *            zero-padded copies Z [2][round_up(F, 128)][round_up(B, 32)] and the per-split partial sums.  _bwd reads the Z that
+ *            _fwd left there, so the same buffer goes to both calls, untouched in between.
+ * _bwd: grad_x = 2 g[0] / ||xm_i|| * ((G Z)_i - r_i z_i) for each requested side, [B, F]; grad_base or grad_other may be
+ * NULL (the generator's loss needs `other` only; both NULL is a no-op); every element of a requested gradient is written.
+ * It recomputes the Gram tiles (one more pass, once per side and per 128 examples).  First order only.
+ * Capacity: 2 <= B <= 8192, 1 <= F <= 2^20, round_up(F, 128) * round_up(B, 32) <= 2^26 (512 MiB of Z); the scratch query
+ * returns the bytes (> 0) or the status.  Before any device work: NULL base / other / loss / saved / scratch / g or a
+ * misaligned scratch, B < 2, F < 1: SRGAN_EINVAL; a shape beyond the capacity: SRGAN_ERANGE with the shape in
+ * srgan_last_error(). */
+int64_t srgan_feature_corrcoef_l1_scratch_bytes(int32_t B, int32_t F);
+int srgan_feature_corrcoef_l1_fwd(const float* base, const float* other, float* loss, float* saved, float* scratch, int32_t B,
+                                  int32_t F, void* stream);
+int srgan_feature_corrcoef_l1_bwd(const float* base, const float* other, const float* saved, const float* scratch, const float* g,
+                                  float* grad_base, float* grad_other, int32_t B, int32_t F, void* stream);
 /* rows[b] = sum_{hw} mean_c |maps[b,c,hw] - target[b,hw]| and its backward (reference crowd/srgan.py:252). */
 int srgan_crowd_map_l1_fwd(const float* maps, const float* target, float* rows, int32_t B, int32_t Cm, int64_t HW,
                            void* stream);

@@ -105,6 +105,9 @@ SIGNATURES = {
     'srgan_dropout': ([vp, vp, i64, i64, i64, i64, i64, f32, i32, vp, vp], ctypes.c_int),
     'srgan_crowd_map_l1_fwd': ([vp, vp, vp, i32, i32, i64, vp], ctypes.c_int),
     'srgan_crowd_map_l1_bwd': ([vp, vp, vp, vp, i32, i32, i64, vp], ctypes.c_int),
+    'srgan_feature_corrcoef_l1_scratch_bytes': ([i32, i32], ctypes.c_int64),
+    'srgan_feature_corrcoef_l1_fwd': ([vp, vp, vp, vp, vp, i32, i32, vp], ctypes.c_int),
+    'srgan_feature_corrcoef_l1_bwd': ([vp, vp, vp, vp, vp, vp, vp, i32, i32, vp], ctypes.c_int),
     'srgan_profile_begin': ([], ctypes.c_int),
     'srgan_profile_end': ([ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),

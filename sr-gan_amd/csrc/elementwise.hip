@@ -7,7 +7,8 @@
 namespace srgan {
 
 enum UnaryOp { U_COPY = 0, U_NEG, U_ABS, U_SIGN, U_SQRT, U_EXP, U_LOG, U_LOG1P, U_SQUARE, U_RECIP, U_TANH, U_RELU,
-               U_STEP, U_AFFINE, U_POW, U_LEAKY, U_SIGMOID, U_SOFTPLUS, U_ONE_MINUS_SQ, U_RSQRT, U_COUNT };
+               U_STEP, U_AFFINE, U_POW, U_LEAKY, U_SIGMOID, U_SOFTPLUS, U_ONE_MINUS_SQ, U_RSQRT, U_ACOS, U_CLAMP,
+               U_IN_RANGE, U_COUNT };
 enum BinaryOp { B_ADD = 0, B_SUB, B_MUL, B_DIV, B_DIV_SAFE, B_MAX, B_LEAKY_MASK_MUL, B_AXPY, B_COUNT };
 
 template <int OP>
@@ -33,6 +34,9 @@ __device__ __forceinline__ float unary(float x, float p0, float p1) {
     case U_SOFTPLUS: return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
     case U_ONE_MINUS_SQ: return 1.f - x * x;
     case U_RSQRT: return 1.f / sqrtf(x);
+    case U_ACOS: return acosf(x);
+    case U_CLAMP: return x < p0 ? p0 : (x > p1 ? p1 : x);             // comparisons, not fminf / fmaxf: a NaN stays a NaN (torch.clamp)
+    case U_IN_RANGE: return (x >= p0 && x <= p1) ? 1.f : 0.f;         // clamp's gradient mask, edges inclusive; NaN -> 0
   }
   return x;
 }
@@ -351,6 +355,7 @@ int srgan_ew_unary(int op, const float* x, float* y, int64_t n, float p0, float 
     CASE(U_COPY) CASE(U_NEG) CASE(U_ABS) CASE(U_SIGN) CASE(U_SQRT) CASE(U_EXP) CASE(U_LOG) CASE(U_LOG1P)
     CASE(U_SQUARE) CASE(U_RECIP) CASE(U_TANH) CASE(U_RELU) CASE(U_STEP) CASE(U_AFFINE) CASE(U_POW) CASE(U_LEAKY)
     CASE(U_SIGMOID) CASE(U_SOFTPLUS) CASE(U_ONE_MINUS_SQ) CASE(U_RSQRT)
+    CASE(U_ACOS) CASE(U_CLAMP) CASE(U_IN_RANGE)
 #undef CASE
   }
   return SRGAN_EINVAL;

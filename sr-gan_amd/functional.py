@@ -14,7 +14,7 @@ from .tape import Var, Node, grad_enabled, no_grad, accumulates_into
 
 # op codes of srgan_ew_unary / srgan_ew_binary (include/srgan_hip.h)
 U_COPY, U_NEG, U_ABS, U_SIGN, U_SQRT, U_EXP, U_LOG, U_LOG1P, U_SQUARE, U_RECIP, U_TANH, U_RELU, U_STEP, U_AFFINE, \
-    U_POW, U_LEAKY, U_SIGMOID, U_SOFTPLUS, U_ONE_MINUS_SQ, U_RSQRT = range(20)
+    U_POW, U_LEAKY, U_SIGMOID, U_SOFTPLUS, U_ONE_MINUS_SQ, U_RSQRT, U_ACOS, U_CLAMP, U_IN_RANGE = range(23)
 B_ADD, B_SUB, B_MUL, B_DIV, B_DIV_SAFE, B_MAX, B_LEAKY_MASK_MUL, B_AXPY = range(8)
 
 FORCE_KERNEL = 0   # tests set 1 (direct) / 2 (MFMA) to cross-check the two contraction kernels
@@ -293,6 +293,18 @@ def sigmoid(x):
 
 def softplus(x):
     return _unary(U_SOFTPLUS, x, lambda g, needs: (mul(g, sigmoid(x)),), 'softplus')
+
+
+def acos(x):
+    """acos(x); d/dx = -1 / sqrt(1 - x^2), written with tape operations (differentiable to any order)."""
+    return _unary(U_ACOS, x, lambda g, needs: (neg(div(g, sqrt(one_minus_square(x)))),), 'acos')
+
+
+def clamp(x, low, high):
+    """torch.clamp(x, low, high): the gradient passes where low <= x <= high (edges included) and is 0 elsewhere; the mask
+    is a constant, so the backward is linear in the gradient and differentiates to any order.  A NaN stays a NaN."""
+    low, high = float(low), float(high)
+    return _unary(U_CLAMP, x, lambda g, needs: (mul(g, Var(_unary_raw(U_IN_RANGE, x.data, low, high))),), 'clamp', low, high)
 
 
 def view(x, shape):
@@ -942,6 +954,42 @@ def crowd_map_l1(maps, target):
         _call('srgan_crowd_map_l1_bwd', _ptr(maps), _ptr(target), _ptr(g), gm.data_ptr(), b, cm, hw, _stream())
         return (Var(gm),)
     return _out(data, (maps,), backward, 'crowd_map_l1')
+
+
+def feature_corrcoef_l1(base, other):
+    """sum_{i != j} |corrcoef(base)_ij - corrcoef(other)_ij| of two ``[B, F]`` feature batches -> shape [1], fused
+    (``srgan_feature_corrcoef_l1_fwd`` / ``_bwd``, include/srgan_hip.h): no F x F matrix is stored.  The scratch (the two
+    normalised, transposed copies of the inputs) and the saved statistics come from torch's allocator, not from the stream's
+    workspace, and live until the backward has run.  FIRST ORDER ONLY, like ``crowd_map_l1``: nothing in a step
+    differentiates a feature loss twice (the penalty's double backward goes through the interpolates' scores)."""
+    if len(base.shape) != 2 or tuple(base.shape) != tuple(other.shape):
+        raise ValueError(f'feature_corrcoef_l1: two [B, F] tensors of one shape, got {tuple(base.shape)} and {tuple(other.shape)}')
+    b, f = base.shape
+    library = _lib.library()
+    scratch_bytes = library.srgan_feature_corrcoef_l1_scratch_bytes(b, f)
+    if scratch_bytes < 0:
+        _lib.check(int(scratch_bytes), 'srgan_feature_corrcoef_l1_scratch_bytes')
+    x, y = base.data, other.data
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if not y.is_contiguous():
+        y = y.contiguous()
+    scratch = torch.empty(scratch_bytes // 4, dtype=torch.float32, device=x.device)
+    saved = _empty((2, 3, f), x)
+    data = _empty((1,), x)
+    _call('srgan_feature_corrcoef_l1_fwd', x.data_ptr(), y.data_ptr(), data.data_ptr(), saved.data_ptr(), scratch.data_ptr(), b, f,
+          _stream())
+
+    def backward(g, needs):
+        if grad_enabled():
+            raise NotImplementedError('feature_corrcoef_l1 (feature_covariance_loss) is first-order only')
+        upstream = g.data if g.data.is_contiguous() else g.data.contiguous()
+        g_base = _empty((b, f), x) if needs[0] else None
+        g_other = _empty((b, f), x) if needs[1] else None
+        _call('srgan_feature_corrcoef_l1_bwd', x.data_ptr(), y.data_ptr(), saved.data_ptr(), scratch.data_ptr(),
+              upstream.data_ptr(), _ptr(g_base), _ptr(g_other), b, f, _stream())
+        return (Var(g_base) if needs[0] else None), (Var(g_other) if needs[1] else None)
+    return _out(data, (base, other), backward, 'feature_corrcoef_l1')
 
 
 def row_max(x2d):

@@ -36,7 +36,8 @@ from .optim import Adam
 from .settings import Settings
 from .tape import Var, backward, no_grad
 from . import image_summaries
-from .utility import SummaryWriter, MixtureModel, current_device, make_directory_name_unique, seed_all, to_image_range
+from .utility import SummaryWriter, MixtureModel, current_device, make_directory_name_unique, norm_squared, seed_all, \
+    to_image_range
 
 
 def as_var(value, staged=False):
@@ -102,6 +103,8 @@ DRAW_Z_D, DRAW_ALPHA, DRAW_Z_G = 0, 1, 2      # the draw ids of an iteration's t
 # the summary draws 8 and 9.
 DROPOUT_DRAWS_D, DROPOUT_DRAWS_DNN, DROPOUT_DRAW_RANGE = 0x10000, 0x20000, 0x10000
 DROPOUT_DRAW_BASES = {'D': DROPOUT_DRAWS_D, 'DNN': DROPOUT_DRAWS_DNN}
+# Optional settings (None or a callable) that replace Experiment.feature_distance_loss: see there.
+FEATURE_LOSS_SETTINGS = ('matching_feature_loss', 'contrasting_feature_loss')
 # Passes of D whose place in the host's program order depends on a side-stream setting number their dropout calls in a section
 # of D's range of their own (nn.DropoutStream.section), so the masks do not depend on the stream settings.
 DROPOUT_SECTION_PENALTY, DROPOUT_SECTION_GENERATOR_UNLABELED = 1, 2
@@ -433,6 +436,7 @@ class Experiment(ABC):
             raise NotImplementedError('a generator with batch-statistics normalisation (settings.generator_batch_norm) runs on '
                                       'one device only: statistics synchronised across the data-parallel ranks are future work')
         self.refuse_dropout_under_data_parallelism()
+        self.refuse_feature_loss_hooks_under_data_parallelism()
         device = current_device()
         for module in (self.D, self.DNN, self.G):
             if getattr(module, '_srgan_arena', None) is None:
@@ -444,6 +448,13 @@ class Experiment(ABC):
             # a rank would have to mask its rows of the GLOBAL batch's activations (a `first` per call and per layer)
             raise NotImplementedError('a network with dropout layers (settings.drop_rate > 0) runs on one device only: masks '
                                       'windowed over the data-parallel ranks are future work')
+
+    def refuse_feature_loss_hooks_under_data_parallelism(self):
+        if self.dp is not None and self.dp.world_size > 1 and \
+                any(getattr(self.settings, name, None) is not None for name in FEATURE_LOSS_SETTINGS):
+            # a hook sees this rank's rows only: the batch means / Gram matrices of a sharded batch need collectives of their own
+            raise NotImplementedError('settings.matching_feature_loss / settings.contrasting_feature_loss run on one device '
+                                      'only: feature losses over a batch sharded across data-parallel ranks are future work')
 
     def cpu_mode(self):
         raise RuntimeError('the MI355X training step has no CPU mode')
@@ -1200,7 +1211,22 @@ class Experiment(ABC):
             param_group['lr'] = lr
 
     def feature_distance_loss(self, base_features, other_features, distance_function=None):
-        """distance(mean_b(base) - mean_b(other)) (reference srgan.py:438-449)."""
+        """distance(mean_b(base) - mean_b(other)) (reference srgan.py:438-449).
+
+        ``settings.matching_feature_loss`` / ``settings.contrasting_feature_loss`` (read with ``getattr``, default None: not
+        part of ``Settings``) replace it: each is a callable ``(base_features, other_features) -> scalar Var``, e.g.
+        ``feature_covariance_loss`` or ``feature_angle_loss`` below.  A call without ``distance_function`` (the unlabeled
+        loss and the generator loss) uses the matching one, the call that passes ``settings.contrasting_distance_function``
+        (the fake loss) the contrasting one.  A hook gets the features as the discriminator left them and decides about
+        means and norms itself: ``settings.normalize_feature_norm`` is ignored.  One device only (``gpu_mode`` refuses them
+        under data parallelism)."""
+        hook = None
+        if distance_function is None:
+            hook = getattr(self.settings, 'matching_feature_loss', None)
+        elif distance_function is self.settings.contrasting_distance_function:
+            hook = getattr(self.settings, 'contrasting_feature_loss', None)
+        if hook is not None:
+            return hook(base_features, other_features)
         if distance_function is None:
             distance_function = self.settings.matching_distance_function
         normalize = self.settings.normalize_feature_norm
@@ -1255,6 +1281,89 @@ class _Contexts:
     def __exit__(self, *exc):
         for manager in reversed(self.managers):
             manager.__exit__(*exc)
+
+
+# --------------------------------------------------------------------- alternative feature losses (reference srgan.py:472-535)
+# Tape functions of two feature batches [B, F...]; any of them can be a settings.matching_feature_loss /
+# settings.contrasting_feature_loss (Experiment.feature_distance_loss).  Scalars have shape [1], as everywhere on the tape.
+def _batch_mean(features):
+    rows = F.flatten2d(features)
+    return F.scale(F.col_sum(rows), 1.0 / rows.shape[0])
+
+
+def unit_vector(vector):
+    """vector / (|vector| + 1e-10) (reference srgan.py:472-474)."""
+    flat = F.view(vector, (vector.numel(),))
+    norm_plus_epsilon = F.add_scalar(F.sqrt(F.sum_all(F.square(flat))), 1e-10)
+    return F.view(F.scalar_mul(flat, F.div(F.full_like(norm_plus_epsilon, 1.0), norm_plus_epsilon)), vector.shape)
+
+
+def angle_between(vector0, vector1):
+    """The angle between two vectors, their cosine clamped to +-(1 - 1e-6) (reference srgan.py:477-482)."""
+    epsilon = 1e-6
+    cosine = F.sum_all(F.mul(unit_vector(vector0), unit_vector(vector1)))
+    return F.acos(F.clamp(cosine, -1.0 + epsilon, 1.0 - epsilon))
+
+
+def square(tensor):
+    """Squares the tensor value (reference srgan.py:485-487)."""
+    return F.square(tensor)
+
+
+def feature_distance_loss_unmeaned(base_features, other_features, distance_function=square):
+    """mean(distance(mean_b(base) - other)): only the base is averaged over the batch (reference srgan.py:490-494)."""
+    other_rows = F.flatten2d(other_features)
+    difference = F.sub(F.col_broadcast(_batch_mean(base_features), other_rows.shape[0]), other_rows)
+    return F.mean_all(distance_function(difference))
+
+
+def feature_distance_loss_both_unmeaned(base_features, other_features, distance_function=norm_squared):
+    """mean(distance(base - other)), example by example (reference srgan.py:497-500)."""
+    return F.mean_all(distance_function(F.sub(F.flatten2d(base_features), F.flatten2d(other_features))))
+
+
+def feature_angle_loss(base_features, other_features, target=0, summary_writer=None):
+    """|angle(mean_b(base), mean_b(other)) - target|^2 (reference srgan.py:503-508).  A ``summary_writer`` logs
+    ``Feature Vector/Angle`` -- through ``.item()``, a host synchronisation: pass none inside a captured step."""
+    angle = angle_between(_batch_mean(base_features), _batch_mean(other_features))
+    if summary_writer:
+        summary_writer.add_scalar('Feature Vector/Angle', angle.item())
+    return F.square(F.abs_(F.add_scalar(angle, -float(target))))
+
+
+def _correlation(xm, observations_in_rows):
+    count = xm.shape[0] if observations_in_rows else xm.shape[1]
+    covariance = F.scale(F.mm(xm, xm, transpose_a=observations_in_rows, transpose_b=not observations_in_rows), 1.0 / (count - 1))
+    # (the diagonal of the covariance as the sums of squares it is made of: the tape has no diag(); equal in exact arithmetic)
+    squares = F.col_sum(F.square(xm)) if observations_in_rows else F.row_sum(F.square(xm))
+    stddev = F.sqrt(F.scale(squares, 1.0 / (count - 1)))
+    inverse = F.div(F.full_like(stddev, 1.0), stddev)
+    size = covariance.shape[0]
+    by_columns = F.chan_affine(covariance, None, inverse, None, None, dims=(size, size, 1))
+    return F.clamp(F.row_scale(by_columns, inverse), -1.0, 1.0)
+
+
+def corrcoef(x):
+    """The correlation coefficients of the ROWS of ``x`` [variables, observations] as a MATERIALISED matrix, composed of
+    ``F.mm`` and elementwise tape operations (reference srgan.py:517-528): for a small number of variables and for callers
+    who want the matrix.  ``feature_covariance_loss`` does NOT go through it."""
+    mean = F.scale(F.row_sum(x), 1.0 / x.shape[1])
+    return _correlation(F.sub(x, F.row_broadcast(mean, x.shape)), observations_in_rows=False)
+
+
+def feature_corrcoef(x):
+    """``corrcoef`` of the features (columns) of ``x`` [B, F] -> [F, F] (reference srgan.py:511-514), materialised; the
+    transposition is folded into the contraction."""
+    rows = F.flatten2d(x)
+    xm = F.sub(rows, F.col_broadcast(_batch_mean(rows), rows.shape[0]))
+    return _correlation(xm, observations_in_rows=True)
+
+
+def feature_covariance_loss(base_features, other_features):
+    """sum |feature_corrcoef(base) - feature_corrcoef(other)| (reference srgan.py:531-535) as ONE fused operation
+    (``F.feature_corrcoef_l1``): the two F x F matrices are formed tile by tile on the fp32 MFMA and never stored, so it runs
+    at F = 4096 (VGG) and F = 32768 (the DCGAN discriminators) too.  The diagonal contributes exactly 0; first order only."""
+    return F.feature_corrcoef_l1(F.flatten2d(base_features), F.flatten2d(other_features))
 
 
 def disable_batch_norm_updates(module):
