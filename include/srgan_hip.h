@@ -84,6 +84,8 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_FEATURE_LOSSES 0x8000u /* ABI 1.1, additive: srgan_feature_corrcoef_l1_fwd / _bwd / _scratch_bytes (the
                                                 correlation-matrix feature loss, fused) and unary ops 20-22 (acos, clamp,
                                                 in_range) */
+#define SRGAN_FEATURE_CROWD_EVALUATION 0x10000u /* ABI 1.1, additive: srgan_crowd_evaluation_sums / _scratch_bytes (the sums
+                                                   behind the crowd evaluation scalars, from batches resident on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -513,6 +515,33 @@ int srgan_crowd_extract_patches(const void* const* images_u8, const float* const
                                 const int32_t* heights, const int32_t* widths, const int32_t* ys, const int32_t* xs,
                                 const int32_t* flips, int32_t B, int32_t P, float* out_images, float* out_labels,
                                 float* out_maps, void* stream);
+/* The sums behind the crowd evaluation scalars (SRGAN_FEATURE_CROWD_EVALUATION; reference crowd/srgan.py:149-191: count ME /
+ * MAE / MSE and kNN-map MAE / MSE) of one batch that lives on the device.  predicted_counts [B]; labels [B, HW], the head-count
+ * label patches; predicted_maps [B, M, HW] and maps [B, HW], both or neither; all fp32, contiguous.  With L_b = the sum of
+ * labels[b, :] and d_b = (double)predicted_counts[b] - L_b the call ADDS to the caller's eight doubles `sums`
+ *   sums[0] += sum_b d_b      sums[1] += sum_b |d_b|      sums[2] += sum_b d_b * d_b      sums[3] += B
+ * and, when the map pointers are given, with e = (double)predicted_maps[b, m, i] - (double)maps[b, i],
+ *   sums[4] += sum |e|        sums[5] += sum e * e        sums[6] += B * M * HW
+ * sums[7] is reserved and never touched.  Every accumulation is fp64; every square is rounded as a product before it is added
+ * (no FMA contraction): each term is the one NumPy float64 arithmetic forms from the same fp32 inputs, only the order of the
+ * additions differs.  Two launches on `stream`, nothing else: a partials kernel (256 threads per workgroup over (example,
+ * 2048-element chunk of the plane); 16-byte loads where HW % 4 == 0 and labels / predicted_maps / maps are 16-byte aligned,
+ * element loads otherwise) leaves three doubles per workgroup in `scratch`, and a one-workgroup kernel adds them in a fixed
+ * order (16 lanes per example, lane s adding the example's slots s, s + 16, ... in that order; a butterfly over the 16; then
+ * the examples' terms over the 256 threads in a fixed tree) and updates `sums`.
+ * No atomics, no meeting of workgroups inside a launch, no workspace of the stream: the same inputs give the same bits.
+ * `scratch`: srgan_crowd_evaluation_scratch_bytes(B, M, HW) bytes of the caller's, 8-byte aligned, fully overwritten before
+ * it is read (it may hold anything).  The query returns the bytes (> 0) or the status.
+ * Before any device work: NULL predicted_counts / labels / sums / scratch, exactly one of predicted_maps / maps, B < 0,
+ * HW < 0, M < 1 with maps (M is ignored without), a misaligned sums / scratch: SRGAN_EINVAL; B * M * HW (B * HW without maps)
+ * above max_tensor_elements, or more than 2^24 - 1 workgroups (B * ceil(HW / 2048): a launch holds fewer than 2^32 threads;
+ * an evaluation batch at 512 x 512 / 16 is 2048): SRGAN_ERANGE, from the query too.  B == 0 or HW == 0: SRGAN_OK, `sums`
+ * untouched.  The translation unit is compiled with FMA contraction off (`#pragma clang fp contract(off)`): the squares are
+ * v_mul_f64 + v_add_f64 in the kernels' code. */
+int srgan_crowd_evaluation_sums(const float* predicted_counts, const float* labels, const float* predicted_maps,
+                                const float* maps, int32_t B, int32_t M, int64_t HW, double* sums, void* scratch,
+                                void* stream);
+int64_t srgan_crowd_evaluation_scratch_bytes(int32_t B, int32_t M, int64_t HW);
 
 /* Training-batch assembly from a database of equally sized frames resident on the device (SRGAN_FEATURE_IMAGE_BATCHES):
  * the reference's AgeDataset / SteeringAngleDataset items (age/data.py:52-60, driving/data.py:44-51) collated by its

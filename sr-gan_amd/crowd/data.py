@@ -2,7 +2,10 @@
 image (reference crowd/data.py:370-453,521-560) and the uint8 -> [-1, 1] normalisation (crowd/data.py:115-128).
 ``ImageSlidingWindowDataset`` is the host-side NumPy form and the single source of the window positions;
 ``DeviceSlidingWindows`` cuts the same windows on the device from a scene resident in HBM, as ``DeviceCrowdPatchLoader``
-does for training batches.  The reference's training datasets / preprocessors stay out of scope."""
+does for training batches; ``ResidentCrowdEvaluationSet`` holds the fixed patches a validation epoch scores (DESIGN.md
+section 3h).  The reference's training datasets / preprocessors stay out of scope."""
+from enum import Enum
+
 import numpy as np
 import torch
 
@@ -99,6 +102,74 @@ class PreprocessedCrowdDataset:
                 (self[index] for index in range(self.length))]
 
 
+class CrowdDataset(Enum):
+    """Selects the crowd dataset (``settings.crowd_dataset``; reference crowd/data.py:13-18)."""
+    ucf_qnrf = 'UCF QNRF'
+    shanghai_tech = 'ShanghaiTech'
+    world_expo = 'World Expo'
+
+
+class UcfQnrfCrowdDataset:
+    """Full-image examples of a UCF-QNRF database as the reference's preprocessor writes it and its
+    ``UcfQnrfFullImageDataset`` reads it (crowd/ucf_qnrf_data.py:18-53): ``<database_directory>/<Train|Test>/{images,
+    labels,<map_directory_name>}/*.npy``.  The ``.npy`` names of ``labels`` are sorted and then shuffled by
+    ``random.Random(seed)`` -- the permutation the reference's ``seed_all(seed); random.shuffle(...)`` gives on a sorted
+    listing (it shuffles the directory's own order) -- and sliced ``[examples_start : examples_start +
+    number_of_examples]`` with the reference's ``None`` rules: the labeled scenes are the first ``labeled_dataset_size``
+    of the permutation, the unlabeled ones those behind them.  ``__getitem__`` / ``examples()`` as
+    ``PreprocessedCrowdDataset``."""
+
+    def __init__(self, database_directory, dataset='train', seed=None, number_of_examples=None,
+                 map_directory_name='maps', examples_start=None):
+        import os
+        import random
+        if examples_start is None:
+            examples_end = number_of_examples
+        elif number_of_examples is None:
+            examples_end = None
+        else:
+            examples_end = examples_start + number_of_examples
+        self.dataset_directory = os.path.join(database_directory, dataset.capitalize())
+        names = sorted(name for name in os.listdir(os.path.join(self.dataset_directory, 'labels')) if name.endswith('.npy'))
+        random.Random(seed).shuffle(names)
+        self.file_names = names[examples_start:examples_end]
+        self.length = len(self.file_names)
+        self.map_directory_name = map_directory_name
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, index):
+        import os
+        file_name = self.file_names[index]
+        return tuple(np.load(os.path.join(self.dataset_directory, directory, file_name))
+                     for directory in ('images', 'labels', self.map_directory_name))
+
+    def examples(self):
+        return [CrowdExample(image=image, label=label, map_=map_) for image, label, map_ in
+                (self[index] for index in range(self.length))]
+
+
+def draw_example(generator, length, start_indexes, shapes, patch_size, flip):
+    """One ``(scene index, y, x, flip)`` from ``generator`` (a ``np.random.RandomState``): a uniform draw over all
+    ``length`` valid patch centres of the scenes (reference crowd/shanghai_tech_data.py:83-98) and, with ``flip``, a fair
+    coin (crowd/data.py:104; no coin is drawn without).  The one rule of ``DeviceCrowdPatchLoader.draw_positions`` and of
+    ``ResidentCrowdEvaluationSet``'s fixed list."""
+    half = patch_size // 2
+    index = int(generator.randint(length))
+    scene = int(np.searchsorted(start_indexes, index, side='right') - 1)
+    height, width = shapes[scene]
+    columns = width - 2 * half + 1
+    y_index, x_index = divmod(index - start_indexes[scene], columns)
+    return scene, half + y_index, half + x_index, int(flip and generator.randint(2))
+
+
+def evaluation_batch_count(batch_size):
+    """Batches one evaluation epoch walks: the smallest ``n`` with ``(n - 1) * batch_size >= 100`` -- the reference's
+    ``if index * batch_size >= 100: break`` behind batch ``index`` (crowd/srgan.py:176)."""
+    return -(-100 // batch_size) + 1
+
+
 class DeviceCrowdPatchLoader:
     """Endless training batches cut ON THE DEVICE from full crowd scenes that stay resident in HBM:
     the reference's ``ShanghaiTechTransformedDataset`` + ``DataLoader(num_workers=4)`` pipeline (random position
@@ -140,15 +211,8 @@ class DeviceCrowdPatchLoader:
     def draw_positions(self):
         """(scene index, y, x, flip) of one batch: a uniform draw over all valid centres (reference
         crowd/shanghai_tech_data.py:83-98) and a fair coin per example (crowd/data.py:104)."""
-        half = self.patch_size // 2
-        draws = []
-        for _ in range(self.batch_size):
-            index = int(self.generator.randint(self.length))
-            scene = int(np.searchsorted(self.start_indexes, index, side='right') - 1)
-            height, width = self.shapes[scene]
-            columns = width - 2 * half + 1
-            y_index, x_index = divmod(index - self.start_indexes[scene], columns)
-            draws.append((scene, half + y_index, half + x_index, int(self.flip and self.generator.randint(2))))
+        draws = [draw_example(self.generator, self.length, self.start_indexes, self.shapes, self.patch_size, self.flip)
+                 for _ in range(self.batch_size)]
         if self.dp is not None:
             local = self.batch_size // self.dp.world_size
             draws = draws[self.dp.rank * local:(self.dp.rank + 1) * local]
@@ -176,6 +240,45 @@ class DeviceCrowdPatchLoader:
     def __iter__(self):
         while True:
             yield self.batch_for(self.draw_positions())
+
+
+class ResidentCrowdEvaluationSet:
+    """The fixed patches one evaluation epoch walks, cut ON THE DEVICE from resident scenes: the stand-in for the reference's
+    ``...TransformedDataset`` as ``evaluation_epoch`` and the map comparisons use it (crowd/srgan.py:51,69,149-191).  The
+    reference draws fresh random patches at every evaluation; here the ``evaluation_batch_count(batch_size) * batch_size``
+    draws ``(scene, y, x, flip)`` are made ONCE, at construction, from a private ``np.random.RandomState(seed)`` with
+    ``draw_example`` -- the loader's per-example rule -- so that successive summary steps score the same patches and no
+    stream that training uses moves.
+
+    ``source``: a ``DeviceCrowdPatchLoader`` whose resident scenes are shared (the train set: no second upload; its
+    generator is not touched) or a list of ``CrowdExample``s that are uploaded here (the test split).  Nothing but the
+    scenes and the draw list is kept between evaluations: every batch is one ``srgan_crowd_extract_patches`` launch."""
+
+    def __init__(self, source, batch_size, image_patch_size=224, seed=0, flip=False, device=None):
+        if isinstance(source, DeviceCrowdPatchLoader):
+            if source.patch_size != image_patch_size:
+                raise ValueError('the evaluation set shares the scenes of a loader with another patch size')
+            self.scenes = source
+        else:       # a loader of its own is the upload; one device, and its generator is never drawn from
+            self.scenes = DeviceCrowdPatchLoader(source, batch_size, image_patch_size, seed=seed, device=device, flip=flip)
+        self.batch_size, self.patch_size, self.flip, self.seed = batch_size, image_patch_size, flip, seed
+        generator = np.random.RandomState(seed)
+        scenes = self.scenes
+        self.draws = [draw_example(generator, scenes.length, scenes.start_indexes, scenes.shapes, image_patch_size, flip)
+                      for _ in range(evaluation_batch_count(batch_size) * batch_size)]
+
+    def __len__(self):
+        return len(self.draws)
+
+    def device_batches(self):
+        """``(image f32[B, 3, P, P], label f32[B, P, P], map f32[B, P, P])`` device batches, in list order."""
+        for start in range(0, len(self.draws), self.batch_size):
+            yield self.scenes.batch_for(self.draws[start:start + self.batch_size])
+
+    def __getitem__(self, index):
+        """Example ``index`` of the list as device tensors ``(image[3, P, P], label[P, P], map[P, P])``."""
+        image, label, map_ = self.scenes.batch_for([self.draws[index]])
+        return image[0], label[0], map_[0]
 
 
 class DeviceSlidingWindows:

@@ -9,7 +9,7 @@ from .. import functional as F
 from .. import image_summaries
 from ..srgan import Experiment, as_var
 from ..tape import no_grad
-from .data import CrowdExample, DeviceSlidingWindows, ImageSlidingWindowDataset
+from .data import CrowdDataset, CrowdExample, DeviceSlidingWindows, ImageSlidingWindowDataset
 from .models import DCGenerator, KnnDenseNetCat
 from ..synthetic import SyntheticLoader
 
@@ -24,11 +24,23 @@ class CrowdExperiment(Experiment):
         contract (crowd/shanghai_tech_data.py:99-104): image f32[3,S,S] in [-1,1], label f32[S,S], map f32[S,S].
         With ``SRGAN_CROWD_DATABASE`` pointing at a database preprocessed by the reference: the
         ShanghaiTech branch of reference crowd/srgan.py:54-69 -- labeled / unlabeled scenes resident in HBM and cut into
-        random patches on the device, the test split behind ``dataset_class`` for the full-image summaries."""
+        random patches on the device, the test split behind ``dataset_class`` for the full-image summaries; with
+        ``settings.crowd_dataset`` ``'UCF QNRF'`` the UCF-QNRF branch (``ucf_qnrf_dataset_setup``).  With
+        ``settings.crowd_validation = 'device'`` (``getattr``, default unset; needs the database) the evaluation sets of
+        ``validation_summaries`` are attached as well (``attach_evaluation_sets``)."""
         import os
         settings = self.settings
         size = settings.image_patch_size
         directory = os.environ.get(self.DATABASE_ENV)
+        validation = getattr(settings, 'crowd_validation', None)
+        if validation is not None and validation != 'device':
+            raise ValueError("settings.crowd_validation is unset or 'device', not {!r}".format(validation))
+        if validation is not None and not directory:
+            raise ValueError('settings.crowd_validation cuts its evaluation sets from a resident database: it needs {} '
+                             '(the synthetic batches have no scenes)'.format(self.DATABASE_ENV))
+        if directory and settings.crowd_dataset in (CrowdDataset.ucf_qnrf, CrowdDataset.ucf_qnrf.value):
+            self.ucf_qnrf_dataset_setup(directory)
+            return
         if directory:
             from .data import DeviceCrowdPatchLoader, PreprocessedCrowdDataset
             part = os.environ.get(self.DATABASE_ENV + '_PART') or None
@@ -43,10 +55,53 @@ class CrowdExperiment(Experiment):
                                                                    settings.batch_size, size, seed=100, dp=self.dp)
             self.dataset_class = lambda dataset, map_directory_name: PreprocessedCrowdDataset(
                 directory, dataset, part, map_directory_name=map_directory_name)
+            self.attach_evaluation_sets(lambda count: PreprocessedCrowdDataset(
+                directory, 'test', part, number_of_examples=count, map_directory_name=maps).examples())
             return
         self.train_dataset_loader = SyntheticLoader.crowd(settings.batch_size, size, seed=settings.labeled_dataset_seed,
                                                           dp=self.dp)
         self.unlabeled_dataset_loader = SyntheticLoader.crowd(settings.batch_size, size, seed=100, dp=self.dp)
+
+    def ucf_qnrf_dataset_setup(self, directory):
+        """The UCF-QNRF branch of reference crowd/srgan.py:34-52 (``settings.crowd_dataset`` ``CrowdDataset.ucf_qnrf`` or
+        ``'UCF QNRF'``): ``<directory>/<Train|Test>/...``, one seeded permutation of the training scenes of which the
+        labeled loader keeps the first ``labeled_dataset_size`` and the unlabeled loader the ``unlabeled_dataset_size``
+        behind them.  (The full-image walk behind ``dataset_class`` reads the test split in a fixed order -- the
+        reference's is unseeded; the totals do not depend on it.)"""
+        from .data import DeviceCrowdPatchLoader, UcfQnrfCrowdDataset
+        settings = self.settings
+        size, maps = settings.image_patch_size, settings.map_directory_name
+
+        def scenes(count, start=None):
+            return UcfQnrfCrowdDataset(directory, 'train', seed=settings.labeled_dataset_seed, number_of_examples=count,
+                                       map_directory_name=maps, examples_start=start).examples()
+        self.train_dataset_loader = DeviceCrowdPatchLoader(scenes(settings.labeled_dataset_size), settings.batch_size, size,
+                                                           seed=settings.labeled_dataset_seed, dp=self.dp)
+        self.unlabeled_dataset_loader = DeviceCrowdPatchLoader(
+            scenes(settings.unlabeled_dataset_size, settings.labeled_dataset_size), settings.batch_size, size, seed=100,
+            dp=self.dp)
+        self.dataset_class = lambda dataset, map_directory_name: UcfQnrfCrowdDataset(
+            directory, dataset, seed=0, map_directory_name=map_directory_name)
+        self.attach_evaluation_sets(lambda count: UcfQnrfCrowdDataset(
+            directory, 'test', seed=101, number_of_examples=count, map_directory_name=maps).examples())
+
+    def attach_evaluation_sets(self, validation_scenes):
+        """With ``settings.crowd_validation = 'device'`` (read with ``getattr``; unset: nothing happens here): the
+        ``train_dataset`` / ``validation_dataset`` that ``validation_summaries`` evaluates, as fixed patch lists cut on the
+        device -- the train set over the labeled loader's resident scenes (seed ``labeled_dataset_seed``, flips), the
+        validation set over the test split (seed 101, no flips; reference crowd/srgan.py:36-38,51,55-57,69), of which
+        ``settings.crowd_validation_scenes`` (``getattr``, default all) scenes are uploaded.  Under data parallelism only
+        the rank that writes the trial's event files holds and evaluates them (the rule of ``image_summaries_on``)."""
+        settings = self.settings
+        if getattr(settings, 'crowd_validation', None) != 'device' or (self.dp is not None and self.dp.rank != 0):
+            return
+        from .data import ResidentCrowdEvaluationSet
+        size = settings.image_patch_size
+        self.train_dataset = ResidentCrowdEvaluationSet(self.train_dataset_loader, settings.batch_size, size,
+                                                        seed=settings.labeled_dataset_seed, flip=True)
+        self.validation_dataset = ResidentCrowdEvaluationSet(
+            validation_scenes(getattr(settings, 'crowd_validation_scenes', None)), settings.batch_size, size, seed=101,
+            flip=False, device=self.train_dataset_loader.device)
 
     def model_setup(self):
         """reference crowd/srgan.py:92-96 (``pretrained=True`` there downloads torchvision weights; offline the
@@ -113,7 +168,10 @@ class CrowdExperiment(Experiment):
                          shuffle=True):
         """Count ME / MAE / MSE and kNN-map MAE / MSE of ``network`` over batches of ``dataset`` (reference
         crowd/srgan.py:149-191), stopping once more than 100 examples have been seen.  As in the reference, the map
-        errors cover the FIRST batch only (its concatenation of the maps sits inside the "still empty" branch)."""
+        errors cover the FIRST batch only (its concatenation of the maps sits inside the "still empty" branch).  A dataset
+        that offers ``device_batches`` (``ResidentCrowdEvaluationSet``) is evaluated by ``evaluation_epoch_device``."""
+        if hasattr(dataset, 'device_batches'):
+            return self.evaluation_epoch_device(network, dataset, summary_writer, summary_name, comparison_value)
         self.join_dnn_stream()
         order = np.random.permutation(len(dataset)) if shuffle else np.arange(len(dataset))
         predicted_counts, label_counts = [], []
@@ -139,6 +197,54 @@ class CrowdExperiment(Experiment):
         summary_writer.add_scalar('{}/kNN MAE'.format(summary_name), np.abs(predicted_maps - maps).mean())
         summary_writer.add_scalar('{}/MSE'.format(summary_name), (np.abs(predicted_counts - label_counts) ** 2).mean())
         summary_writer.add_scalar('{}/kNN MSE'.format(summary_name), (np.abs(predicted_maps - maps) ** 2).mean())
+        if comparison_value is not None:
+            summary_writer.add_scalar('{}/Ratio MAE GAN DNN'.format(summary_name), count_mae / comparison_value)
+        return count_mae
+
+    def evaluation_epoch_device(self, network, dataset, summary_writer, summary_name, comparison_value=None):
+        """``evaluation_epoch`` over the device batches of ``dataset`` with nothing but 64 bytes going back to the host:
+        per batch the forward pass and one ``srgan_crowd_evaluation_sums`` call into eight doubles on the device (the maps
+        are passed for the first batch only, as the reference accumulates them), one download at the end.  The same six
+        scalars under the same tags in the same order; returns the count MAE.  The dataset fixes the number of batches
+        (``evaluation_batch_count``: the reference's 100-example rule)."""
+        from .. import _lib
+        self.join_dnn_stream()
+        lib = _lib.library()
+        sums = scratch = None
+        for index, (images, labels, maps) in enumerate(dataset.device_batches()):
+            with no_grad():
+                _, predicted_counts, predicted_maps = self.images_to_predicted_labels(network, as_var(images))
+            predicted_counts = predicted_counts.data.float().reshape(-1).contiguous()
+            labels = labels.float().contiguous()
+            batch, plane = labels.shape[0], labels.shape[1] * labels.shape[2]
+            if predicted_counts.shape[0] != batch:
+                raise ValueError('one predicted count per example is evaluated')
+            channels = 0
+            if index == 0:
+                predicted_maps, maps = predicted_maps.data.float().contiguous(), maps.float().contiguous()
+                channels = predicted_maps.shape[1]
+                if tuple(predicted_maps.shape) != (batch, channels) + tuple(maps.shape[1:]) or maps.shape != labels.shape:
+                    raise ValueError('predicted maps {} do not match the maps {}'.format(tuple(predicted_maps.shape),
+                                                                                         tuple(maps.shape)))
+                sums = torch.zeros(8, dtype=torch.float64, device=labels.device)
+            needed = lib.srgan_crowd_evaluation_scratch_bytes(batch, channels, plane)
+            if needed < 0:
+                _lib.check(int(needed), 'srgan_crowd_evaluation_scratch_bytes')
+            if scratch is None or scratch.numel() * 8 < needed:
+                scratch = torch.empty((needed + 7) // 8, dtype=torch.float64, device=labels.device)
+            _lib.check(lib.srgan_crowd_evaluation_sums(
+                predicted_counts.data_ptr(), labels.data_ptr(), predicted_maps.data_ptr() if index == 0 else None,
+                maps.data_ptr() if index == 0 else None, batch, channels, plane, sums.data_ptr(), scratch.data_ptr(),
+                _lib.stream_handle()), 'srgan_crowd_evaluation_sums')
+        if sums is None:
+            raise ValueError('the evaluation set is empty')
+        difference, absolute, square, examples, map_absolute, map_square, map_elements, _ = sums.cpu().numpy()
+        count_mae = absolute / examples
+        summary_writer.add_scalar('{}/ME'.format(summary_name), difference / examples)
+        summary_writer.add_scalar('{}/MAE'.format(summary_name), count_mae)
+        summary_writer.add_scalar('{}/kNN MAE'.format(summary_name), map_absolute / map_elements)
+        summary_writer.add_scalar('{}/MSE'.format(summary_name), square / examples)
+        summary_writer.add_scalar('{}/kNN MSE'.format(summary_name), map_square / map_elements)
         if comparison_value is not None:
             summary_writer.add_scalar('{}/Ratio MAE GAN DNN'.format(summary_name), count_mae / comparison_value)
         return count_mae
