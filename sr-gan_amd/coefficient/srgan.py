@@ -1,7 +1,7 @@
 """Coefficient application (surface of reference coefficient/srgan.py:17-101): toy datasets, MLP D / DNN and generator, the
-MAE / MSE summaries and, with ``settings.distribution_summaries`` (read with ``getattr``, default off), the reference's two
-distribution outputs built on the device (``distribution_summaries.py``): the scalar ``Generator/Predicted Label Wasserstein``
-and the ``Distributions`` frame of kernel-density curves -- without the figure's text."""
+MAE / MSE summaries and, with ``settings.distribution_summaries``, the reference's two distribution outputs built on the device
+(``distribution_summaries.py``): the scalar ``Generator/Predicted Label Wasserstein`` and the ``Distributions`` frame of
+kernel-density curves -- without the figure's text."""
 import numpy as np
 import torch
 from scipy.stats import norm
@@ -9,6 +9,7 @@ from torch.utils.data import DataLoader
 
 from .. import distribution_summaries
 from .. import functional as F
+from ..settings import option
 from ..srgan import Experiment, as_var
 from ..tape import no_grad
 from ..utility import MixtureModel, current_device
@@ -79,13 +80,13 @@ class CoefficientExperiment(Experiment):
         values['predicted_labels'] = predicted
         return values
 
-    # ``settings.distribution_summaries`` (read with getattr, default off): the reference's distribution outputs of a summary
-    # step, computed on the device.  Unlike the image summaries this one DOES draw from a host stream -- the reference draws its
-    # z from NumPy's global stream at every summary step, and so does this -- which is one more reason it is off by default:
-    # switching it on moves every later host draw of z_D.  (Under ``settings.device_random_draws`` the training draws do not
-    # come from that stream, and a run trains the same bits with the setting on and off.)
+    # ``settings.distribution_summaries``: the reference's distribution outputs of a summary step, computed on the device.
+    # Unlike the image summaries this one DOES draw from a host stream -- the reference draws its z from NumPy's global stream
+    # at every summary step, and so does this -- which is one more reason it is off by default: switching it on moves every
+    # later host draw of z_D.  (Under ``settings.device_random_draws`` the training draws do not come from that stream, and a
+    # run trains the same bits with the setting on and off.)
     def distribution_summaries_setting(self):
-        return bool(getattr(self.settings, 'distribution_summaries', False))
+        return bool(option(self.settings, 'distribution_summaries'))
 
     def distribution_summaries_on(self):
         """Under data parallelism only the rank that writes the trial's event files launches anything."""

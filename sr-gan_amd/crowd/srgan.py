@@ -7,6 +7,7 @@ import torch
 
 from .. import functional as F
 from .. import image_summaries
+from ..settings import option
 from ..srgan import Experiment, as_var
 from ..tape import no_grad
 from .data import CrowdDataset, CrowdExample, DeviceSlidingWindows, ImageSlidingWindowDataset
@@ -26,13 +27,13 @@ class CrowdExperiment(Experiment):
         ShanghaiTech branch of reference crowd/srgan.py:54-69 -- labeled / unlabeled scenes resident in HBM and cut into
         random patches on the device, the test split behind ``dataset_class`` for the full-image summaries; with
         ``settings.crowd_dataset`` ``'UCF QNRF'`` the UCF-QNRF branch (``ucf_qnrf_dataset_setup``).  With
-        ``settings.crowd_validation = 'device'`` (``getattr``, default unset; needs the database) the evaluation sets of
+        ``settings.crowd_validation = 'device'`` (needs the database) the evaluation sets of
         ``validation_summaries`` are attached as well (``attach_evaluation_sets``)."""
         import os
         settings = self.settings
         size = settings.image_patch_size
         directory = os.environ.get(self.DATABASE_ENV)
-        validation = getattr(settings, 'crowd_validation', None)
+        validation = option(settings, 'crowd_validation')
         if validation is not None and validation != 'device':
             raise ValueError("settings.crowd_validation is unset or 'device', not {!r}".format(validation))
         if validation is not None and not directory:
@@ -86,21 +87,21 @@ class CrowdExperiment(Experiment):
             directory, 'test', seed=101, number_of_examples=count, map_directory_name=maps).examples())
 
     def attach_evaluation_sets(self, validation_scenes):
-        """With ``settings.crowd_validation = 'device'`` (read with ``getattr``; unset: nothing happens here): the
+        """With ``settings.crowd_validation = 'device'`` (unset: nothing happens here): the
         ``train_dataset`` / ``validation_dataset`` that ``validation_summaries`` evaluates, as fixed patch lists cut on the
         device -- the train set over the labeled loader's resident scenes (seed ``labeled_dataset_seed``, flips), the
         validation set over the test split (seed 101, no flips; reference crowd/srgan.py:36-38,51,55-57,69), of which
-        ``settings.crowd_validation_scenes`` (``getattr``, default all) scenes are uploaded.  Under data parallelism only
+        ``settings.crowd_validation_scenes`` (default all) scenes are uploaded.  Under data parallelism only
         the rank that writes the trial's event files holds and evaluates them (the rule of ``image_summaries_on``)."""
         settings = self.settings
-        if getattr(settings, 'crowd_validation', None) != 'device' or (self.dp is not None and self.dp.rank != 0):
+        if option(settings, 'crowd_validation') != 'device' or (self.dp is not None and self.dp.rank != 0):
             return
         from .data import ResidentCrowdEvaluationSet
         size = settings.image_patch_size
         self.train_dataset = ResidentCrowdEvaluationSet(self.train_dataset_loader, settings.batch_size, size,
                                                         seed=settings.labeled_dataset_seed, flip=True)
         self.validation_dataset = ResidentCrowdEvaluationSet(
-            validation_scenes(getattr(settings, 'crowd_validation_scenes', None)), settings.batch_size, size, seed=101,
+            validation_scenes(option(settings, 'crowd_validation_scenes')), settings.batch_size, size, seed=101,
             flip=False, device=self.train_dataset_loader.device)
 
     def model_setup(self):
@@ -304,8 +305,8 @@ class CrowdExperiment(Experiment):
         The reference resizes every predicted density patch to the patch size with ``scipy.misc.imresize`` (removed
         from SciPy); ``KnnDenseNetCat`` already predicts at the patch size, where that resize is the identity, and
         only that case is supported here; ``predict_full_example_device`` (chosen by ``settings.full_image_inference =
-        'device'``, read with ``getattr``; the default is this host path) resizes on the device."""
-        if getattr(self.settings, 'full_image_inference', 'host') == 'device':
+        'device'``; the default is this host path) resizes on the device."""
+        if option(self.settings, 'full_image_inference') == 'device':
             return self.predict_full_example_device(full_example, network)
         settings = self.settings
         patch_size = settings.image_patch_size

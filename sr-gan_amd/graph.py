@@ -41,6 +41,7 @@ import gc
 import torch
 
 from . import functional as F
+from .settings import option
 from .tape import Var
 
 # attributes a training step leaves on the experiment for summaries / tests; after a replay they must again refer to
@@ -89,7 +90,7 @@ class CapturedIteration:
         """Replays run on the current stream, eager iterations in between put the DNN step on its side stream without
         joining it (resident batches): at every switch between the two the streams wait for each other, so that an eager
         DNN step never runs next to a replay's and the other way round."""
-        side = getattr(self.experiment, '_dnn_stream', None)
+        side = self.experiment._dnn_stream
         if side is not None:
             main = torch.cuda.current_stream()
             main.wait_stream(side)
@@ -110,8 +111,8 @@ class CapturedIteration:
         for writer in (e.dnn_summary_writer, e.gan_summary_writer):
             writer.step = step
         summary = e.dnn_summary_writer.is_summary_step() or e.gan_summary_writer.is_summary_step()
-        if summary or self.eager_iterations < int(getattr(settings, 'step_graph_warmup', 2)) or \
-                getattr(settings, 'reference_schedule', False):
+        if summary or self.eager_iterations < int(option(settings, 'step_graph_warmup')) or \
+                option(settings, 'reference_schedule'):
             return self.eager(*inputs, step)
         flat = _flatten(inputs, [])
         generator_phase = step % settings.generator_training_step_period == 0
@@ -135,8 +136,8 @@ class CapturedIteration:
         host = {name: value.reshape(-1) if name == 'alpha' else value for name, value in host.items() if value is not None}
         # (which draws enter through a buffer is baked in too: with device draws, only the injected ones)
         key = (tuple(tuple(v.shape) for v in flat), generator_phase, F.COMPUTE_DTYPE,
-               tuple(o.param_groups[0]['lr'] for o in self.optimizers()), getattr(settings, 'storage_dtype', None),
-               float(getattr(settings, 'loss_scale', 1.0)), tuple(sorted(host)))
+               tuple(o.param_groups[0]['lr'] for o in self.optimizers()), option(settings, 'storage_dtype'),
+               float(option(settings, 'loss_scale')), tuple(sorted(host)))
         record = self.records.get(key)
         if record is not None and record['shadows'] != self.shadow_counts():
             # a weight shadow appeared since this capture (an eager summary step, a new phase): the captured refreshes do not

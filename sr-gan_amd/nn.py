@@ -5,11 +5,13 @@ container / checkpoint format, not a compute path.
 """
 import contextlib
 
+import numpy as np
 import torch
 from torch import nn
 
 from . import functional as F
 from .tape import Var
+from .utility import current_device
 
 
 def parameter_var(parameter):
@@ -158,6 +160,14 @@ class AvgPool2d(nn.Module):
         return F.avg_pool2d(x, self.kernel_size, self.stride)
 
 
+def draw_state(seed, iteration):
+    """The state of ``srgan_random_fill`` on the device: int32 x 4 holding the words {seed_lo, seed_hi, iteration, 0} of a
+    64-bit seed and a 32-bit iteration count (both taken modulo their width)."""
+    seed = int(seed) & (2 ** 64 - 1)
+    words = np.array([seed & 0xffffffff, seed >> 32, int(iteration) & 0xffffffff, 0], dtype=np.uint32)
+    return torch.from_numpy(words.view(np.int32)).to(current_device())
+
+
 class DropoutStream:
     """Which mask a dropout call of one network gets.  Two parts: a device state ``uint32[4] = {seed_lo, seed_hi,
     iteration, 0}`` (the state of ``srgan_random_fill``, created at first use) and a host-side call counter.  A
@@ -182,10 +192,7 @@ class DropoutStream:
 
     def state(self):
         if self._state is None:
-            import numpy as np
-            from .utility import current_device
-            words = np.array([self.seed & 0xffffffff, self.seed >> 32, self.iteration, 0], dtype=np.uint32)
-            self._state = torch.from_numpy(words.view(np.int32)).to(current_device())
+            self._state = draw_state(self.seed, self.iteration)
         return self._state
 
     def begin_step(self):

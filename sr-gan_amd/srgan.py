@@ -33,7 +33,7 @@ from . import _lib
 from . import functional as F
 from . import nn
 from .optim import Adam
-from .settings import Settings
+from .settings import Settings, option
 from .tape import Var, backward, no_grad
 from . import image_summaries
 from .utility import SummaryWriter, MixtureModel, current_device, make_directory_name_unique, norm_squared, seed_all, \
@@ -158,6 +158,12 @@ class Experiment(ABC):
         self.last_losses = {}          # device scalars of the latest step (no host sync)
         self._draw_state = None        # settings.device_random_draws: device int32 x 4 {seed_lo, seed_hi, iteration, 0}
         self._dropout_streams = {}     # 'D' / 'DNN' -> (network, its nn.DropoutStream or None), made at the first training step
+        self._captured_iteration = None          # settings.step_graph: the graph.CapturedIteration, made at the first iteration
+        self._single_compute_stream = False      # captured under data parallelism: the side streams are off for this run
+        self._graph_note = False                 # why a data-parallel run with step_graph stays eager: said once
+        self._typed_commands = set()             # rank 0: 'save' / 'quit' typed since the ranks last exchanged them
+        self._dnn_stream = self._aux_stream = self._gp_stream = None       # the side streams, each made at first use
+        self._stack_too_large = False            # the stacked discriminator pass passed the kernels' 2^31 elements once
 
     @property
     def parallel(self):
@@ -284,8 +290,8 @@ class Experiment(ABC):
         ``settings.step_graph`` on a single device (fp32 or the 16-bit path; data parallel: fp32 only) the iteration is captured
         once as a HIP graph and replayed
         (``graph.CapturedIteration``); summary steps and the first ``settings.step_graph_warmup`` iterations run eagerly."""
-        if getattr(self.settings, 'step_graph', False) and examples_on_gpu() and self._exchanges_are_capturable():
-            if getattr(self, '_captured_iteration', None) is None:
+        if option(self.settings, 'step_graph') and examples_on_gpu() and self._exchanges_are_capturable():
+            if self._captured_iteration is None:
                 from .graph import CapturedIteration
                 self._captured_iteration = CapturedIteration(self)
             return self._captured_iteration.run(labeled_examples, labels, unlabeled_examples, step)
@@ -295,9 +301,9 @@ class Experiment(ABC):
     def _stream_setting(self, name):
         """A side-stream switch of ``settings`` as THIS iteration sees it: off while the iteration is captured / replayed as a
         HIP graph under data parallelism (``_single_compute_stream``), without touching ``settings`` itself."""
-        if getattr(self, '_single_compute_stream', False):
+        if self._single_compute_stream:
             return False
-        return getattr(self.settings, name, False)
+        return option(self.settings, name)
 
     def _exchanges_are_capturable(self):
         """True when this run's iterations can be captured as HIP graphs.  Single device: always.  Data parallel: fp32 only (settings.storage_dtype
@@ -311,14 +317,14 @@ class Experiment(ABC):
         the compute side streams AND the communication stream)."""
         if not self.parallel:
             return True
-        if getattr(self.settings, 'storage_dtype', None):
-            if not getattr(self, '_graph_note', False):
+        if option(self.settings, 'storage_dtype'):
+            if not self._graph_note:
                 print('[srgan_amd] step_graph with settings.storage_dtype replays on a single device only; running eagerly '
                       'under data parallelism')
                 self._graph_note = True
             return False
-        if getattr(self.settings, 'step_graph_collectives', None) != 'abi':
-            if not getattr(self, '_graph_note', False):
+        if option(self.settings, 'step_graph_collectives') != 'abi':
+            if not self._graph_note:
                 print('[srgan_amd] step_graph under data parallelism needs settings.step_graph_collectives = "abi" '
                       '(the C ABI\'s RCCL entry points); running eagerly')
                 self._graph_note = True
@@ -327,7 +333,7 @@ class Experiment(ABC):
             self.dp.use_abi_collectives()
         if getattr(self.dp, 'abi', None) is None:
             return False
-        if not getattr(self, '_single_compute_stream', False):
+        if not self._single_compute_stream:
             self.join_dnn_stream()                  # an eager iteration may have left work on a side stream
             self._single_compute_stream = True
             print('[srgan_amd] step_graph under data parallelism: one compute stream + RCCL\'s (side streams off for this run)')
@@ -391,10 +397,10 @@ class Experiment(ABC):
             commands = self._poll_stdin()
         else:
             if self.dp.rank == 0:
-                self._typed_commands = getattr(self, '_typed_commands', set()) | self._poll_stdin()
+                self._typed_commands |= self._poll_stdin()
             if step % self.USER_INPUT_EXCHANGE_PERIOD != 0 and step != self.settings.steps_to_run - 1:
                 return
-            commands = self.dp.broadcast_object(sorted(getattr(self, '_typed_commands', set())))
+            commands = self.dp.broadcast_object(sorted(self._typed_commands))
             self._typed_commands = set()
         if 'save' in commands:
             self.save_models(step)
@@ -415,18 +421,18 @@ class Experiment(ABC):
         """The norm-layer arguments of a DCGAN generator, for every ``model_setup`` that builds one:
         ``settings.generator_batch_norm`` (norm layers with batch statistics) and ``settings.blocked_batch_norm`` (such a
         generator stays on the blocked data path that ``settings.storage_dtype`` / ``settings.blocked_fp32`` select; without
-        either of them it changes nothing).  The latter is read with ``getattr`` and defaults to off: with it off the
-        generator with norm layers keeps the fp32 graph, which the 16-bit storage test of the batch-norm step pins."""
-        return dict(batch_norm=getattr(self.settings, 'generator_batch_norm', False),
-                    blocked_batch_norm=getattr(self.settings, 'blocked_batch_norm', False))
+        either of them it changes nothing).  With the latter off the generator with norm layers keeps the fp32 graph, which
+        the 16-bit storage test of the batch-norm step pins."""
+        return dict(batch_norm=self.settings.generator_batch_norm,
+                    blocked_batch_norm=option(self.settings, 'blocked_batch_norm'))
 
     def discriminator_norm_arguments(self):
         """The norm-layer arguments of a DCGAN discriminator (D and DNN), for every ``model_setup`` that builds one:
         ``settings.discriminator_batch_norm`` (frozen norm layers) and ``settings.blocked_frozen_norm`` (such a discriminator
         stays on the blocked data path that ``settings.storage_dtype`` / ``settings.blocked_fp32`` select; without either of
-        them it changes nothing).  The latter is read with ``getattr`` and defaults to off: the fp32 NCHW graph."""
-        return dict(batch_norm=getattr(self.settings, 'discriminator_batch_norm', False),
-                    blocked_frozen_norm=getattr(self.settings, 'blocked_frozen_norm', False))
+        them it changes nothing).  With the latter off: the fp32 NCHW graph."""
+        return dict(batch_norm=self.settings.discriminator_batch_norm,
+                    blocked_frozen_norm=option(self.settings, 'blocked_frozen_norm'))
 
     def gpu_mode(self):
         """Moves each network into its flat parameter / gradient arena on this rank's device."""
@@ -451,7 +457,7 @@ class Experiment(ABC):
 
     def refuse_feature_loss_hooks_under_data_parallelism(self):
         if self.dp is not None and self.dp.world_size > 1 and \
-                any(getattr(self.settings, name, None) is not None for name in FEATURE_LOSS_SETTINGS):
+                any(option(self.settings, name) is not None for name in FEATURE_LOSS_SETTINGS):
             # a hook sees this rank's rows only: the batch means / Gram matrices of a sharded batch need collectives of their own
             raise NotImplementedError('settings.matching_feature_loss / settings.contrasting_feature_loss run on one device '
                                       'only: feature losses over a batch sharded across data-parallel ranks are future work')
@@ -528,22 +534,19 @@ class Experiment(ABC):
         reproducible across devices; here it comes from torch's CPU stream and is copied over."""
         return self._global_draw(batch_size, lambda count: torch.rand(count))
 
-    # ``settings.device_random_draws`` (read with getattr, default off; seed: ``settings.device_random_seed``, default 0): the
-    # three draws come from the counter-based generator of csrc/random_draws.hip instead of the host streams -- kernel
-    # launches on the stream that uses them, nothing staged, and a HIP graph captures them with the step.  Element e of draw d
-    # of iteration t is a pure function of (seed, t, d, e); t lives in a device state that ``gan_training_step`` advances once
-    # per iteration.  The stream is NOT the reference's (host draws stay the default and the only stream pinned against it);
-    # an injected draw still wins.
+    # ``settings.device_random_draws`` (seed: ``settings.device_random_seed``): the three draws come from the counter-based
+    # generator of csrc/random_draws.hip instead of the host streams -- kernel launches on the stream that uses them, nothing
+    # staged, and a HIP graph captures them with the step.  Element e of draw d of iteration t is a pure function of
+    # (seed, t, d, e); t lives in a device state that ``gan_training_step`` advances once per iteration.  The stream is NOT
+    # the reference's (host draws stay the default and the only stream pinned against it); an injected draw still wins.
     def device_random_draws(self):
-        return bool(getattr(self.settings, 'device_random_draws', False))
+        return bool(option(self.settings, 'device_random_draws'))
 
     def device_draw_state(self):
         """The draws' device state, created at first use with ``iteration = starting_step`` (a resumed run continues its
         stream; checkpoints keep the reference's keys, the seed comes from the settings)."""
-        if getattr(self, '_draw_state', None) is None:
-            seed = int(getattr(self.settings, 'device_random_seed', 0)) & (2 ** 64 - 1)
-            words = np.array([seed & 0xffffffff, seed >> 32, int(self.starting_step) & 0xffffffff, 0], dtype=np.uint32)
-            self._draw_state = torch.from_numpy(words.view(np.int32)).to(current_device())
+        if self._draw_state is None:
+            self._draw_state = nn.draw_state(option(self.settings, 'device_random_seed'), self.starting_step)
         return self._draw_state
 
     def _device_draw(self, draw, local_rows, columns, kind, offset=0.0):
@@ -571,25 +574,25 @@ class Experiment(ABC):
             return self._device_draw(DRAW_ALPHA, batch_size, None, 0)
         return as_var((self.draw_interpolation_alpha(batch_size) if alpha is None else alpha).reshape(-1), staged=True)
 
-    # ``settings.drop_rate`` (read with getattr, default 0: no dropout layer exists and none of this runs): dropout on the new
-    # features of every dense layer of D and DNN (reference crowd/models.py:336-353).  The masks come from the counter-based
-    # stream of the device draws and are never stored: a network owns a ``nn.DropoutStream`` -- a device state {seed, iteration}
-    # of its own (seed: ``settings.device_random_seed``; iteration: ``starting_step`` at first use, so a resumed run continues
-    # its masks) and a host-side call counter.  The counter is reset when the network's step of an iteration begins, each
-    # training-mode dropout call takes the next draw id of the network's range, and the state is advanced once per iteration
-    # behind the last launch that reads it (the ordering edges).  The draws' own state is untouched.
+    # ``settings.drop_rate`` (0: no dropout layer exists and none of this runs): dropout on the new features of every dense
+    # layer of D and DNN (reference crowd/models.py:336-353).  The masks come from the counter-based stream of the device
+    # draws and are never stored: a network owns a ``nn.DropoutStream`` -- a device state {seed, iteration} of its own (seed:
+    # ``settings.device_random_seed``; iteration: ``starting_step`` at first use, so a resumed run continues its masks) and a
+    # host-side call counter.  The counter is reset when the network's step of an iteration begins, each training-mode dropout
+    # call takes the next draw id of the network's range, and the state is advanced once per iteration behind the last launch
+    # that reads it (the ordering edges).  The draws' own state is untouched.
     def dense_drop_rate(self):
-        return float(getattr(self.settings, 'drop_rate', 0) or 0)
+        return float(option(self.settings, 'drop_rate') or 0)
 
     def dropout_stream(self, name):
         """The dropout stream of network ``name`` ('D' / 'DNN'), or None when it has no active dropout layer."""
         network = getattr(self, name, None)
-        streams = self.__dict__.setdefault('_dropout_streams', {})
+        streams = self._dropout_streams
         known = streams.get(name)
         if known is None or known[0] is not network:
             stream = None
             if nn.active_dropout_layers(network):
-                stream = nn.DropoutStream(DROPOUT_DRAW_BASES[name], getattr(self.settings, 'device_random_seed', 0),
+                stream = nn.DropoutStream(DROPOUT_DRAW_BASES[name], option(self.settings, 'device_random_seed'),
                                           self.starting_step, DROPOUT_DRAW_RANGE)
                 nn.attach_dropout_stream(network, stream)
             known = streams[name] = (network, stream)
@@ -654,7 +657,7 @@ class Experiment(ABC):
     def _dnn_side_stream(self):
         if not self._stream_setting('overlap_dnn_step') or not examples_on_gpu():
             return None
-        if getattr(self, '_dnn_stream', None) is None:
+        if self._dnn_stream is None:
             self._dnn_stream = torch.cuda.Stream()
         return self._dnn_stream
 
@@ -665,7 +668,7 @@ class Experiment(ABC):
             # communication stream gets the fourth hardware queue of the HIP runtime to itself: a fifth stream aliases onto a
             # queue and couples two chains)
             return None
-        if getattr(self, '_aux_stream', None) is None:
+        if self._aux_stream is None:
             self._aux_stream = torch.cuda.Stream()
         return self._aux_stream
 
@@ -679,7 +682,7 @@ class Experiment(ABC):
         if not self._stream_setting('overlap_gradient_penalty') or not examples_on_gpu() or \
                 getattr(self.D, '_srgan_arena', None) is None:
             return None
-        if getattr(self, '_gp_stream', None) is None:
+        if self._gp_stream is None:
             # (default priority: a high-priority stream for this, the longest chain, is one more hardware queue and lost 18-47 %
             # under graph replay and data parallelism, profiles/r05_stream_priority.txt)
             self._gp_stream = torch.cuda.Stream(priority=0)
@@ -702,8 +705,8 @@ class Experiment(ABC):
 
     def _apply_stream_settings(self):
         """``settings.wgrad_stream`` (None: leave the module attribute as it is) -> ``fused.WGRAD_STREAM``."""
-        wanted = getattr(self.settings, 'wgrad_stream', None)
-        if getattr(self, '_single_compute_stream', False):
+        wanted = option(self.settings, 'wgrad_stream')
+        if self._single_compute_stream:
             wanted = False
         if wanted is not None:
             from . import fused
@@ -713,9 +716,8 @@ class Experiment(ABC):
         return bool(getattr(self.train_dataset_loader, 'resident', False))
 
     def _join_side_stream(self):
-        stream = getattr(self, '_dnn_stream', None)
-        if stream is not None:
-            torch.cuda.current_stream().wait_stream(stream)
+        if self._dnn_stream is not None:
+            torch.cuda.current_stream().wait_stream(self._dnn_stream)
 
     def join_dnn_stream(self):
         """Settle the networks before anything outside the training step reads them: the current stream waits for an
@@ -731,36 +733,36 @@ class Experiment(ABC):
             return None
         # settings.gradient_wire_dtype ('f32' | 'bf16': buckets travel as bf16, the master gradients stay fp32) and
         # settings.gradient_exchange_form ('all_reduce' | 'reduce_scatter'), opt-in per configuration
-        return self.dp.gradient_exchange(module._srgan_arena, wire=getattr(self.settings, 'gradient_wire_dtype', None),
-                                         form=getattr(self.settings, 'gradient_exchange_form', None))
+        return self.dp.gradient_exchange(module._srgan_arena, wire=option(self.settings, 'gradient_wire_dtype'),
+                                         form=option(self.settings, 'gradient_exchange_form'))
 
     # ---- mixed precision (BASELINE.json configs 2 and 5; the reference is fp32-only) --------------------------------
     def precision(self, phase='step'):
         """The MFMA operand type of a phase as a context manager: ``settings.compute_dtype`` ('f32' default, 'bf16',
         'f16') for the step, ``settings.gradient_penalty_dtype`` (default 'f32': "fp16 with fp32 GP") for the
         gradient-penalty chain -- its forward, the recorded inner gradient and the penalty's own backward."""
-        name = getattr(self.settings, 'compute_dtype', 'f32')
+        name = option(self.settings, 'compute_dtype')
         if phase == 'penalty':
-            name = getattr(self.settings, 'gradient_penalty_dtype', 'f32')
+            name = option(self.settings, 'gradient_penalty_dtype')
         # settings.storage_dtype ('bf16' / 'f16' / None): the networks with a 16-bit data path (blocked16) keep activations
         # and gradients in that type while the phase computes in it; a phase in another type (an fp32 penalty chain) does not
-        storage = getattr(self.settings, 'storage_dtype', None)
+        storage = option(self.settings, 'storage_dtype')
         if storage and F.COMPUTE_DTYPES[storage] == F.COMPUTE_DTYPES[name]:
             return _Contexts(F.compute_dtype(name), F.storage_dtype(storage))
         # settings.blocked_fp32: a phase that computes in fp32 runs the DCGAN stacks' 4x4 / stride 2 stages on fp32 tensors in
         # the blocked layout (exact arithmetic on the LDS-DMA kernels of csrc/blocked16_k4s2.hip)
-        if F.COMPUTE_DTYPES[name] == 0 and getattr(self.settings, 'blocked_fp32', False):
+        if F.COMPUTE_DTYPES[name] == 0 and option(self.settings, 'blocked_fp32'):
             return _Contexts(F.compute_dtype(name), F.storage_dtype('f32b'))
         return _Contexts(F.compute_dtype(name), F.storage_dtype(None))
 
     def scaled_backward(self, root, **arguments):
         """``backward(root)`` with the root gradient set to ``settings.loss_scale`` (static loss scaling for the fp16 mode:
         gradients of 1e-6 would otherwise reach the fp16 operands as subnormals); ``apply_update`` divides it out."""
-        scale = float(getattr(self.settings, 'loss_scale', 1.0))
+        scale = float(option(self.settings, 'loss_scale'))
         return backward(root, grad=None if scale == 1.0 else F.full_like(root, scale), **arguments)
 
     def apply_update(self, optimizer):
-        scale = float(getattr(self.settings, 'loss_scale', 1.0))
+        scale = float(option(self.settings, 'loss_scale'))
         if scale != 1.0:
             F._unary_raw(F.U_AFFINE, optimizer.arena.grad, 1.0 / scale, 0.0, out=optimizer.arena.grad)
         optimizer.step()
@@ -772,7 +774,7 @@ class Experiment(ABC):
             self.apply_update(optimizer)
             return
         exchange.finish()
-        if not getattr(self.settings, 'overlap_gradient_exchange', True):
+        if not option(self.settings, 'overlap_gradient_exchange'):
             exchange.wait()
             self.apply_update(optimizer)
             return
@@ -834,7 +836,7 @@ class Experiment(ABC):
         batch_size = unlabeled_examples.shape[0]
         penalty_stream = None
         with self.precision():
-            if getattr(settings, 'reference_schedule', False):
+            if option(settings, 'reference_schedule'):
                 labeled_loss = self.labeled_loss_calculation(labeled_examples, labels)
                 self.scaled_backward(labeled_loss)
                 unlabeled_loss = self.unlabeled_loss_calculation(labeled_examples, unlabeled_examples)
@@ -957,7 +959,7 @@ class Experiment(ABC):
         three over B triples the work per kernel launch, which is what the 16x16 / 32x32 dense blocks lack."""
         settings = self.settings
         sizes = (labeled_examples.shape[0], unlabeled_examples.shape[0], fake_examples.shape[0])
-        stackable = getattr(settings, 'batched_discriminator', True) and not getattr(self, '_stack_too_large', False) and \
+        stackable = option(settings, 'batched_discriminator') and not self._stack_too_large and \
             tuple(labeled_examples.shape[1:]) == tuple(unlabeled_examples.shape[1:]) == tuple(fake_examples.shape[1:])
         if stackable:
             # Stacking triples the batch of every activation; one of them may then pass the 2^31-element limit of the
@@ -1145,16 +1147,16 @@ class Experiment(ABC):
         self.regression_evaluation_epoch(self.D, validation, self.gan_summary_writer, '1 Validation Error',
                                          comparison_value=dnn_mae, normalized=normalized)
 
-    # ``settings.image_summaries`` (read with getattr, default off): the pictures the reference writes at every summary step --
-    # grids of training images and of G's samples, the crowd map comparison -- built on the device (``image_summaries.py``)
-    # and downloaded once each by ``SummaryWriter.add_image``.  Nothing here draws from a host stream or advances a loader's
-    # schedule, so a run trains the same bits with the setting on and off.
+    # ``settings.image_summaries``: the pictures the reference writes at every summary step -- grids of training images and
+    # of G's samples, the crowd map comparison -- built on the device (``image_summaries.py``) and downloaded once each by
+    # ``SummaryWriter.add_image``.  Nothing here draws from a host stream or advances a loader's schedule, so a run trains the
+    # same bits with the setting on and off.
     SUMMARY_DRAW_STANDARD, SUMMARY_DRAW_OFFSET = 8, 9      # draw ids of the two summary z (the training draws are 0, 1, 2)
 
     def image_summaries_on(self):
         """Under data parallelism only the rank that writes the trial's event files launches anything (no collective is
         involved: G in eval mode and the two image kernels are local)."""
-        return bool(getattr(self.settings, 'image_summaries', False)) and (self.dp is None or self.dp.rank == 0)
+        return bool(option(self.settings, 'image_summaries')) and (self.dp is None or self.dp.rank == 0)
 
     def real_image_summary(self, examples, range):
         """``Real`` on the GAN writer: the first ``min(9, B)`` of ``examples`` in a grid three wide (reference
@@ -1186,9 +1188,7 @@ class Experiment(ABC):
 
     def summary_draw_state(self, step):
         """Device int32 x 4 {seed_lo, seed_hi, step, 0} for the summary draws of ``step`` (``srgan_random_fill``'s state)."""
-        seed = int(getattr(self.settings, 'device_random_seed', 0)) & (2 ** 64 - 1)
-        words = np.array([seed & 0xffffffff, seed >> 32, int(step) & 0xffffffff, 0], dtype=np.uint32)
-        return torch.from_numpy(words.view(np.int32)).to(current_device())
+        return nn.draw_state(option(self.settings, 'device_random_seed'), step)
 
     def regression_image_summaries(self):
         """The image grids of the age and driving applications (reference age/srgan.py:73-90, driving/srgan.py:68-85): images
@@ -1213,18 +1213,17 @@ class Experiment(ABC):
     def feature_distance_loss(self, base_features, other_features, distance_function=None):
         """distance(mean_b(base) - mean_b(other)) (reference srgan.py:438-449).
 
-        ``settings.matching_feature_loss`` / ``settings.contrasting_feature_loss`` (read with ``getattr``, default None: not
-        part of ``Settings``) replace it: each is a callable ``(base_features, other_features) -> scalar Var``, e.g.
-        ``feature_covariance_loss`` or ``feature_angle_loss`` below.  A call without ``distance_function`` (the unlabeled
-        loss and the generator loss) uses the matching one, the call that passes ``settings.contrasting_distance_function``
-        (the fake loss) the contrasting one.  A hook gets the features as the discriminator left them and decides about
-        means and norms itself: ``settings.normalize_feature_norm`` is ignored.  One device only (``gpu_mode`` refuses them
-        under data parallelism)."""
+        ``settings.matching_feature_loss`` / ``settings.contrasting_feature_loss`` replace it: each is a callable
+        ``(base_features, other_features) -> scalar Var``, e.g. ``feature_covariance_loss`` or ``feature_angle_loss`` below.
+        A call without ``distance_function`` (the unlabeled loss and the generator loss) uses the matching one, the call that
+        passes ``settings.contrasting_distance_function`` (the fake loss) the contrasting one.  A hook gets the features as
+        the discriminator left them and decides about means and norms itself: ``settings.normalize_feature_norm`` is
+        ignored.  One device only (``gpu_mode`` refuses them under data parallelism)."""
         hook = None
         if distance_function is None:
-            hook = getattr(self.settings, 'matching_feature_loss', None)
+            hook = option(self.settings, 'matching_feature_loss')
         elif distance_function is self.settings.contrasting_distance_function:
-            hook = getattr(self.settings, 'contrasting_feature_loss', None)
+            hook = option(self.settings, 'contrasting_feature_loss')
         if hook is not None:
             return hook(base_features, other_features)
         if distance_function is None:
