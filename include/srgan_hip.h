@@ -86,6 +86,8 @@ const char* srgan_last_error(void);
                                                 in_range) */
 #define SRGAN_FEATURE_CROWD_EVALUATION 0x10000u /* ABI 1.1, additive: srgan_crowd_evaluation_sums / _scratch_bytes (the sums
                                                    behind the crowd evaluation scalars, from batches resident on the device) */
+#define SRGAN_FEATURE_SUMMARY_HISTOGRAM 0x20000u /* ABI 1.1, additive: srgan_tensor_histogram (the histogram record of a device
+                                                    tensor: moments, edges and counts of its finite elements) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -664,6 +666,27 @@ int srgan_curve_frame(const float* vertices, const int32_t* offsets, int32_t C, 
                       int32_t H, int32_t W, float x_lo, float x_hi, float y_lo, float y_hi, const float* background,
                       const float* grid_colour, const float* x_ticks, int32_t n_x, const float* y_ticks, int32_t n_y, float* out,
                       void* stream);
+
+/* ---- histogram summaries on the device (SRGAN_FEATURE_SUMMARY_HISTOGRAM) -------------------------------------------------------
+ * srgan_tensor_histogram: the record a summary writer logs for a tensor (the reference wrapper's add_histogram, utility.py:35-39),
+ * of x [n] fp32 on the device, into out = device double[5 + (bins + 1) + bins]:
+ *   out[0..4] = {min, max, sum, sum_squares, finite_count}     out[5 .. 5 + bins] = edges     out[6 + bins ..] = counts
+ * Only FINITE elements count: NaN and +-inf are left out, and n - finite_count tells how many there were.  min and max are over
+ * the finite elements, a zero minimum or maximum (of either sign) is reported as +0.0; sum and sum_squares are fp64 sums of the
+ * fp32 values (each square formed in fp64, where it is exact), started from +0.0.  Edges, in fp64 without FMA contraction:
+ * lo = min, hi = max, or lo = min - 0.5, hi = max + 0.5 when min == max (NumPy's rule); edge_i = lo + i * ((hi - lo) / bins) for
+ * i < bins and edge_bins = hi exactly.  Element x belongs to the largest i <= bins - 1 with edge_i <= x, so x == hi goes to
+ * bins - 1: np.histogram(x, bins=edges).  The bin is found by an estimate that is then corrected against the stored edges: the
+ * result is the comparison's.  Counts are summed as integers (32-bit per workgroup in LDS, 64-bit across workgroups) and
+ * converted at the end: exact above 2^24.  No finite element (n == 0 included): all of out is +0.0.
+ * Two launches on `stream`: the moments (the workgroups' five fp64 values meet in the stream's workspace in a fixed order, see
+ * srgan_split_is_ordered; no floating-point atomics, two calls give the same bits), then edges and counts.  16-byte loads over
+ * the 16-byte aligned body of x, single floats for the at most 3 + 3 elements around it, with the same results.  A stream
+ * without a registered workspace gets one workgroup per launch: the same record (the sums in another order), slowly.  Not for
+ * use under stream capture.
+ * Before any device work: NULL x with n > 0, NULL out, n < 0, bins outside [1, 1024], x not 4-byte or out not 8-byte aligned:
+ * SRGAN_EINVAL; n above max_tensor_elements: SRGAN_ERANGE. */
+int srgan_tensor_histogram(const float* x, int64_t n, int32_t bins, double* out, void* stream);
 
 /* Offline ikNN label of a crowd scene (reference crowd/database_preprocessor.py:93-101,266-290: generate_knn_map +
  * 1 / (map + epsilon)): out[y, x] = 1 / (mean over the k nearest heads of the Euclidean distance from (y, x), each

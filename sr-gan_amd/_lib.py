@@ -132,6 +132,7 @@ SIGNATURES = {
     'srgan_wasserstein_1d': ([vp, i32, vp, i32, vp, vp], ctypes.c_int),
     'srgan_kde_curves': ([vp, vp, i32, i32, f32, f32, vp, vp, vp, vp], ctypes.c_int),
     'srgan_curve_frame': ([vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp, i32, vp, i32, vp, vp], ctypes.c_int),
+    'srgan_tensor_histogram': ([vp, i64, i32, vp, vp], ctypes.c_int),
     'srgan_bn_conv_tangent_weights_job': ([vp, vp, vp, vp, vp, i64, i32, i32, i32, vp], ctypes.c_int),
     'srgan_bn_conv_tangent_weights_grouped': ([vp, i32, i32, i32, vp, vp, vp], ctypes.c_int),
     'srgan_wgrad_group_plan': ([ctypes.POINTER(ConvDesc), ctypes.POINTER(BnRelu), i64, i64, vp, i64, i32, i64, i64, vp, ctypes.POINTER(i32),

@@ -24,10 +24,11 @@
 // and one row per registered (device, stream) workspace -- launches on one stream are ordered, streams do not share a row --
 // and the last workgroup puts its tile's ticket back to zero.
 //
-// Three device functions walk this protocol, and no kernel walks it by hand:
+// Four device functions walk this protocol, and no kernel walks it by hand:
 //   split_finish_ordered   many values per thread per output tile (the accumulators of a contraction split along K)
 //   ordered_row_finish     a few scalars that thread 0 holds (parameter sums, loss sums), the legacy tree of block_sum_256
 //   ordered_lane_finish    V values, thread i holds value i (per-channel sums / moments of a channel group), one barrier
+//   counters_complete_after_adds   integer counters the workgroups add to with atomics: only the ticket, no partials
 #pragma once
 #include <map>
 #include <mutex>
@@ -48,6 +49,22 @@ __device__ __forceinline__ bool last_ticket_after_stores(unsigned int* ticket, i
   if (threadIdx.x == 0) drew_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(parts - 1);
   __syncthreads();
   return drew_last;
+}
+
+// The meeting for INTEGER counters that the workgroups of a launch add to with agent-scope atomics: integer sums do not depend
+// on the order, so there are no partials to keep and re-read, only the question of who is last.  Called by ALL threads of a
+// workgroup straight after their atomic adds, in the RETURNING form with the values consumed (an add has been performed when
+// its value is back, and s_waitcnt vmcnt(0) then covers it).  True in every thread of the workgroup that drew the last of
+// `parts` tickets, the ticket already back at zero: the counters hold the totals, to be read with agent-scope atomic loads.
+// parts == 1: true without a ticket (`ticket` may be NULL).
+__device__ __forceinline__ bool counters_complete_after_adds(unsigned int* ticket, int parts) {
+  if (parts == 1) {
+    __syncthreads();
+    return true;
+  }
+  if (!last_ticket_after_stores(ticket, parts)) return false;
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
 }
 
 // COUNT accumulator floats per thread, THREADS threads per workgroup.  `get(i)` / `set(i, v)` access accumulator i.

@@ -1015,3 +1015,19 @@ def logsumexp_rows(logits):
     s = row_max(logits)
     shifted = sub(logits, row_broadcast(s, logits.shape))
     return add(s, log(row_sum(exp(shifted))))
+
+
+# ------------------------------------------------------------------------------------------- summaries
+def tensor_histogram(tensor, bins=30):
+    """The histogram record of a device tensor (any shape; every element is a sample), ``summary_events``'s dict ``{min, max,
+    sum, sum_squares, finite_count, edges [bins + 1], counts [bins]}`` over its finite elements: one ``srgan_tensor_histogram``
+    call (two launches) where the tensor is, and one download of ``8 * (6 + 2 * bins)`` bytes.  A non-contiguous or non-fp32
+    tensor is made contiguous fp32 first.  Not for use under stream capture: it ends in a download."""
+    from . import summary_events
+    bins = summary_events.check_bins(bins)
+    data = (tensor.data if isinstance(tensor, Var) else tensor).detach()
+    _check_device(data)
+    data = data.float().contiguous().reshape(-1)
+    out = torch.empty(6 + 2 * bins, dtype=torch.float64, device=data.device)
+    _call('srgan_tensor_histogram', data.data_ptr() if data.numel() else None, data.numel(), bins, out.data_ptr(), _stream())
+    return summary_events.histogram_record(out.cpu().numpy(), bins)

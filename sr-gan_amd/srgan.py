@@ -248,6 +248,7 @@ class Experiment(ABC):
             model[network] = getattr(self, network).state_dict()
             model[optimizer] = getattr(self, optimizer).state_dict()
         torch.save(model, os.path.join(self.trial_directory, f'model_{step}.pth'))
+        self.flush_summary_writers()
 
     @staticmethod
     def unpack_labeled(samples):
@@ -268,6 +269,7 @@ class Experiment(ABC):
             with no_grad():
                 self.validation_summaries(step)
             self.train_mode()
+            self.flush_summary_writers()       # a summary step's records are in the event files when the step is over
         self.handle_user_input(step)
         if self.settings.save_step_period and step % self.settings.save_step_period == 0 and step != 0:
             self.save_models(step=step)
@@ -347,6 +349,8 @@ class Experiment(ABC):
             torch.cuda.synchronize()
             abi.close()
             self.dp.abi = None
+        for writer in self.summary_writers():
+            writer.close()
 
     def prepare_optimizers(self):
         """Adam for D (with coupled L2), G and DNN (reference srgan.py:131-138) on the flat arenas."""
@@ -363,6 +367,25 @@ class Experiment(ABC):
         if self.dp is not None and self.dp.rank != 0:
             return None
         return os.path.join(self.trial_directory, name)
+
+    def summary_writers(self):
+        """The writers this experiment has (a DNN-only trial has one)."""
+        return [writer for writer in (self.dnn_summary_writer, self.gan_summary_writer) if writer is not None]
+
+    def flush_summary_writers(self):
+        for writer in self.summary_writers():
+            writer.flush()
+
+    def arena_histogram_summaries(self, bins=30):
+        """Histograms of the flat parameter and gradient arenas, taken on the device: ``Parameters/<D|G|DNN>`` and
+        ``Gradients/<D|G|DNN>``, the DNN's to the DNN writer and the others to the GAN writer.  Called by nothing here: a
+        subclass that wants them calls it from its ``validation_summaries``."""
+        for name, writer in (('DNN', self.dnn_summary_writer), ('D', self.gan_summary_writer), ('G', self.gan_summary_writer)):
+            arena = getattr(getattr(self, name, None), '_srgan_arena', None)
+            if arena is None or writer is None:
+                continue
+            writer.add_histogram(f'Parameters/{name}', arena.data, bins=bins)
+            writer.add_histogram(f'Gradients/{name}', arena.grad, bins=bins)
 
     def prepare_summary_writers(self):
         self.dnn_summary_writer = SummaryWriter(self.summary_directory('DNN'))

@@ -40,9 +40,11 @@ gpu = _LazyDevice()
 
 
 class SummaryWriter:
-    """Scalar and image logger with the reference wrapper's interface (utility.py:21-49): implicit ``step``,
-    ``summary_period``, ``is_summary_step``.  Records in memory (every scalar; the most recent image per tag); forwards to
-    tensorboardX when installed."""
+    """Scalar, image and histogram logger with the reference wrapper's interface (utility.py:21-49): implicit ``step``,
+    ``summary_period``, ``is_summary_step``.  Records in memory (every scalar; the most recent image and histogram record per
+    tag).  With a ``log_dir`` it also writes TensorBoard event files: through tensorboardX when that imports, through this
+    package's own ``summary_events.EventFileWriter`` when it does not.  Without a ``log_dir`` nothing is written and
+    ``flush()`` / ``close()`` do nothing."""
 
     def __init__(self, log_dir=None, comment='', summary_period=1, steps_to_run=-1, **kwargs):
         self.log_dir = log_dir
@@ -51,13 +53,16 @@ class SummaryWriter:
         self.steps_to_run = steps_to_run
         self.scalars = {}
         self.images = {}               # tag -> (step, float32 ndarray [3, H, W]) of the most recent add_image
-        self._backend = None
+        self.histograms = {}           # tag -> (step, histogram record) of the most recent add_histogram
+        self._backend = None           # tensorboardX's writer
+        self._events = None            # summary_events.EventFileWriter
         if log_dir is not None:
             try:
                 from tensorboardX import SummaryWriter as Backend
                 self._backend = Backend(log_dir=log_dir, comment=comment, **kwargs)
             except ImportError:
-                self._backend = None
+                from .summary_events import EventFileWriter
+                self._events = EventFileWriter(log_dir)
 
     def add_scalar(self, tag, scalar_value, global_step=None, **kwargs):
         if global_step is None:
@@ -65,9 +70,34 @@ class SummaryWriter:
         self.scalars.setdefault(tag, []).append((global_step, float(scalar_value)))
         if self._backend is not None:
             self._backend.add_scalar(tag, scalar_value, global_step, **kwargs)
+        elif self._events is not None:
+            self._events.add_scalar(tag, float(scalar_value), global_step)
 
-    def add_histogram(self, *args, **kwargs):
-        pass
+    def add_histogram(self, tag, values, global_step=None, bins=30, **kwargs):
+        """The histogram record of ``values`` (``summary_events``: moments, ``bins`` equal-width buckets between the smallest and
+        the largest finite element, their counts).  A device tensor or ``Var`` goes through ``srgan_tensor_histogram`` where it
+        is, and 8 * (6 + 2 * bins) bytes are downloaded; anything else through ``summary_events.histogram_of_array``.  Takes the
+        reference wrapper's arguments (utility.py:35-39); a string ``bins`` such as its default ``'auto'`` means 30."""
+        from . import summary_events
+        if global_step is None:
+            global_step = self.step
+        bins = summary_events.check_bins(bins)
+        if isinstance(values, Var):
+            values = values.data
+        if isinstance(values, torch.Tensor) and values.is_cuda:
+            record = F.tensor_histogram(values, bins)
+        else:
+            if isinstance(values, torch.Tensor):
+                values = values.detach().float().numpy()
+            record = summary_events.histogram_of_array(values, bins)
+        self.histograms[tag] = (global_step, record)
+        if self._backend is not None:
+            self._backend.add_histogram_raw(tag, min=record['min'], max=record['max'], num=record['finite_count'],
+                                            sum=record['sum'], sum_squares=record['sum_squares'],
+                                            bucket_limits=list(record['edges'][1:]), bucket_counts=list(record['counts']),
+                                            global_step=global_step)
+        elif self._events is not None:
+            self._events.add_histogram(tag, record, global_step)
 
     def add_image(self, tag, img_tensor, global_step=None, **kwargs):
         """``img_tensor``: a ``[3, H, W]`` picture (a device tensor from ``image_summaries``, or anything NumPy reads); it is
@@ -82,6 +112,19 @@ class SummaryWriter:
         self.images[tag] = (global_step, image)
         if self._backend is not None:
             self._backend.add_image(tag, image, global_step, **kwargs)
+        elif self._events is not None:
+            self._events.add_image(tag, image, global_step)
+
+    def flush(self):
+        for sink in (self._backend, self._events):
+            if sink is not None:
+                sink.flush()
+
+    def close(self):
+        """Idempotent; the in-memory records stay readable."""
+        for sink in (self._backend, self._events):
+            if sink is not None:
+                sink.close()
 
     def is_summary_step(self):
         return self.step % self.summary_period == 0 or self.step == self.steps_to_run - 1
