@@ -88,6 +88,8 @@ const char* srgan_last_error(void);
                                                    behind the crowd evaluation scalars, from batches resident on the device) */
 #define SRGAN_FEATURE_SUMMARY_HISTOGRAM 0x20000u /* ABI 1.1, additive: srgan_tensor_histogram (the histogram record of a device
                                                     tensor: moments, edges and counts of its finite elements) */
+#define SRGAN_FEATURE_REGRESSION_EVALUATION 0x40000u /* ABI 1.1, additive: srgan_regression_evaluation_sums (the sums behind
+                                                        the age / driving evaluation scalars, from a batch on the device) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -544,6 +546,27 @@ int srgan_crowd_evaluation_sums(const float* predicted_counts, const float* labe
                                 const float* maps, int32_t B, int32_t M, int64_t HW, double* sums, void* scratch,
                                 void* stream);
 int64_t srgan_crowd_evaluation_scratch_bytes(int32_t B, int32_t M, int64_t HW);
+/* The sums behind the age and driving evaluation scalars (SRGAN_FEATURE_REGRESSION_EVALUATION; reference age/srgan.py:92-107,
+ * driving/srgan.py:87-104: MAE / MSE, NMAE = MAE / label range) of one batch that lives on the device.  predictions: B rows,
+ * row b starting at predictions[b * row_stride] (elements, row_stride >= K); labels [B]; all fp32.  The prediction p_b of a row:
+ *   bins == NULL (then K == 1):  p_b = predictions[b * row_stride]
+ *   bins != NULL (bins [K], K >= 1: the SGAN case, reference age/sgan.py:22-26): the row holds K class logits and
+ *     p_b = bins[j], j the LOWEST index of the row's maximum -- utility.logits_to_bin_values, i.e. torch.max(dim=1)'s first
+ *     maximal index; +0.0 and -0.0 compare equal, +-inf are ordinary values; a row that holds a NaN is outside the contract.
+ * With d_b = (double)p_b - (double)labels[b] the call updates the caller's eight doubles `sums`
+ *   sums[0] += sum_b d_b      sums[1] += sum_b |d_b|      sums[2] += sum_b d_b * d_b      sums[3] += B
+ *   sums[4] = fmin(sums[4], min_b labels[b])              sums[5] = fmax(sums[5], max_b labels[b])
+ * sums[6] and sums[7] are reserved and never touched.  An epoch's record starts as {0, 0, 0, 0, +inf, -inf, 0, 0}.  Every
+ * accumulation is fp64; every square is rounded as a product before it is added (the translation unit is compiled with
+ * `#pragma clang fp contract(off)`): each term is the one NumPy float64 arithmetic forms from the same fp32 inputs, only the
+ * order of the additions differs.  One launch of one workgroup of 256 threads on `stream`, nothing else: thread t takes rows t,
+ * t + 256, ... in that order, the wave's 64 sums meet in a butterfly and the four waves in wave order through LDS.  No atomics,
+ * no scratch, no workspace of the stream: the same inputs give the same bits.
+ * Before any device work: NULL predictions / labels / sums, B < 0, K < 1, K > 1 without bins, row_stride < K, a misaligned
+ * sums: SRGAN_EINVAL; then K > 1024 or B * K > 2^22 (a limit of the one-workgroup design -- an evaluation batch is a few
+ * thousand rows -- not a measured optimum): SRGAN_ERANGE.  B == 0: SRGAN_OK, `sums` untouched. */
+int srgan_regression_evaluation_sums(const float* predictions, int64_t row_stride, int32_t K, const float* bins,
+                                     const float* labels, int32_t B, double* sums, void* stream);
 
 /* Training-batch assembly from a database of equally sized frames resident on the device (SRGAN_FEATURE_IMAGE_BATCHES):
  * the reference's AgeDataset / SteeringAngleDataset items (age/data.py:52-60, driving/data.py:44-51) collated by its

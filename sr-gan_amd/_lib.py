@@ -123,6 +123,7 @@ SIGNATURES = {
     'srgan_crowd_extract_patches': ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_evaluation_sums': ([vp, vp, vp, vp, i32, i32, i64, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_evaluation_scratch_bytes': ([i32, i32, i64], ctypes.c_int64),
+    'srgan_regression_evaluation_sums': ([vp, i64, i32, vp, vp, i32, vp, vp], ctypes.c_int),
     'srgan_image_batch_gather': ([vp, ctypes.c_int, i32, i32, i32, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_extract_windows': ([vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp], ctypes.c_int),
     'srgan_crowd_resize_bilinear': ([vp, i32, i32, i32, i32, vp, vp], ctypes.c_int),

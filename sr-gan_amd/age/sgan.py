@@ -3,6 +3,7 @@
 import torch
 
 from ..sgan import SganExperiment
+from ..utility import logits_to_bin_values
 from .models import Generator, Discriminator
 from .srgan import AgeExperiment
 
@@ -20,3 +21,11 @@ class AgeSganExperiment(SganExperiment, AgeExperiment):
         self.G = Generator(image_size=size, **self.generator_norm_arguments())
         d_norm = self.discriminator_norm_arguments()
         self.D, self.DNN = (Discriminator(image_size=size, number_of_outputs=BIN_LOGITS, **d_norm) for _ in range(2))
+
+    def prediction_rows(self, network, examples):
+        """The class logits and the bin values: the device evaluation takes the first maximal logit's bin on the device."""
+        return self.class_logits(network, examples), self._bins()
+
+    def predicted_labels(self, network, examples):
+        """The bin value of the highest class logit (reference age/sgan.py:22-26, ``images_to_predicted_ages``)."""
+        return logits_to_bin_values(*self.prediction_rows(network, examples))

@@ -9,7 +9,7 @@
 // on data, so two calls on the same inputs give the same bits.  Every accumulation is fp64 and every square is formed as a
 // rounded product BEFORE it is added (no FMA contraction): each term is the one NumPy forms from the same fp32 inputs, only
 // the order of the additions differs.
-#include "common.h"
+#include "evaluation_sums.h"
 
 // hipcc compiles with -ffp-contract=fast, and this ROCm's __dmul_rn / __dadd_rn are a plain `*` / `+` that the compiler fuses
 // like any other: contraction is switched off for every expression of this file instead (the pragma travels with the
@@ -21,28 +21,6 @@ namespace srgan {
 
 constexpr int EVAL_CHUNK = 2048;      // plane elements per workgroup: two 16-byte loads per thread and operand
 constexpr int EVAL_SLOT = 3;          // doubles per workgroup: sum of labels, sum |e|, sum e * e
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int offset = 32; offset > 0; offset >>= 1) v += __shfl_xor(v, offset, 64);
-  return v;
-}
-
-// The workgroup's total of EVAL_SLOT running sums, valid in thread 0: the wave64 butterfly, then the four waves in wave order
-// through LDS.
-__device__ __forceinline__ void block_sums_f64(double (&v)[EVAL_SLOT], double (*scratch)[4]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < EVAL_SLOT; ++k) {
-    v[k] = wave_sum_f64(v[k]);
-    if (lane == 0) scratch[k][wave] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < EVAL_SLOT; ++k) v[k] = ((scratch[k][0] + scratch[k][1]) + scratch[k][2]) + scratch[k][3];
-  }
-}
 
 __device__ __forceinline__ void map_term(float predicted, float map, double& abs_sum, double& square_sum) {
   const double e = (double)predicted - (double)map;

@@ -125,6 +125,10 @@ def device_draw_window(global_rows, columns, world_size=1, rank=0):
 
 class Experiment(ABC):
     """Manages one experimental trial (reference srgan.py:24-469)."""
+    # How the age and driving applications take their validation summaries (``regression_validation_summaries``).  A run sets
+    # them on the instance or in a subclass; any other value is a ValueError when the summaries are first taken.
+    regression_validation = 'host'     # 'device': the summary step's errors from sums taken on the device
+    validation_precision = 'f32'       # 'step': the evaluation's forward passes run under self.precision()
 
     def __init__(self, settings: Settings):
         self.settings = settings
@@ -1134,6 +1138,22 @@ class Experiment(ABC):
         self.load_models(with_optimizers=False)
         self.eval_mode()
 
+    def predicted_labels(self, network, examples):
+        """The labels ``network`` predicts for ``examples``, one per example (the reference's ``images_to_predicted_ages`` /
+        ``images_to_predicted_angles``, age/srgan.py:109-112, driving/srgan.py:106-110).  An application whose networks return
+        something else overrides it (the age SGAN's class logits)."""
+        return network(examples)
+
+    def prediction_rows(self, network, examples):
+        """``(rows, bins)`` for the device evaluation: ``bins`` None and one prediction per row -- ``predicted_labels`` -- or
+        ``[B, K]`` class logits with the ``K`` bin values, of which ``srgan_regression_evaluation_sums`` takes the first
+        maximal one's on the device."""
+        return self.predicted_labels(network, examples), None
+
+    def validation_forward_context(self):
+        """``validation_precision = 'step'``: the evaluation's forward passes run on the data path the run trains on."""
+        return self.precision() if self.validation_precision == 'step' else contextlib.nullcontext()
+
     def regression_evaluation_epoch(self, network, dataset, summary_writer, summary_name, comparison_value=None,
                                     normalized=False):
         """MAE / MSE (and NMAE = MAE / label range with ``normalized``) of ``network`` over ``dataset`` -- any
@@ -1141,9 +1161,9 @@ class Experiment(ABC):
         when given.  Forward passes only (reference age/srgan.py:92-107, driving/srgan.py:87-104)."""
         predictions, labels = [], []
         self.join_dnn_stream()
-        with no_grad():
+        with no_grad(), self.validation_forward_context():
             for examples, batch_labels in dataset:
-                predicted = network(as_var(examples))
+                predicted = self.predicted_labels(network, as_var(examples))
                 predictions.append(predicted.cpu().numpy().reshape(-1).astype(np.float64))
                 labels.append(np.asarray(batch_labels.cpu() if hasattr(batch_labels, 'cpu') else batch_labels,
                                          dtype=np.float64).reshape(-1))
@@ -1157,18 +1177,95 @@ class Experiment(ABC):
             summary_writer.add_scalar('{}/Ratio MAE GAN DNN'.format(summary_name), mae / comparison_value)
         return mae
 
+    def regression_evaluation_epoch_device(self, network, dataset, record):
+        """One evaluation epoch with nothing going back to the host: per batch one forward pass and one
+        ``srgan_regression_evaluation_sums`` call, on the stream the forward ran on, into ``record`` -- eight doubles on the
+        device that start as ``EVALUATION_RECORD``.  Batches of a resident loader (``in_order``) and of ``SyntheticLoader`` are
+        on the device already; a host tensor is uploaded.  No collective: under data parallelism every rank evaluates what it
+        evaluates on the host path."""
+        self.join_dnn_stream()
+        lib = _lib.library()
+        device = record.device
+        with no_grad(), self.validation_forward_context():
+            for examples, batch_labels in dataset:
+                rows, bins = self.prediction_rows(network, as_var(examples))
+                rows = (rows.data if isinstance(rows, Var) else rows).float()
+                rows = rows.reshape(rows.shape[0], -1).contiguous()
+                batch, width = rows.shape
+                labels = torch.as_tensor(batch_labels).to(device, dtype=torch.float32, non_blocking=True)
+                labels = labels.reshape(-1).contiguous()
+                if labels.shape[0] != batch:
+                    raise ValueError('{} labels for {} predicted rows'.format(labels.shape[0], batch))
+                if bins is None:
+                    if width != 1:
+                        raise ValueError('one prediction per example is evaluated, the network gave {}'.format(width))
+                else:
+                    bins = (bins.data if isinstance(bins, Var) else bins).to(device, dtype=torch.float32).reshape(-1).contiguous()
+                    if bins.shape[0] < width:
+                        raise ValueError('{} class logits but {} bins'.format(width, bins.shape[0]))
+                _lib.check(lib.srgan_regression_evaluation_sums(
+                    rows.data_ptr(), width, width, None if bins is None else bins.data_ptr(), labels.data_ptr(), batch,
+                    record.data_ptr(), _lib.stream_handle()), 'srgan_regression_evaluation_sums')
+
+    EVALUATION_RECORD = (0.0, 0.0, 0.0, 0.0, float('inf'), float('-inf'), 0.0, 0.0)      # an epoch's eight doubles before its
+    # first batch: sum d, sum |d|, sum d * d, examples, smallest label, largest label, two reserved (include/srgan_hip.h)
+
+    @staticmethod
+    def download_evaluation_records(records):
+        """The one device-to-host copy of a summary step on the device path: its four 64-byte records."""
+        return records.cpu().numpy()
+
+    @staticmethod
+    def log_regression_record(record, summary_writer, summary_name, comparison_value=None, normalized=False):
+        """The scalars of ``regression_evaluation_epoch`` from an epoch's downloaded record, under the same tags in the same
+        order; returns the MAE."""
+        _, absolute, square, examples, smallest, largest = (float(value) for value in record[:6])
+        if examples == 0:
+            raise ValueError('the evaluation set is empty')
+        mae = absolute / examples
+        summary_writer.add_scalar('{}/MAE'.format(summary_name), mae)
+        if normalized:
+            summary_writer.add_scalar('{}/NMAE'.format(summary_name), mae / (largest - smallest))
+        summary_writer.add_scalar('{}/MSE'.format(summary_name), square / examples)
+        if comparison_value is not None:
+            summary_writer.add_scalar('{}/Ratio MAE GAN DNN'.format(summary_name), mae / comparison_value)
+        return mae
+
     def regression_validation_summaries(self, normalized=False):
         """DNN and D on the train and validation batches, D's validation MAE relative to the DNN's (reference
         age/srgan.py:52-71, driving/srgan.py:48-67; the image grids: ``regression_image_summaries``).  A loader over a database
-        (``in_order``) is walked once in stored order, every example of the split as upstream; any other loader is iterated."""
+        (``in_order``) is walked once in stored order, every example of the split as upstream; any other loader is iterated.
+
+        ``regression_validation = 'device'``: the four epochs leave their sums in four consecutive 64-byte records of one device
+        tensor (``regression_evaluation_epoch_device``), one download of those 256 bytes ends the step, and the scalars are
+        formed from the records -- the same tags in the same order as the host path, the DNN's validation MAE under D's ratio."""
+        if self.regression_validation not in ('host', 'device'):
+            raise ValueError("regression_validation is 'host' or 'device', not {!r}".format(self.regression_validation))
+        if self.validation_precision not in ('f32', 'step'):
+            raise ValueError("validation_precision is 'f32' or 'step', not {!r}".format(self.validation_precision))
         train, validation = (loader.in_order() if hasattr(loader, 'in_order') else loader
                              for loader in (self.train_dataset_loader, self.validation_dataset_loader))
-        self.regression_evaluation_epoch(self.DNN, train, self.dnn_summary_writer, '2 Train Error', normalized=normalized)
-        dnn_mae = self.regression_evaluation_epoch(self.DNN, validation, self.dnn_summary_writer, '1 Validation Error',
-                                                   normalized=normalized)
-        self.regression_evaluation_epoch(self.D, train, self.gan_summary_writer, '2 Train Error', normalized=normalized)
-        self.regression_evaluation_epoch(self.D, validation, self.gan_summary_writer, '1 Validation Error',
-                                         comparison_value=dnn_mae, normalized=normalized)
+        epochs = ((self.DNN, train, self.dnn_summary_writer, '2 Train Error'),
+                  (self.DNN, validation, self.dnn_summary_writer, '1 Validation Error'),
+                  (self.D, train, self.gan_summary_writer, '2 Train Error'),
+                  (self.D, validation, self.gan_summary_writer, '1 Validation Error'))
+        records = None
+        if self.regression_validation == 'device':
+            records = torch.tensor([self.EVALUATION_RECORD] * len(epochs), dtype=torch.float64, device=current_device())
+            for record, (network, dataset, _, _) in zip(records, epochs):
+                self.regression_evaluation_epoch_device(network, dataset, record)
+            records = self.download_evaluation_records(records)
+        dnn_mae = None
+        for index, (network, dataset, summary_writer, summary_name) in enumerate(epochs):
+            comparison_value = dnn_mae if index == 3 else None
+            if records is None:
+                mae = self.regression_evaluation_epoch(network, dataset, summary_writer, summary_name,
+                                                       comparison_value=comparison_value, normalized=normalized)
+            else:
+                mae = self.log_regression_record(records[index], summary_writer, summary_name,
+                                                 comparison_value=comparison_value, normalized=normalized)
+            if index == 1:
+                dnn_mae = mae
 
     # ``settings.image_summaries``: the pictures the reference writes at every summary step -- grids of training images and
     # of G's samples, the crowd map comparison -- built on the device (``image_summaries.py``) and downloaded once each by
