@@ -1,5 +1,5 @@
 """Times the 16-bit 3x3 kernels on VGG-16's shapes (batch 128 and the stacked 384):  python scratch/h_conv_bench.py [fwd|wgrad]
-Environment switches of csrc/blocked16.hip apply (SRGAN_H_DMA_RING, SRGAN_H_CONV_NI)."""
+Environment switches of csrc/blocked16_conv3x3.hip apply (SRGAN_H_DMA_RING, SRGAN_H_CONV_NI)."""
 import os
 import sys
 

@@ -6,39 +6,14 @@
 //                                                                                 ds_read_b128 from an XOR-swizzled LDS image
 //   hlinear_wgrad_kernel  gw[m][k] += sum_n S[n][m] * X[n][k]                      both operands reduced over ROWS: fragments by
 //                                                                                 ds_read_b64_tr_b16 (blocked16.h)
-//   h_pack_matrix_kernel  the 16-bit shadow of a weight matrix, optionally transposed and with the row / column order of a
-//                         flattened blocked plane ([c][p] -> [c / 8][p][c % 8])
+// The 16-bit shadow of a weight matrix, optionally transposed and with the row / column order of a flattened blocked plane
+// ([c][p] -> [c / 8][p][c % 8]: h_plane_index, weight_shadows.h), is written by srgan_h_pack_matrix (blocked16_shadows.hip).
 #include <type_traits>
-#include "blocked16.h"
+#include "weight_shadows.h"
 #include "launchers.h"
 #include "split_finish.h"
 
 namespace srgan {
-
-// out16[r][c] (pitch ld elements, ld % 8 == 0) = src[map(r, row_plane) * rs + map(c, col_plane) * cs] for map(r) < rows_real,
-// map(c) < cols_real, else 0.  One thread per slot of 8 consecutive c (body: h_pack_matrix_slot, blocked16.h).
-template <int PREC>
-__global__ __launch_bounds__(256) void h_pack_matrix_kernel(const float* __restrict__ src, Slot* __restrict__ out, int64_t slots,
-                                                            int32_t row_slots, int64_t rows_real, int64_t cols_real, int64_t rs,
-                                                            int64_t cs, int32_t row_plane, int32_t col_plane) {
-  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (slot >= slots) return;
-  h_pack_matrix_slot<PREC>(src, out, slot, row_slots, rows_real, cols_real, rs, cs, row_plane, col_plane);
-}
-
-// The same for row_stride == 1 (the TRANSPOSED shadow of a row-major matrix: consecutive output rows are consecutive source
-// addresses): a 64 x 64 tile goes through LDS, so both the fp32 reads (along r) and the 16-byte slot stores (along c) are
-// coalesced -- the one-thread-per-slot kernel read eight floats a row pitch apart and fetched every line seven times
-// (4.1 GB per step for VGG-16's two large linear layers, PMC profiles/r06f).  Body: h_pack_matrix_tile (blocked16.h), shared with
-// the batched refresh (h_pack_batched_kernel).
-template <int PREC>
-__global__ __launch_bounds__(256) void h_pack_matrix_transposed_kernel(const float* __restrict__ src, Slot* __restrict__ out,
-                                                                       int64_t rows, int32_t row_slots, int64_t rows_real,
-                                                                       int64_t cols_real, int64_t cs, int32_t row_plane,
-                                                                       int32_t col_plane, int32_t tiles_r) {
-  __shared__ float tile[64][65];
-  h_pack_matrix_tile<PREC>(src, out, tile, (int)blockIdx.x, rows, row_slots, rows_real, cols_real, cs, row_plane, col_plane, tiles_r);
-}
 
 struct HGemmParams {
   const Slot* a; const Slot* b; Slot* out; const float* bias; const Slot* ref;
@@ -296,37 +271,11 @@ __global__ __launch_bounds__(256, 2) void hlinear_wgrad_kernel(const HLinearWgra
   }
 }
 
-static const char* const H16_ONLY = "blocked 16-bit tensors are bf16 (1) or fp16 (2)";
-
 }  // namespace srgan
 
 using namespace srgan;
 
 extern "C" {
-
-// out16[rows][cols] (row pitch = ceil(cols / 8) slots) = src[map(r, row_plane) * row_stride + map(c, col_plane) * col_stride],
-// zero where the mapped index is outside [rows_real) x [cols_real).  map(i, P) = the NCHW-flattened index of element i of a
-// flattened blocked plane tensor with P pixels (P <= 1: identity).
-int srgan_h_pack_matrix(const float* src, void* out, int64_t rows, int64_t cols, int64_t rows_real, int64_t cols_real,
-                        int64_t row_stride, int64_t col_stride, int32_t row_plane, int32_t col_plane, int dtype,
-                        void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_precision<1, 2>(dtype, H16_ONLY)) return status;
-  SRGAN_REQUIRE(src && out && rows > 0 && cols > 0, SRGAN_EINVAL, "srgan_h_pack_matrix arguments");
-  const int64_t row_slots = (cols + 7) / 8, slots = rows * row_slots;
-  SRGAN_REQUIRE(row_slots < ((int64_t)1 << 31), SRGAN_ERANGE, "srgan_h_pack_matrix row length");
-  if (row_stride == 1 && col_stride != 1) {
-    const int tiles_r = (int)((rows + 63) / 64), tiles_c = (int)((row_slots * 8 + 63) / 64);
-    const dim3 tgrid((unsigned)(tiles_r * tiles_c));
-    return launch_for_precision<1, 2>(dtype, [&](auto prec) {
-      hipLaunchKernelGGL(h_pack_matrix_transposed_kernel<decltype(prec)::value>, tgrid, dim3(256), 0, s, src, (Slot*)out, rows, (int32_t)row_slots, rows_real, cols_real, col_stride, row_plane, col_plane, tiles_r);
-    });
-  }
-  const dim3 grid((unsigned)((slots + 255) / 256));
-  return launch_for_precision<1, 2>(dtype, [&](auto prec) {
-    hipLaunchKernelGGL(h_pack_matrix_kernel<decltype(prec)::value>, grid, dim3(256), 0, s, src, (Slot*)out, slots, (int32_t)row_slots, rows_real, cols_real, row_stride, col_stride, row_plane, col_plane);
-  });
-}
 
 // out[N][M'] = epi(B[N][K] * A[M][K]^T [+ bias]) on 16-bit row-major matrices (pitches = ceil(. / 8) slots); M' = out_cols.
 // epi as srgan_h_conv3x3.  The output's columns beyond M (inside its last slot) are written as zeros.

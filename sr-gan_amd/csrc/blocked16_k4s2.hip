@@ -10,35 +10,22 @@
 // with kh(0, a) = 3 - 2a, oy(0) = -1; kh(1, a) = 2 - 2a, oy(1) = 0 ("up": the generator's forward; the data gradient of the
 // strided convolution).  No multiply-accumulate is spent on taps that cannot align.  Both are ONE kernel: a 2x2-tap implicit
 // GEMM in the blocked layout whose halo gather -- stride 2 with the parity offset for "down", stride 1 for "up" -- lives entirely
-// in the per-lane source addresses of an LDS-DMA ring (see hconv3x3_dma_kernel in blocked16.hip, whose structure this shares), and
+// in the per-lane source addresses of an LDS-DMA ring (see hconv3x3_dma_kernel in blocked16_conv3x3.hip, whose structure this shares), and
 // whose stores go to (y * dsy + doy, x * dsx + dox).  A chunk is CK = 4 k-slots (32 reduced channels: one channel group with
 // its four parities for "down", four groups for "up") x 4 taps = 32 MFMAs per wave at a 64 x 256 tile.
 //
 //   hconv2x2_kernel        both directions, epilogues as the 3x3 kernel (bias + leaky, mask by reference)
 //   hwgrad4x4s2_kernel     gw[k][c][4][4] += gy (x) in over pixels: wave = one parity (qy, qx) = four of the sixteen taps,
 //                          transpose-read fragments, partial blocks + ordered finish
-//   h_pack_k4s2_weights    the operand shadows: "down" [chunk = group][tap][parity][rows], "up" [class][chunk][tap][group][rows]
+// The operand shadows -- "down" [chunk = group][tap][parity][rows], "up" [class][chunk][tap][group][rows] -- are written by
+// srgan_h_pack_k4s2_weights (blocked16_shadows.hip; layout and chunk constants: weight_shadows.h).
 #include <type_traits>
 #include <stdlib.h>
-#include "blocked16.h"
+#include "weight_shadows.h"
 #include "launchers.h"
 #include "split_finish.h"
 
 namespace srgan {
-
-// (G = channels per slot: 8, or 4 for the fp32 form)
-// mode 0 ("down"): slot (chunk, tap = 2a + b, j = 2 qy + qx, o) = G reduced channels G chunk .. of w[o][.][2a + qy][2b + qx]
-// mode 1 + 2 ry + rx ("up", one output parity class): slot (chunk, tap, j, o) = 8 reduced channels 8 (4 chunk + j) .. of
-//   w[.][o][kh(ry, a)][kw(rx, b)]
-// element (row o, reduced r, kh, kw) at w[o * row_stride + r * reduced_stride + kh * 4 + kw]
-template <int PREC>
-__global__ __launch_bounds__(256) void h_pack_k4s2_weights_kernel(const float* __restrict__ w, Slot* __restrict__ packed,
-                                                                  int64_t slots, int32_t rows, int32_t reduced, int64_t row_stride,
-                                                                  int64_t reduced_stride, int32_t mode) {
-  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (slot >= slots) return;
-  h_pack_k4s2_weights_slot<PREC>(w, packed, slot, rows, reduced, row_stride, reduced_stride, mode);
-}
 
 struct HConv2Params {
   const Slot* in; const Slot* wp; Slot* out; const float* bias; const Slot* ref;
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void hconv2x2_kernel(const HConv2Params pp,
   const int ty = block % p.tiles_y;
   const int n0 = (block / p.tiles_y) * IMG;
   const int m0 = tm * BM, y0 = ty * ROWS, x0 = tx * TW;
-  // the tile's bias values in LDS, staged here and read in the epilogue (blocked16.hip, hconv3_stage_bias: per value from global
+  // the tile's bias values in LDS, staged here and read in the epilogue (blocked16_conv3x3.hip, hconv3_stage_bias: per value from global
   // memory they were 4 dependent loads per quad of the epilogue)
   __shared__ __attribute__((aligned(16))) float bias_rows[BM];
   const bool with_bias = p.epi == 1 && p.bias != nullptr;
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void hconv2x2_kernel(const HConv2Params pp,
     if (n >= p.N || y >= p.GH || x >= p.GW) continue;
     const int pixel = (y * p.dsy + p.doy) * p.OW + x * p.dsx + p.dox;
     // epi 2: the mask references of this pixel column in ONE batch in front of its stores (loads and stores share the in-order
-    // vmcnt: interleaved, every load waited for the stores in front of it -- blocked16.hip, hconv3_epilogue)
+    // vmcnt: interleaved, every load waited for the stores in front of it -- blocked16_conv3x3.hip, hconv3_epilogue)
     using RefWord = std::conditional_t<PREC == 0, float4, uint2>;
     RefWord refs[MI][4];
     if (p.epi == 2) {
@@ -230,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void hconv2x2_kernel(const HConv2Params pp,
 #pragma unroll
         for (int qp = 0; qp < 2; ++qp) {
           // two register quads = this lane's half (channels 4 lhi .. 4 lhi + 3) of the slots of groups g0 and g0 + 1; the halves
-          // change places between the half-waves (v_permlane32_swap, blocked16.hip hconv3_epilogue) and every lane stores a whole slot
+          // change places between the half-waves (v_permlane32_swap, blocked16_conv3x3.hip hconv3_epilogue) and every lane stores a whole slot
           const int g0 = (m0 + mi * 32) / 8 + 2 * qp;
           uint2 packed[2];
 #pragma unroll
@@ -666,37 +653,11 @@ static void hwgrad4_launch(const HWgrad4Params& p, dim3 grid, hipStream_t stream
   else hipLaunchKernelGGL((hwgrad4x4s2_kernel<TW, ROWS, PREC>), grid, dim3(256), 0, stream, p);
 }
 
-static const char* const H_ANY = "blocked tensors are fp32 (0: four channels per slot), bf16 (1) or fp16 (2)";
-
 }  // namespace srgan
 
 using namespace srgan;
 
 extern "C" {
-
-// 16-byte slots of one operand of a [A][B][4][4] weight tensor: direction 0 "down" (rows = A: the strided convolution's forward /
-// a transposed convolution's data gradient), 1 "up" (rows = B, all four output parity classes, class-major).
-int64_t srgan_h_k4s2_weight_slots(int32_t A, int32_t B, int direction, int dtype) {
-  if (direction == 0) return (int64_t)channel_groups(B, dtype) * K4_TAPS * K4_CK * A;
-  return (int64_t)4 * ((channel_groups(A, dtype) + K4_CK - 1) / K4_CK) * K4_TAPS * K4_CK * B;
-}
-
-int srgan_h_pack_k4s2_weights(const float* w, void* packed, int32_t A, int32_t B, int direction, int dtype, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (const int status = check_precision<0, 1, 2>(dtype, H_ANY)) return status;
-  SRGAN_REQUIRE(w && packed && A > 0 && B > 0 && (direction == 0 || direction == 1), SRGAN_EINVAL, "srgan_h_pack_k4s2_weights arguments");
-  // "down": one operand of rows A; "up": the four parity classes, rows B each
-  const int classes = direction ? 4 : 1;
-  const int64_t slots = srgan_h_k4s2_weight_slots(A, B, direction, dtype) / classes;
-  const dim3 grid((unsigned)((slots + 255) / 256));
-  return launch_for_precision<0, 1, 2>(dtype, [&](auto prec) {
-    auto kernel = h_pack_k4s2_weights_kernel<decltype(prec)::value>;
-    if (direction == 0) hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w, (Slot*)packed, slots, A, B, (int64_t)B * 16, (int64_t)16, 0);
-    else
-      for (int cls = 0; cls < 4; ++cls)
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w, (Slot*)packed + cls * slots, slots, B, A, (int64_t)16, (int64_t)B * 16, 1 + cls);
-  });
-}
 
 // "down": out[N, rows, H/2, W/2] = epi(conv2d 4x4 / stride 2 / pad 1 of x[N, C_in, H, W]) with the direction-0 operand of
 // srgan_h_pack_k4s2_weights (rows = its A).  epi as srgan_h_conv3x3.

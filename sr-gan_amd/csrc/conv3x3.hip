@@ -46,7 +46,7 @@ struct Conv3Params {
   const float* epi_x; int64_t epi_x_bs;
   float* epi_partial; int32_t epi_tiles;
   const void* w_packed;   // mixed precision: the weights repacked by conv3x3_pack_weights_kernel (16-byte operand slots);
-                          // fp32 (WIMG kernels): the layer's weight image img[(ci * 9 + tap) * CO_pad + o] (blocked16.h)
+                          // fp32 (WIMG kernels): the layer's weight image img[(ci * 9 + tap) * CO_pad + o] (weight_shadows.h)
   // Output placement: element (o, y, x) of the H x W grid the kernel walks goes to out[o * out_plane + y * out_sy +
   // x * out_sx + out_off] (a plain convolution: H * W, W, 1, 0; a stride-2 class of a transposed convolution writes every
   // other pixel of a 2H x 2W plane) and `taps` is the 9-bit mask of the window positions (kh * 3 + kw) that exist.
@@ -73,7 +73,7 @@ __device__ unsigned int g_conv3_split_tickets[SPLIT_TICKET_SETS * SPLIT_TICKET_T
 // TAPS: compile-time mask of the window positions the inner loop multiplies (0x1FF = the full 3x3 window; the four
 // stride-2 classes of a k4 / s2 / p1 transposed convolution are 2x2 sub-windows: 0x01B, 0x036, 0x0D8, 0x1B0).
 // WIMG: the weights come from the layer's weight image (p.w_packed, packed once per optimizer step: conv3x3_image_element,
-// blocked16.h) instead of being gathered, transposed and zero-padded from p.w in every workgroup.  A chunk's slice of the image
+// weight_shadows.h) instead of being gathered, transposed and zero-padded from p.w in every workgroup.  A chunk's slice of the image
 // is CI_T * 9 runs of BM contiguous floats, rows and channels that do not exist are zeros IN the image, so each wave moves its
 // share with two or three global_load_lds_dwordx4 (no register, no predicate, no LDS write instruction) into one of TWO weight
 // stages: the next chunk's slice lands during this chunk's MFMAs.  The LDS rows are BM floats, unpadded: the fragment reads are

@@ -27,8 +27,8 @@ enum LaunchKind {
   KIND_STEM7X7_WGRAD = 11,
   KIND_STEM7X7_BWD_DATA = 12,
   KIND_POINTWISE_RING = 13,     // pointwise_ring.hip
-  KIND_HCONV3X3 = 14,           // blocked16.hip: forward and data gradient
-  KIND_HWGRAD3X3 = 15,
+  KIND_HCONV3X3 = 14,           // blocked16_conv3x3.hip: forward and data gradient
+  KIND_HWGRAD3X3 = 15,          // blocked16_conv3x3_wgrad.hip
   KIND_HGEMM = 16,              // blocked16_gemm.hip
   KIND_HLINEAR_WGRAD = 17,
   KIND_HCONV4X4S2 = 18,         // blocked16_k4s2.hip
@@ -75,7 +75,7 @@ inline BnBackwardEpilogue bn_backward_epilogue(const srgan_bn_relu* bn, const fl
 struct Conv3Placement { int32_t taps, out_plane, out_sy, out_sx, out_off; };
 constexpr int CONV3_MIN_WIDTH = 7;        // narrowest plane of the kernel (the 14- and 7-wide planes at 224)
 // How the kernel walks its weights: element (o, i, kh, kw) of the 3x3 window at w[base + o * so + i * si + kh * skh + kw * skw];
-// `image`: the operand's weight image (blocked16.h), fused fp32 forms only.
+// `image`: the operand's weight image (weight_shadows.h), fused fp32 forms only.
 struct Conv3Weights { const float* w; int32_t base, so, si, skh, skw; const float* image; };
 // The forward taps of a [K, C, 3, 3] weight (o = k, i = c).
 inline Conv3Weights conv3_forward_taps(const float* w, int32_t C, const float* image = nullptr) {

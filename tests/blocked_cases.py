@@ -10,14 +10,14 @@ or 4.  The one rounding of a 16-bit store is torch's CPU conversion `.to(torch.b
 """
 import torch
 
-# ---- the hosts' constants (common.h, split_finish.h, blocked16.h, blocked16.hip) ---------------------------------------------
+# ---- the hosts' constants (common.h, split_finish.h, weight_shadows.h, blocked16_streaming.hip, blocked16_shadows.hip) -------
 THREADS = 256
 STREAM_BLOCKS = 2048            # stream_grid's cap
 ROW_FINISH_ROWS = 4096          # split_finish.h: channel groups per launch that can use the ordered finish; above: two launches
 SUMS_PER_PART = 4096            # srgan_h_channel_sums: (n, pixel) pairs per workgroup of a group ...
 SUMS_MAX_PARTS = 256            # ... at most this many workgroups per group ...
 SUMS_MAX_BLOCKS = 4096          # ... halved while parts * CG is above this
-K4_CK, K4_TAPS = 4, 4           # blocked16.h: k-slots per chunk and taps of the 4x4 / stride 2 operands
+K4_CK, K4_TAPS = 4, 4           # weight_shadows.h: k-slots per chunk and taps of the 4x4 / stride 2 operands
 TILE = 64                       # h_pack_matrix_tile: rows x columns of one workgroup
 
 GROUP = {0: 4, 1: 8, 2: 8}      # channels per 16-byte slot

@@ -15,26 +15,26 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 def test_constants_mirror_the_kernel_sources():
     """A changed host constant fails here (and then, with the mirror updated, in the branch tests below) instead of silently
     un-covering a branch."""
-    text = {name: open(os.path.join(CSRC, name)).read() for name in ('common.h', 'split_finish.h', 'blocked16.h', 'blocked16.hip',
-                                                                     'blocked16_gemm.hip', 'precision_dispatch.h')}
+    text = {name: open(os.path.join(CSRC, name)).read() for name in os.listdir(CSRC) if name.endswith(('.h', '.hip'))}
+    everything = ''.join(text.values())
     assert f'if (blocks > {B.STREAM_BLOCKS}) blocks = {B.STREAM_BLOCKS};' in text['common.h']
     assert f'constexpr int ROW_FINISH_ROWS = {B.ROW_FINISH_ROWS};' in text['split_finish.h']
     assert 'if (split_atomics_forced() || rows > ROW_FINISH_ROWS || parts < 1) return nullptr;' in text['split_finish.h']
-    host = text['blocked16.hip']
+    host = text['blocked16_streaming.hip']
     assert f'int parts = (int)((per_group + {B.SUMS_PER_PART - 1}) / {B.SUMS_PER_PART});' in host
     assert f'if (parts > {B.SUMS_MAX_PARTS}) parts = {B.SUMS_MAX_PARTS};' in host
     assert f'while (parts > 1 && (int64_t)parts * CG > {B.SUMS_MAX_BLOCKS}) parts >>= 1;' in host
     assert 'float* part = row_finish_workspace(CG, parts, 8, g_h_sum_tickets, s, &tickets);' in host
     assert f'i += (int64_t)parts * {B.THREADS})' in host
-    assert f'constexpr int K4_CK = {B.K4_CK};' in text['blocked16.h'] and f'constexpr int K4_TAPS = {B.K4_TAPS};' in text['blocked16.h']
-    # the 64 x 64 tile: the LDS array, the tile origin and both hosts' tile counts
-    assert f'float (*tile)[{B.TILE + 1}]' in text['blocked16.h'] and f'__shared__ float tile[{B.TILE}][{B.TILE + 1}];' in host
-    assert f'r0 = (int64_t)(tile_index % tiles_r) * {B.TILE}, c0 = (int64_t)(tile_index / tiles_r) * {B.TILE};' in text['blocked16.h']
-    assert f'tiles_r = (rows + {B.TILE - 1}) / {B.TILE}, tiles = tiles_r * ((row_slots * 8 + {B.TILE - 1}) / {B.TILE});' in host
-    assert f'tiles_r = (int)((rows + {B.TILE - 1}) / {B.TILE}), tiles_c = (int)((row_slots * 8 + {B.TILE - 1}) / {B.TILE});' in text['blocked16_gemm.hip']
-    # the switch between the two matrix bodies, in the single call and in the job
-    assert host.count('if (row_stride == 1 && col_stride != 1) {') == 1
-    assert text['blocked16_gemm.hip'].count('if (row_stride == 1 && col_stride != 1) {') == 1
+    layouts, shadows = text['weight_shadows.h'], text['blocked16_shadows.hip']
+    assert f'constexpr int K4_CK = {B.K4_CK};' in layouts and f'constexpr int K4_TAPS = {B.K4_TAPS};' in layouts
+    # the 64 x 64 tile: the LDS array (of the single-layer kernel and of the batched one), the tile origin and the hosts' tile count
+    assert f'float (*tile)[{B.TILE + 1}]' in layouts and shadows.count(f'__shared__ float tile[{B.TILE}][{B.TILE + 1}];') == 2
+    assert f'r0 = (int64_t)(tile_index % tiles_r) * {B.TILE}, c0 = (int64_t)(tile_index / tiles_r) * {B.TILE};' in layouts
+    tile_count = f'tiles_r = (rows + {B.TILE - 1}) / {B.TILE}, tiles = tiles_r * ((row_slots * 8 + {B.TILE - 1}) / {B.TILE});'
+    assert tile_count in shadows and everything.count(tile_count) == 1 and everything.count(f'(rows + {B.TILE - 1}) / {B.TILE}') == 1
+    # the switch between the two matrix bodies: one rule for the single call and the job
+    assert 'return row_stride == 1 && col_stride != 1;' in shadows and everything.count('row_stride == 1') == 1
     # four channels per slot for dtype 0, eight for the 16-bit types
     found = re.search(r'slot_channels\(int \w+\) \{ return \w+ == 0 \? (\d+) : (\d+); \}', text['precision_dispatch.h'])
     assert found and (int(found.group(1)), int(found.group(2))) == (B.GROUP[0], B.GROUP[1]) and B.GROUP[2] == B.GROUP[1]
