@@ -90,6 +90,9 @@ const char* srgan_last_error(void);
                                                     tensor: moments, edges and counts of its finite elements) */
 #define SRGAN_FEATURE_REGRESSION_EVALUATION 0x40000u /* ABI 1.1, additive: srgan_regression_evaluation_sums (the sums behind
                                                         the age / driving evaluation scalars, from a batch on the device) */
+#define SRGAN_FEATURE_CROWD_PATCH_DRAWS 0x80000u /* ABI 1.1, additive: srgan_crowd_draw_patches /
+                                                    srgan_crowd_extract_patches_indexed (the crowd loader's patch positions drawn
+                                                    on the device; the cut over per-scene tables) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -519,6 +522,42 @@ int srgan_crowd_extract_patches(const void* const* images_u8, const float* const
                                 const int32_t* heights, const int32_t* widths, const int32_t* ys, const int32_t* xs,
                                 const int32_t* flips, int32_t B, int32_t P, float* out_images, float* out_labels,
                                 float* out_maps, void* stream);
+/* The same batch with the host taken out (SRGAN_FEATURE_CROWD_PATCH_DRAWS): the positions drawn on the device from the stream
+ * of srgan_random_fill, and the cut driven by that table over per-SCENE tables that are uploaded once.  All pointers are device
+ * pointers.
+ * srgan_crowd_draw_patches: table int32[n][4], row i = {scene, y, x, flip_bit} of global example e = first + i.
+ *   starts[S + 1]: the running count of valid patch centres; scene s owns starts[s + 1] - starts[s] =
+ *     max(heights[s] - P + 1, 0) * max(widths[s] - P + 1, 0) of them; length = starts[S], 1 <= length < 2^63.
+ *   state: the uint32[4] = {seed_lo, seed_hi, iteration, 0} of srgan_random_fill.
+ *   Example e owns the WHOLE Philox block e of draw `draw` (counter (e & 0xffffffff, e >> 32, draw, iteration), words w0..w3):
+ *     r = (uint64(w1) << 32) | w0;  index = floor(r * length / 2^64), the high half of the 128-bit product -- no rejection
+ *     loop: a centre's probability deviates from 1 / length by less than 2^-64, i.e. the deviation from uniform is below
+ *     length / 2^64 per centre, relative;
+ *     scene = the largest s in [0, S) with starts[s] <= index (a scene without a centre is never chosen);
+ *     local = index - starts[scene], columns = widths[scene] - P + 1;
+ *     y = P / 2 + local / columns, x = P / 2 + local % columns;  flip_bit = flip ? (w2 >> 31) : 0;  w3 is unused.
+ *   A window [first, first + n) holds the same rows whoever fills it: a data-parallel rank fills first = rank * local_batch.
+ *   One thread per example; no LDS, no atomics, no workspace.  The consistency of starts / heights / widths is the caller's
+ *   contract (checking it would need a synchronisation); the search is clamped to [0, S - 1], so the kernel never indexes
+ *   outside the three tables whatever they hold.
+ *   Before any device work: a NULL pointer, S < 1, P < 2 or odd, n < 0, first < 0 (or first + n beyond 2^63 - 1), draw < 0:
+ *   SRGAN_EINVAL.  n == 0 is a successful no-op.
+ * srgan_crowd_extract_patches_indexed: images_u8 / labels / maps / heights / widths have one entry per scene (length S);
+ *   example b is the patch of scene table[b][0] centred on (table[b][1], table[b][2]), mirrored when table[b][3] != 0, with
+ *   the pixel contract of srgan_crowd_extract_patches bit for bit (labels / maps and their outputs may be NULL).  A row whose
+ *   scene is outside [0, S) yields an all-padding patch (-1 / 0 / 0) and reads no scene memory.  One wave per patch row, four
+ *   rows per workgroup; 16-byte stores when P % 4 == 0 and the three outputs are 16-byte aligned, single floats otherwise,
+ *   with the same results.  Before any device work: NULL images_u8 / heights / widths / table / out_images, S < 1, B < 1 or
+ *   B > 65535, P < 1 or odd: SRGAN_EINVAL; B * 3 * P * P above max_tensor_elements: SRGAN_ERANGE. */
+#define SRGAN_CROWD_PATCH_DRAW_LABELED 0x30000      /* the labeled loader's draw id: above the dropout ranges */
+#define SRGAN_CROWD_PATCH_DRAW_UNLABELED 0x30001    /* the unlabeled loader's */
+int srgan_crowd_draw_patches(const int64_t* starts, const int32_t* heights, const int32_t* widths, int32_t S, int32_t P,
+                             int32_t flip, int64_t first, int32_t n, int32_t draw, const uint32_t* state, int32_t* table,
+                             void* stream);
+int srgan_crowd_extract_patches_indexed(const void* const* images_u8, const float* const* labels, const float* const* maps,
+                                        const int32_t* heights, const int32_t* widths, int32_t S, const int32_t* table,
+                                        int32_t B, int32_t P, float* out_images, float* out_labels, float* out_maps,
+                                        void* stream);
 /* The sums behind the crowd evaluation scalars (SRGAN_FEATURE_CROWD_EVALUATION; reference crowd/srgan.py:149-191: count ME /
  * MAE / MSE and kNN-map MAE / MSE) of one batch that lives on the device.  predicted_counts [B]; labels [B, HW], the head-count
  * label patches; predicted_maps [B, M, HW] and maps [B, HW], both or neither; all fp32, contiguous.  With L_b = the sum of

@@ -121,6 +121,8 @@ SIGNATURES = {
     'srgan_crowd_density_label': ([vp, i32, i32, i32, f32, vp, i32, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_iknn_map': ([vp, i32, i32, i32, i32, f32, f32, vp, vp], ctypes.c_int),
     'srgan_crowd_extract_patches': ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp], ctypes.c_int),
+    'srgan_crowd_draw_patches': ([vp, vp, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp], ctypes.c_int),
+    'srgan_crowd_extract_patches_indexed': ([vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_evaluation_sums': ([vp, vp, vp, vp, i32, i32, i64, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_evaluation_scratch_bytes': ([i32, i32, i64], ctypes.c_int64),
     'srgan_regression_evaluation_sums': ([vp, i64, i32, vp, vp, i32, vp, vp], ctypes.c_int),

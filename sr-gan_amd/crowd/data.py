@@ -170,6 +170,11 @@ def evaluation_batch_count(batch_size):
     return -(-100 // batch_size) + 1
 
 
+# The draw ids of the two loaders' device draws (SRGAN_CROWD_PATCH_DRAW_* in include/srgan_hip.h): above the dropout ranges
+# [0x10000, 0x30000), away from an iteration's draws 0, 1, 2 and the summary draws 8 and 9.
+CROWD_DRAW_LABELED, CROWD_DRAW_UNLABELED = 0x30000, 0x30001
+
+
 class DeviceCrowdPatchLoader:
     """Endless training batches cut ON THE DEVICE from full crowd scenes that stay resident in HBM:
     the reference's ``ShanghaiTechTransformedDataset`` + ``DataLoader(num_workers=4)`` pipeline (random position
@@ -179,12 +184,25 @@ class DeviceCrowdPatchLoader:
     ``examples``: ``CrowdExample``s with uint8 ``image`` (H, W, 3) and float ``label`` / ``map`` (H, W).  Yields
     ``(image f32[B, 3, P, P], label f32[B, P, P], map f32[B, P, P])`` device tensors -- the batch contract of
     ``CrowdExperiment``.  Positions and flips come from a private ``numpy`` generator (the reference's
-    multi-process workers make its own stream irreproducible anyway)."""
+    multi-process workers make its own stream irreproducible anyway).
 
-    def __init__(self, examples, batch_size, image_patch_size=224, seed=0, device=None, flip=True, dp=None):
+    ``draws='device'`` takes the host out of a batch: the positions come from the port's
+    counter-based stream (``srgan_crowd_draw_patches``: example ``e`` of the batch of iteration ``i`` is a function of
+    ``(seed, i, draw_id, e)``), the scenes' pointers, shapes and running centre counts are uploaded ONCE, and a batch is the
+    draw, ``srgan_crowd_extract_patches_indexed`` and ``srgan_random_advance`` -- three launches, no host-to-device copy.
+    ``start_at(step)`` puts the stream at an iteration (a continued run: its ``starting_step``), ``last_table`` is the
+    ``int32 [local batch, 4]`` table ``(scene, y, x, flip)`` of the latest batch, ``batch_for_table`` cuts an explicit
+    device table.  Under ``dp`` a rank draws only its own rows of the global table."""
+
+    def __init__(self, examples, batch_size, image_patch_size=224, seed=0, device=None, flip=True, dp=None, draws='host',
+                 draw_id=CROWD_DRAW_LABELED):
         """``batch_size`` is the GLOBAL batch; under data parallelism (``dp``) every rank draws the positions of the whole
-        batch from the shared seed and cuts only its own contiguous slice (same examples as one device would see)."""
+        batch from the shared seed and cuts only its own contiguous slice (same examples as one device would see).
+        ``draws``: ``'host'`` (the private ``numpy`` generator) or ``'device'`` (draw ``draw_id`` of the counter-based stream
+        under ``seed``, taken modulo 2^64)."""
         from .. import _lib
+        if draws not in ('host', 'device'):
+            raise ValueError("draws is 'host' or 'device', not {!r}".format(draws))
         self.dp = dp if dp is not None and dp.world_size > 1 else None
         if self.dp is not None:
             self.dp.local_batch(batch_size)           # raises unless the global batch divides over the ranks
@@ -192,7 +210,7 @@ class DeviceCrowdPatchLoader:
         self._lib = _lib
         self.device = device or current_device()
         self.batch_size, self.patch_size, self.flip = batch_size, image_patch_size, flip
-        self.generator = np.random.RandomState(seed)
+        self.generator = np.random.RandomState(seed) if draws == 'host' else None      # (a device seed has 64 bits)
         half = image_patch_size // 2
         self.images, self.labels, self.maps, self.shapes, self.start_indexes = [], [], [], [], []
         self.length = 0
@@ -207,10 +225,88 @@ class DeviceCrowdPatchLoader:
             self.length += max(height - 2 * half + 1, 0) * max(width - 2 * half + 1, 0)
         if self.length == 0:
             raise ValueError('no scene is as large as one patch')
+        self.draw_mode, self.draw_id, self.seed = draws, int(draw_id), seed
+        self.state = self.last_table = self.scene_pointers = None
+        if draws == 'device':
+            if image_patch_size < 2 or image_patch_size % 2:
+                raise ValueError('device draws need an even patch size')
+            self.upload_scene_table()
+
+    def upload_scene_table(self):
+        """The per-SCENE tables of the indexed entry points, uploaded once: ``scene_pointers`` int64 ``[3, S]`` (images,
+        labels, maps), ``scene_heights`` / ``scene_widths`` int32 ``[S]`` and ``scene_starts`` int64 ``[S + 1]``, the running
+        count of valid centres (``scene_starts[S] == length``)."""
+        if self.scene_pointers is None:
+            pointers = [[tensor.data_ptr() for tensor in tensors] for tensors in (self.images, self.labels, self.maps)]
+            self.scene_pointers = torch.tensor(pointers, dtype=torch.int64).to(self.device)
+            self.scene_heights = torch.tensor([shape[0] for shape in self.shapes], dtype=torch.int32).to(self.device)
+            self.scene_widths = torch.tensor([shape[1] for shape in self.shapes], dtype=torch.int32).to(self.device)
+            self.scene_starts = torch.tensor(self.start_indexes + [self.length], dtype=torch.int64).to(self.device)
+            # the leading arguments of the two calls, as plain integers: nothing is looked up per batch
+            self._draw_arguments = (self.scene_starts.data_ptr(), self.scene_heights.data_ptr(),
+                                    self.scene_widths.data_ptr(), len(self.shapes))
+            self._cut_arguments = tuple(self.scene_pointers[row].data_ptr() for row in range(3)) + self._draw_arguments[1:]
+        return self
+
+    @property
+    def local_batch_size(self):
+        """The rows of the global batch this rank cuts."""
+        return self.batch_size if self.dp is None else self.batch_size // self.dp.world_size
+
+    def start_at(self, step):
+        """Device draws: the next batch is that of iteration ``step`` (``state`` = ``nn.draw_state(seed, step)``)."""
+        if self.draw_mode != 'device':
+            raise ValueError("start_at belongs to draws='device': the host generator has no position to set")
+        from ..nn import draw_state
+        self.state = draw_state(self.seed, step).to(self.device)
+
+    def _stream(self):
+        return torch._C._cuda_getCurrentRawStream(self.device.index if self.device.index is not None
+                                                  else torch._C._cuda_getDevice())
+
+    def draw_table(self):
+        """Device draws: this rank's rows of the current iteration's table, ``int32 [local batch, 4]`` on the device (the
+        state is not advanced)."""
+        if self.state is None:
+            self.start_at(0)
+        local = self.local_batch_size
+        first = self.dp.rank * local if self.dp is not None else 0
+        table = torch.empty((local, 4), dtype=torch.int32, device=self.device)
+        self._lib.check(self._lib.library().srgan_crowd_draw_patches(
+            *self._draw_arguments, self.patch_size, int(bool(self.flip)), first, local, self.draw_id, self.state.data_ptr(),
+            table.data_ptr(), self._stream()), 'srgan_crowd_draw_patches')
+        return table
+
+    def batch_for_table(self, table):
+        """The device batch of an explicit DEVICE table ``int32 [count, 4]`` of ``(scene, y, x, flip)`` rows -- the device
+        counterpart of ``batch_for``: one launch, nothing uploaded.  A row whose scene is outside ``[0, S)`` gives an
+        all-padding patch."""
+        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous():
+            raise ValueError('a table is a contiguous int32 [count, 4] tensor')
+        self.upload_scene_table()
+        count, size = table.shape[0], self.patch_size
+        image = torch.empty((count, 3, size, size), dtype=torch.float32, device=self.device)
+        label = torch.empty((count, size, size), dtype=torch.float32, device=self.device)
+        map_ = torch.empty((count, size, size), dtype=torch.float32, device=self.device)
+        self._lib.check(self._lib.library().srgan_crowd_extract_patches_indexed(
+            *self._cut_arguments, table.data_ptr(), count, size, image.data_ptr(), label.data_ptr(), map_.data_ptr(),
+            self._stream()), 'srgan_crowd_extract_patches_indexed')
+        return image, label, map_
+
+    def device_batch(self):
+        """Device draws: one batch -- draw, cut, advance -- enqueued on the current stream."""
+        table = self.draw_table()
+        batch = self.batch_for_table(table)
+        self._lib.check(self._lib.library().srgan_random_advance(self.state.data_ptr(), self._stream()),
+                        'srgan_random_advance')
+        self.last_table = table
+        return batch
 
     def draw_positions(self):
         """(scene index, y, x, flip) of one batch: a uniform draw over all valid centres (reference
         crowd/shanghai_tech_data.py:83-98) and a fair coin per example (crowd/data.py:104)."""
+        if self.generator is None:
+            raise ValueError("draw_positions belongs to draws='host': device draws are read from last_table")
         draws = [draw_example(self.generator, self.length, self.start_indexes, self.shapes, self.patch_size, self.flip)
                  for _ in range(self.batch_size)]
         if self.dp is not None:
@@ -239,7 +335,7 @@ class DeviceCrowdPatchLoader:
 
     def __iter__(self):
         while True:
-            yield self.batch_for(self.draw_positions())
+            yield self.device_batch() if self.draw_mode == 'device' else self.batch_for(self.draw_positions())
 
 
 class ResidentCrowdEvaluationSet:
@@ -252,20 +348,28 @@ class ResidentCrowdEvaluationSet:
 
     ``source``: a ``DeviceCrowdPatchLoader`` whose resident scenes are shared (the train set: no second upload; its
     generator is not touched) or a list of ``CrowdExample``s that are uploaded here (the test split).  Nothing but the
-    scenes and the draw list is kept between evaluations: every batch is one ``srgan_crowd_extract_patches`` launch."""
+    scenes and the draw list is kept between evaluations: every batch is one ``srgan_crowd_extract_patches`` launch.
 
-    def __init__(self, source, batch_size, image_patch_size=224, seed=0, flip=False, device=None):
+    Over a loader in device mode (``draws='device'``; for scenes uploaded here: the ``draws`` argument) the list -- still
+    drawn by the host rule -- is uploaded once as ``table``, int32 ``[N, 4]``, and every batch is a slice of it cut by
+    ``batch_for_table``: the same bits as ``batch_for``, no per-evaluation upload.  The loader's state is not touched."""
+
+    def __init__(self, source, batch_size, image_patch_size=224, seed=0, flip=False, device=None, draws='host'):
         if isinstance(source, DeviceCrowdPatchLoader):
             if source.patch_size != image_patch_size:
                 raise ValueError('the evaluation set shares the scenes of a loader with another patch size')
             self.scenes = source
         else:       # a loader of its own is the upload; one device, and its generator is never drawn from
-            self.scenes = DeviceCrowdPatchLoader(source, batch_size, image_patch_size, seed=seed, device=device, flip=flip)
+            self.scenes = DeviceCrowdPatchLoader(source, batch_size, image_patch_size, seed=seed, device=device, flip=flip,
+                                                 draws=draws)
         self.batch_size, self.patch_size, self.flip, self.seed = batch_size, image_patch_size, flip, seed
         generator = np.random.RandomState(seed)
         scenes = self.scenes
         self.draws = [draw_example(generator, scenes.length, scenes.start_indexes, scenes.shapes, image_patch_size, flip)
                       for _ in range(evaluation_batch_count(batch_size) * batch_size)]
+        self.table = None
+        if scenes.draw_mode == 'device':
+            self.table = torch.tensor(self.draws, dtype=torch.int32).to(scenes.device)
 
     def __len__(self):
         return len(self.draws)
@@ -273,11 +377,18 @@ class ResidentCrowdEvaluationSet:
     def device_batches(self):
         """``(image f32[B, 3, P, P], label f32[B, P, P], map f32[B, P, P])`` device batches, in list order."""
         for start in range(0, len(self.draws), self.batch_size):
-            yield self.scenes.batch_for(self.draws[start:start + self.batch_size])
+            if self.table is not None:
+                yield self.scenes.batch_for_table(self.table[start:start + self.batch_size])
+            else:
+                yield self.scenes.batch_for(self.draws[start:start + self.batch_size])
 
     def __getitem__(self, index):
         """Example ``index`` of the list as device tensors ``(image[3, P, P], label[P, P], map[P, P])``."""
-        image, label, map_ = self.scenes.batch_for([self.draws[index]])
+        if self.table is not None:
+            index = range(len(self.draws))[index]             # negative indices and IndexError as the list's
+            image, label, map_ = self.scenes.batch_for_table(self.table[index:index + 1])
+        else:
+            image, label, map_ = self.scenes.batch_for([self.draws[index]])
         return image[0], label[0], map_[0]
 
 

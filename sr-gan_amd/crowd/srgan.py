@@ -50,10 +50,11 @@ class CrowdExperiment(Experiment):
             def scenes(count):
                 return PreprocessedCrowdDataset(directory, 'train', part, number_of_examples=count,
                                                 map_directory_name=maps).examples()
+            labeled, unlabeled = self.patch_loader_arguments()
             self.train_dataset_loader = DeviceCrowdPatchLoader(scenes(settings.labeled_dataset_size), settings.batch_size,
-                                                               size, seed=settings.labeled_dataset_seed, dp=self.dp)
+                                                               size, dp=self.dp, **labeled)
             self.unlabeled_dataset_loader = DeviceCrowdPatchLoader(scenes(settings.unlabeled_dataset_size),
-                                                                   settings.batch_size, size, seed=100, dp=self.dp)
+                                                                   settings.batch_size, size, dp=self.dp, **unlabeled)
             self.dataset_class = lambda dataset, map_directory_name: PreprocessedCrowdDataset(
                 directory, dataset, part, map_directory_name=map_directory_name)
             self.attach_evaluation_sets(lambda count: PreprocessedCrowdDataset(
@@ -62,6 +63,20 @@ class CrowdExperiment(Experiment):
         self.train_dataset_loader = SyntheticLoader.crowd(settings.batch_size, size, seed=settings.labeled_dataset_seed,
                                                           dp=self.dp)
         self.unlabeled_dataset_loader = SyntheticLoader.crowd(settings.batch_size, size, seed=100, dp=self.dp)
+
+    def patch_loader_arguments(self):
+        """``(labeled, unlabeled)`` keyword arguments of the two database loaders under ``self.crowd_patch_draws``.  ``'host'``:
+        the private generators' seeds, as ever.  ``'device'``: positions from the counter-based stream under
+        ``settings.device_random_seed``, one draw id per loader, so that a batch is a function of ``(seed, step)``
+        (``training_loop`` puts the loaders at ``starting_step``)."""
+        from .data import CROWD_DRAW_LABELED, CROWD_DRAW_UNLABELED
+        if self.crowd_patch_draws not in ('host', 'device'):
+            raise ValueError("crowd_patch_draws is 'host' or 'device', not {!r}".format(self.crowd_patch_draws))
+        if self.crowd_patch_draws == 'host':
+            return dict(seed=self.settings.labeled_dataset_seed), dict(seed=100)
+        seed = option(self.settings, 'device_random_seed')
+        return (dict(seed=seed, draws='device', draw_id=CROWD_DRAW_LABELED),
+                dict(seed=seed, draws='device', draw_id=CROWD_DRAW_UNLABELED))
 
     def ucf_qnrf_dataset_setup(self, directory):
         """The UCF-QNRF branch of reference crowd/srgan.py:34-52 (``settings.crowd_dataset`` ``CrowdDataset.ucf_qnrf`` or
@@ -76,11 +91,12 @@ class CrowdExperiment(Experiment):
         def scenes(count, start=None):
             return UcfQnrfCrowdDataset(directory, 'train', seed=settings.labeled_dataset_seed, number_of_examples=count,
                                        map_directory_name=maps, examples_start=start).examples()
+        labeled, unlabeled = self.patch_loader_arguments()
         self.train_dataset_loader = DeviceCrowdPatchLoader(scenes(settings.labeled_dataset_size), settings.batch_size, size,
-                                                           seed=settings.labeled_dataset_seed, dp=self.dp)
+                                                           dp=self.dp, **labeled)
         self.unlabeled_dataset_loader = DeviceCrowdPatchLoader(
-            scenes(settings.unlabeled_dataset_size, settings.labeled_dataset_size), settings.batch_size, size, seed=100,
-            dp=self.dp)
+            scenes(settings.unlabeled_dataset_size, settings.labeled_dataset_size), settings.batch_size, size, dp=self.dp,
+            **unlabeled)
         self.dataset_class = lambda dataset, map_directory_name: UcfQnrfCrowdDataset(
             directory, dataset, seed=0, map_directory_name=map_directory_name)
         self.attach_evaluation_sets(lambda count: UcfQnrfCrowdDataset(
@@ -102,7 +118,7 @@ class CrowdExperiment(Experiment):
                                                         seed=settings.labeled_dataset_seed, flip=True)
         self.validation_dataset = ResidentCrowdEvaluationSet(
             validation_scenes(option(settings, 'crowd_validation_scenes')), settings.batch_size, size, seed=101,
-            flip=False, device=self.train_dataset_loader.device)
+            flip=False, device=self.train_dataset_loader.device, draws=self.train_dataset_loader.draw_mode)
 
     def model_setup(self):
         """reference crowd/srgan.py:92-96 (``pretrained=True`` there downloads torchvision weights; offline the

@@ -7,7 +7,10 @@
 // Pixels outside the scene are zero BEFORE normalisation (the reference pads the uint8 image), i.e. -1 afterwards.
 // The same row body cuts the sliding windows of ONE scene for full-image inference (srgan_crowd_extract_windows: centres
 // from two small tables instead of per-example pointer tables; 3 bytes read, 12 bytes written per pixel).
+// srgan_crowd_draw_patches / srgan_crowd_extract_patches_indexed are the same batch with the host taken out: the positions
+// come from the counter-based stream of philox.h and the tables are per scene, uploaded once.
 #include "common.h"
+#include "philox.h"
 
 namespace srgan {
 
@@ -89,9 +92,99 @@ __global__ __launch_bounds__(256) void crowd_windows_kernel(const uint8_t* __res
                  out_images + (int64_t)blockIdx.y * 3 * P * P + (int64_t)row * P, nullptr, nullptr);
 }
 
+// Training batches without the host.  The draw: one thread per example, example e = first + i owns Philox block
+// e of the draw; the 64-bit word (w1, w0) scaled to [0, length) by the high half of the 128-bit product picks a centre out of
+// the running counts `starts`, a binary search finds its scene, bit 31 of w2 is the coin.
+__global__ __launch_bounds__(256) void crowd_draw_patches_kernel(const int64_t* __restrict__ starts,
+                                                                 const int32_t* __restrict__ heights,
+                                                                 const int32_t* __restrict__ widths, int S, int P, int flip,
+                                                                 int64_t first, int n, uint32_t draw,
+                                                                 const uint32_t* __restrict__ state,
+                                                                 int32_t* __restrict__ table) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[4];
+  draw_block_words((uint64_t)first + (uint64_t)i, draw, state[2], state[0], state[1], w);
+  const uint64_t r = ((uint64_t)w[1] << 32) | w[0];
+  const int64_t index = (int64_t)__umul64hi(r, (uint64_t)starts[S]);      // < length
+  int lo = 0, hi = S - 1;                                                 // the largest s in [0, S) with starts[s] <= index
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (starts[mid] <= index) lo = mid; else hi = mid - 1;
+  }
+  const int64_t local = index - starts[lo];
+  const int64_t columns = max(widths[lo] - P + 1, 1);      // (consistent tables: >= 1 for a scene that owns a centre)
+  int32_t* entry = table + 4 * (int64_t)i;
+  entry[0] = lo;
+  entry[1] = P / 2 + (int)(local / columns);
+  entry[2] = P / 2 + (int)(local % columns);
+  entry[3] = flip ? (int)(w[2] >> 31) : 0;
+}
+
+// The cut: example b reads scene table[b][0] of the per-SCENE tables at centre (table[b][1], table[b][2]), mirrored when
+// table[b][3] != 0.  The form of crowd_windows_kernel: one wave per patch row, four rows per workgroup, 16-byte stores with
+// VEC = 4.  A scene outside [0, S) reads no table and no scene: H = W = 0 makes every pixel padding.
+template <int VEC>
+__global__ __launch_bounds__(256) void crowd_patches_indexed_kernel(const uint8_t* const* __restrict__ images,
+                                                                    const float* const* __restrict__ labels,
+                                                                    const float* const* __restrict__ maps,
+                                                                    const int32_t* __restrict__ heights,
+                                                                    const int32_t* __restrict__ widths, int S,
+                                                                    const int32_t* __restrict__ table, int P,
+                                                                    float* __restrict__ out_images,
+                                                                    float* __restrict__ out_labels,
+                                                                    float* __restrict__ out_maps) {
+  const int row = (int)blockIdx.x * WINDOW_ROWS + ((int)threadIdx.x >> 6);
+  if (row >= P) return;
+  const int b = blockIdx.y;
+  const int32_t* entry = table + 4 * (int64_t)b;
+  const int scene = entry[0];
+  const bool known = (unsigned)scene < (unsigned)S;
+  const int64_t plane = (int64_t)P * P;
+  patch_row<VEC>(known ? images[scene] : nullptr, known && labels ? labels[scene] : nullptr,
+                 known && maps ? maps[scene] : nullptr, known ? heights[scene] : 0, known ? widths[scene] : 0, entry[1],
+                 entry[2], entry[3] != 0, P, row, (int)threadIdx.x & 63, 64,
+                 out_images + (int64_t)b * 3 * plane + (int64_t)row * P,
+                 out_labels ? out_labels + (int64_t)b * plane + (int64_t)row * P : nullptr,
+                 out_maps ? out_maps + (int64_t)b * plane + (int64_t)row * P : nullptr);
+}
+
 }  // namespace srgan
 
 using namespace srgan;
+
+extern "C" int srgan_crowd_draw_patches(const int64_t* starts, const int32_t* heights, const int32_t* widths, int32_t S,
+                                        int32_t P, int32_t flip, int64_t first, int32_t n, int32_t draw,
+                                        const uint32_t* state, int32_t* table, void* stream) {
+  SRGAN_REQUIRE(starts && heights && widths && state && table, SRGAN_EINVAL, "srgan_crowd_draw_patches pointers");
+  SRGAN_REQUIRE(S >= 1 && P >= 2 && P % 2 == 0 && n >= 0 && draw >= 0, SRGAN_EINVAL, "srgan_crowd_draw_patches: S, P, n, draw");
+  SRGAN_REQUIRE(first >= 0 && first <= INT64_MAX - n, SRGAN_EINVAL, "srgan_crowd_draw_patches: first");
+  if (n == 0) return SRGAN_OK;
+  hipLaunchKernelGGL(crowd_draw_patches_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, starts, heights,
+                     widths, S, P, flip, first, n, (uint32_t)draw, state, table);
+  return launch_status();
+}
+
+extern "C" int srgan_crowd_extract_patches_indexed(const void* const* images_u8, const float* const* labels,
+                                                   const float* const* maps, const int32_t* heights, const int32_t* widths,
+                                                   int32_t S, const int32_t* table, int32_t B, int32_t P, float* out_images,
+                                                   float* out_labels, float* out_maps, void* stream) {
+  SRGAN_REQUIRE(images_u8 && heights && widths && table && out_images && S >= 1 && B > 0 && P > 0 && P % 2 == 0 &&
+                B <= 65535, SRGAN_EINVAL, "srgan_crowd_extract_patches_indexed arguments");
+  SRGAN_REQUIRE(P <= 46340 && (int64_t)B * 3 * P * P <= INT32_MAX, SRGAN_ERANGE,
+                "srgan_crowd_extract_patches_indexed: a tensor exceeds 2^31 - 1 elements");
+  const dim3 grid((P + WINDOW_ROWS - 1) / WINDOW_ROWS, B);
+  const uint8_t* const* images = reinterpret_cast<const uint8_t* const*>(images_u8);
+  const uintptr_t bases = reinterpret_cast<uintptr_t>(out_images) | reinterpret_cast<uintptr_t>(out_labels) |
+                          reinterpret_cast<uintptr_t>(out_maps);      // (a NULL output adds no bits)
+  if (P % 4 == 0 && bases % 16 == 0)
+    hipLaunchKernelGGL(crowd_patches_indexed_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, images, labels, maps, heights,
+                       widths, S, table, P, out_images, out_labels, out_maps);
+  else
+    hipLaunchKernelGGL(crowd_patches_indexed_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, images, labels, maps, heights,
+                       widths, S, table, P, out_images, out_labels, out_maps);
+  return launch_status();
+}
 
 extern "C" int srgan_crowd_extract_patches(const void* const* images_u8, const float* const* labels,
                                            const float* const* maps, const int32_t* heights, const int32_t* widths,

@@ -108,7 +108,8 @@ int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
                   SRGAN_FEATURE_BLOCKED_FROZEN_NORM | SRGAN_FEATURE_DEVICE_DRAWS | SRGAN_FEATURE_IMAGE_SUMMARIES |
                   SRGAN_FEATURE_DISTRIBUTION_SUMMARIES | SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE |
                   SRGAN_FEATURE_DROPOUT | SRGAN_FEATURE_FEATURE_LOSSES | SRGAN_FEATURE_CROWD_EVALUATION |
-                  SRGAN_FEATURE_SUMMARY_HISTOGRAM | SRGAN_FEATURE_REGRESSION_EVALUATION;
+                  SRGAN_FEATURE_SUMMARY_HISTOGRAM | SRGAN_FEATURE_REGRESSION_EVALUATION |
+                  SRGAN_FEATURE_CROWD_PATCH_DRAWS;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;

@@ -40,6 +40,7 @@ class DnnExperiment(Experiment, ABC):
 
     def training_loop(self):
         """reference dnn.py:78-100: the SRGAN loop without the unlabeled stream and the GAN step."""
+        self.start_loaders_at(self.starting_step)
         train_dataset_generator = self.infinite_iter(self.train_dataset_loader)
         step_time_start = datetime.datetime.now()
         for step in range(self.starting_step, self.settings.steps_to_run):

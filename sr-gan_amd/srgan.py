@@ -129,6 +129,9 @@ class Experiment(ABC):
     # them on the instance or in a subclass; any other value is a ValueError when the summaries are first taken.
     regression_validation = 'host'     # 'device': the summary step's errors from sums taken on the device
     validation_precision = 'f32'       # 'step': the evaluation's forward passes run under self.precision()
+    # How the crowd application's database loaders draw their patch positions (``crowd.data.DeviceCrowdPatchLoader``); the
+    # same kind of switch: an attribute, checked (``ValueError``) in the crowd ``dataset_setup``.
+    crowd_patch_draws = 'host'         # 'device': positions from the counter-based stream, a function of (seed, step)
 
     def __init__(self, settings: Settings):
         self.settings = settings
@@ -281,6 +284,7 @@ class Experiment(ABC):
 
     def training_loop(self):
         """The per-step hot loop (reference srgan.py:99-129)."""
+        self.start_loaders_at(self.starting_step)
         train_dataset_generator = self.infinite_iter(self.train_dataset_loader)
         unlabeled_dataset_generator = self.infinite_iter(self.unlabeled_dataset_loader)
         step_time_start = datetime.datetime.now()
@@ -1317,6 +1321,13 @@ class Experiment(ABC):
             return
         self.real_image_summary(to_image_range(self.first_train_batch()[:9]), range=(0, 255))
         self.generated_image_summaries(range=(0, 255), to_images=to_image_range)
+
+    def start_loaders_at(self, step):
+        """Before the first batch: a loader whose batches are a function of ``(seed, step)`` (``start_at``: the crowd loaders
+        with device draws) is put at ``step``, so that a continued run cuts what the uninterrupted run cuts there."""
+        for loader in (self.train_dataset_loader, self.unlabeled_dataset_loader):
+            if getattr(loader, 'draw_mode', 'device') == 'device' and hasattr(loader, 'start_at'):
+                loader.start_at(step)
 
     @staticmethod
     def infinite_iter(dataset):
