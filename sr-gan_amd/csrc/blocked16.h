@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "common.h"
 #include "precision_dispatch.h"
+#include "mfma.h"
 
 namespace srgan {
 
@@ -33,9 +34,6 @@ int launch_for_precision(int dtype, Functor&& functor) {
   return launch_status();
 }
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 h_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h_f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 h_bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h_f16x2 __attribute__((ext_vector_type(2)));
 typedef short h_s4 __attribute__((ext_vector_type(4)));
@@ -136,12 +134,10 @@ template <int PREC>
 __device__ __forceinline__ f32x16 h_mfma(const Slot& a, const Slot& b, f32x16 c) {
   if constexpr (PREC == 0) {           // fp32: the slot's four channels are four k-steps of v_mfma_f32_32x32x2_f32 (k pair = the
 #pragma unroll                         // same component of the two lane halves' slots)
-    for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.v[i]), __uint_as_float(b.v[i]), c, 0, 0, 0);
+    for (int i = 0; i < 4; ++i) c = mfma32(__uint_as_float(a.v[i]), __uint_as_float(b.v[i]), c);
     return c;
-  } else if constexpr (PREC == 1)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(h_bf16x8, a), __builtin_bit_cast(h_bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h_f16x8, a), __builtin_bit_cast(h_f16x8, b), c, 0, 0, 0);
+  } else
+    return mfma32<PREC>(__builtin_bit_cast(mfma_frag<PREC>, a), __builtin_bit_cast(mfma_frag<PREC>, b), c);
 }
 
 // LDS-DMA: 64 lanes x 16 bytes from PER-LANE global addresses to LDS at the wave-uniform byte address `lds_dst` + lane * 16

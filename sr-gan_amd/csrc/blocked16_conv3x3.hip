@@ -42,7 +42,7 @@ __device__ __forceinline__ void hconv3_stage_bias(const float* bias, int epi, in
   }
 }
 
-// Epilogue of the 3x3 kernels.  C/D fragment: column = pixel (lane & 31), rows (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5): registers
+// Epilogue of the 3x3 kernels.  C/D fragment: column = pixel (lane & 31), rows mfma32_row(r, lane >> 5): registers
 // 4q .. 4q + 3 are four CONSECUTIVE output channels = 8 bytes of the pixel's slot of group (m0 + 32 mi) / 8 + q; the 32 lanes of
 // a half cover 32 consecutive slots (with the other half: 512 contiguous bytes per store instruction).
 template <int BM, int NI, int TW, int ROWS, int PREC>
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void hconv3x3_kernel(const HConv3Params p) 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int logical_block = block;
   const int tm = block % p.tiles_m; block /= p.tiles_m;
   const int tx = block % p.tiles_x; block /= p.tiles_x;
@@ -263,8 +263,7 @@ __global__ __launch_bounds__(256, 2) void hconv3x3_kernel(const HConv3Params p) 
     constexpr int COUNT = MI * NI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.split_ws + (int64_t)logical_block * gridDim.y * (COUNT * 256), (int)blockIdx.y,
                                           (int)gridDim.y, p.split_tickets + logical_block,
-                                          [&](int i) { return acc[i / (NI * 16)][(i / 16) % NI][i % 16]; },
-                                          [&](int i, float v) { acc[i / (NI * 16)][(i / 16) % NI][i % 16] = v; }))
+                                          acc_flat(acc), acc_flat(acc)))
       return;
   }
 
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(256, RING == 2 ? 2 : 1) void hconv3x3_dma_kernel(co
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int tm = block % p.tiles_m; block /= p.tiles_m;
   const int tx = block % p.tiles_x; block /= p.tiles_x;
   const int ty = block % p.tiles_y;

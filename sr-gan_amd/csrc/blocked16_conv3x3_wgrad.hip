@@ -153,7 +153,7 @@ __global__ __launch_bounds__(128 * MB, 2) void hwgrad3x3_kernel(const HWgrad3Par
 // workgroup 64 consecutive gw elements = 7 of a line's 32 floats and fetched every line 4.5 times (18 GB per step, PMC
 // profiles/r06f) -- the four waves add the walkers w = wave, wave + 4, ... and the four sums meet as (0 + 1) + (2 + 3); the
 // row leaves through LDS in gw's own order.  The read index undoes the accumulator layout: wave = (co' / 32) * 2 + ci' / 32,
-// C/D row co' % 32 = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), column ci' % 32 = lane & 31.
+// C/D row co' % 32 = mfma32_row(r, lane >> 5), column ci' % 32 = lane & 31.
 __global__ __launch_bounds__(256) void hwgrad3x3_finish_kernel(const float* __restrict__ partial, float* __restrict__ gw,
                                                                int32_t CO, int32_t CI, int32_t tiles_ci, int32_t walkers,
                                                                int32_t block_rows) {
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void hwgrad3x3_finish_kernel(const float* __re
   if (co >= CO) return;
   const int threads = 4 * block_rows;
   const int64_t per_walker = (int64_t)9 * 16 * threads;              // accumulators of one workgroup
-  const int r32 = row & 31, lhi = (r32 >> 2) & 1, r = (r32 & 3) + 4 * (r32 >> 3);
+  const int r32 = row & 31, lhi = mfma32_half(r32), r = mfma32_register(r32);
   const int thread = ((row >> 5) * 2 + (lane >> 5)) * 64 + lhi * 32 + (lane & 31);
   const float* base = partial + (int64_t)block * walkers * per_walker + r * threads + thread;
   float total[9];

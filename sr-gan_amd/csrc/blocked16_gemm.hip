@@ -258,14 +258,14 @@ __global__ __launch_bounds__(256, 2) void hlinear_wgrad_kernel(const HLinearWgra
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t mm = h_plane_index((int64_t)mg0 * 8 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi, p.row_plane);
+        const int64_t mm = h_plane_index(mfma32_row(r, lhi, (int64_t)mg0 * 8 + wm * 64 + mi * 32), p.row_plane);
         old_values[mi][r] = mm < p.M_real ? p.gw[mm * p.ldw_m + kk * p.ldw_k] : 0.f;
       }
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t mm = h_plane_index((int64_t)mg0 * 8 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi, p.row_plane);
+        const int64_t mm = h_plane_index(mfma32_row(r, lhi, (int64_t)mg0 * 8 + wm * 64 + mi * 32), p.row_plane);
         if (mm < p.M_real) p.gw[mm * p.ldw_m + kk * p.ldw_k] = old_values[mi][r] + acc[mi][ni][r];
       }
   }

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void hconv2x2_kernel(const HConv2Params pp,
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int tm = block % p.tiles_m; block /= p.tiles_m;
   const int tx = block % p.tiles_x; block /= p.tiles_x;
   const int ty = block % p.tiles_y;
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256, 2) void hwgrad4x4s2_f32_kernel(const HWgrad4Pa
       for (int tap = 0; tap < 4; ++tap) {
         const float b = b_base[(origin + (tap >> 1) * PW + (tap & 1)) * 4];
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) acc[mi][tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b, acc[mi][tap], 0, 0, 0);
+        for (int mi = 0; mi < 2; ++mi) acc[mi][tap] = mfma32(a[mi], b, acc[mi][tap]);
       }
     }
   }
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(256, 2) void hwgrad4x4s2_f32_kernel(const HWgrad4Pa
 
 // One workgroup per (block, row k of the block): 32 columns c x 16 taps = 512 floats; element (c, kh, kw) of row k at
 // gw[k * sk + c * sc + kh * 4 + kw].  Wave = parity (qy, qx) of the producing kernel, so the reader of (kh, kw) looks into
-// wave 2 (kh & 1) + (kw & 1), tap 2 (kh >> 1) + (kw >> 1); C/D row k % 32 = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), column c = lane & 31.
+// wave 2 (kh & 1) + (kw & 1), tap 2 (kh >> 1) + (kw >> 1); C/D row k % 32 = mfma32_row(r, lane >> 5), column c = lane & 31.
 // The eight 32-lane groups of the workgroup take the walkers w = group, group + 8, ...: a lane adds its column of all sixteen
 // taps (sixteen independent 128-byte-run loads per walker), and the eight sums meet in a fixed tree -- the first version walked
 // up to 384 walkers serially in every thread (362 us for the three-channel first layer, profiles/r06l_*).
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(256) void hwgrad4x4s2_finish_kernel(const float* __
   const int k = tk * 64 + row;
   if (k >= K) return;
   const int64_t per_walker = 8 * 16 * 256;
-  const int mi = row >> 5, r32 = row & 31, lhi = (r32 >> 2) & 1, r = (r32 & 3) + 4 * (r32 >> 3);
+  const int mi = row >> 5, r32 = row & 31, lhi = mfma32_half(r32), r = mfma32_register(r32);
   const int c32 = (int)threadIdx.x & 31, part = (int)threadIdx.x >> 5;
   const float* base = partial + (int64_t)block * walkers * per_walker + lhi * 32 + c32;
   float total[16];

@@ -14,17 +14,15 @@
 // before the current chunk's 9 * CI_T / 2 * MI * NI MFMAs, so HBM latency hides under the matrix pipe.
 // Roofline: fp32 MFMA (157.3 TF/s); algorithmic work 2 * 9 * CI * CO FLOP per output pixel.
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "lds_dma.h"
+#include "precision_dispatch.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Conv3Params {
   const float* in;      // [N, CI, H, W] (batch stride in_bs)
@@ -52,10 +50,7 @@ struct Conv3Params {
   // other pixel of a 2H x 2W plane) and `taps` is the 9-bit mask of the window positions (kh * 3 + kw) that exist.
   int32_t out_plane, out_sy, out_sx, out_off;
   int32_t taps;
-  // XCD-aware order: hardware workgroup b runs on XCD b % 8, so logical tile = (b % 8) * (grid / 8) + b / 8 gives every
-  // XCD one contiguous band of tiles -- neighbouring tiles (which share halo rows / columns and the 128-byte lines of a
-  // 32-pixel tile row) then read them through ONE L2 instead of two (round 2 PMC: 1.9x the algorithmic bytes).
-  int32_t xcd_remap;
+  int32_t xcd_remap;    // the grid's workgroups take their tiles in xcd_band_order (mfma.h)
 };
 
 constexpr int CONV3_PRO_MAX_CI = 512;   // channels of one workgroup's K range whose (a, b) fit the LDS table
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = WIMG ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;      // (WIMG: scalar DMA bases)
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int logical_block = block;
   const int tm = block % p.tiles_m; block /= p.tiles_m;
   const int tx = block % p.tiles_x; block /= p.tiles_x;
@@ -254,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
           for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+              acc[mi][ni] = mfma32(a[mi], b[ni], acc[mi][ni]);
         }
       }
       if (WIMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the next chunk's slice (and patch registers) have arrived
@@ -298,11 +293,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int o = min(m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi, p.CO - 1);
+          const int o = min(mfma32_row(r, lhi, m0 + mi * 32), p.CO - 1);
           xs[ni][r] = x_n[(int64_t)o * HW + pix[ni]];
         }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // (= mfma32_row(r, lhi, mi * 32), written out: through the function the 16 EPI instantiations, and only they, come out
+        // with other LDS address registers -- profiles/mfma_layout.md)
         const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
         const int o = m0 + row;
         const float4 t = *reinterpret_cast<const float4*>(table + row * 4);
@@ -342,8 +339,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
     constexpr int COUNT = MI * NI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.split_ws + (int64_t)logical_block * gridDim.y * (COUNT * 256), (int)blockIdx.y,
                                           (int)gridDim.y, p.split_tickets + logical_block,
-                                          [&](int i) { return acc[i / (NI * 16)][(i / 16) % NI][i % 16]; },
-                                          [&](int i, float v) { acc[i / (NI * 16)][(i / 16) % NI][i % 16] = v; }))
+                                          acc_flat(acc), acc_flat(acc)))
       return;
     mode -= 3;
   }
@@ -360,19 +356,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_lds_kernel(const Conv3Params p
       if (mode == 1) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+          const int o = m0 + mi * 32 + mfma32_row(r, lhi);
           previous[r] = o < p.CO ? out_n[(int64_t)o * p.out_plane + y * p.out_sy + x * p.out_sx + p.out_off] : 0.f;
         }
       }
       float bias_values[16];                 // (in front of the stores, like the old values)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
         bias_values[r] = (add_bias && o < p.CO) ? p.bias[o] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
         if (o >= p.CO) continue;
         const float v = acc[mi][ni][r] + bias_values[r];
         float* dst = out_n + (int64_t)o * p.out_plane + y * p.out_sy + x * p.out_sx + p.out_off;
@@ -440,12 +436,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_kernel(const Conv3Params
   constexpr int MI = BM / 32, NI = TH / 4;
   constexpr int PATCH_Q = 2 * PHPW, WT_Q = 9 * 2 * BM, STAGE_Q = PATCH_Q + WT_Q;       // in 16-byte slots
   constexpr int NP = (PATCH_Q + 255) / 256, NW = (WT_Q + 255) / 256;
-  using frag = typename std::conditional<PREC == 1, bf16x8, f16x8>::type;
+  using frag = mfma_frag<PREC>;
   __shared__ Half8 lds[2 * STAGE_Q];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int logical_block = block;
   const int tm = block % p.tiles_m; block /= p.tiles_m;
   const int tx = block % p.tiles_x; block /= p.tiles_x;
@@ -542,10 +538,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_kernel(const Conv3Params
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            if constexpr (PREC == 1) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-            else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-          }
+          for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = mfma32<PREC>(a[mi], b[ni], acc[mi][ni]);
       }
       if (more) stage(c0 + 16, lds + (cur ^ 1) * STAGE_Q);     // the other stage: everyone left it at the previous barrier
       __syncthreads();
@@ -560,8 +553,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_kernel(const Conv3Params
     constexpr int COUNT = MI * NI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.split_ws + (int64_t)logical_block * gridDim.y * (COUNT * 256), (int)blockIdx.y,
                                           (int)gridDim.y, p.split_tickets + logical_block,
-                                          [&](int i) { return acc[i / (NI * 16)][(i / 16) % NI][i % 16]; },
-                                          [&](int i, float v) { acc[i / (NI * 16)][(i / 16) % NI][i % 16] = v; }))
+                                          acc_flat(acc), acc_flat(acc)))
       return;
     mode -= 3;
   }
@@ -574,7 +566,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_kernel(const Conv3Params
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
         if (o >= p.CO) continue;
         float v = acc[mi][ni][r];
         if (add_bias) v += p.bias[o];
@@ -600,12 +592,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_small_kernel(const Conv3
   constexpr int MI = BM / 32;
   constexpr int PATCH_Q = 2 * IMG * PHW, WT_Q = 9 * 2 * BM, STAGE_Q = PATCH_Q + WT_Q;       // in 16-byte slots
   constexpr int NP = (PATCH_Q + 255) / 256, NW = (WT_Q + 255) / 256;
-  using frag = typename std::conditional<PREC == 1, bf16x8, f16x8>::type;
+  using frag = mfma_frag<PREC>;
   __shared__ Half8 lds[2 * STAGE_Q];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
   int block = blockIdx.x;
-  if (p.xcd_remap) block = (block & 7) * ((int)gridDim.x >> 3) + (block >> 3);
+  if (p.xcd_remap) block = xcd_band_order(block, (int)gridDim.x);
   const int tm = block % p.tiles_m, n0 = (block / p.tiles_m) * IMG;
   const int m0 = tm * BM;
   const int cbeg = (int)blockIdx.y * p.ci_per_split;
@@ -694,10 +686,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_small_kernel(const Conv3
         for (int mi = 0; mi < MI; ++mi) a[mi] = *reinterpret_cast<const frag*>(&st[a_lane + tap * 2 * BM + mi * 32]);
         const frag b = *reinterpret_cast<const frag*>(&st[b_lane + kh * PW + kw]);
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          if constexpr (PREC == 1) acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b, acc[mi], 0, 0, 0);
-          else acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi], b, acc[mi], 0, 0, 0);
-        }
+        for (int mi = 0; mi < MI; ++mi) acc[mi] = mfma32<PREC>(a[mi], b, acc[mi]);
       }
       if (more) stage(c0 + 16, lds + (cur ^ 1) * STAGE_Q);     // the other stage: everyone left it at the previous barrier
       __syncthreads();
@@ -709,8 +698,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_small_kernel(const Conv3
   if (mode >= 3) {       // K split, ordered finish (split_finish.h)
     constexpr int COUNT = MI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.split_ws + (int64_t)block * gridDim.y * (COUNT * 256), (int)blockIdx.y, (int)gridDim.y,
-                                          p.split_tickets + block, [&](int i) { return acc[i / 16][i % 16]; },
-                                          [&](int i, float v) { acc[i / 16][i % 16] = v; }))
+                                          p.split_tickets + block, acc_flat(acc), acc_flat(acc)))
       return;
     mode -= 3;
   }
@@ -721,7 +709,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_small_kernel(const Conv3
   for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      const int o = m0 + mi * 32 + mfma32_row(r, lhi);
       if (o >= p.CO) continue;
       float v = acc[mi][r];
       if (add_bias) v += p.bias[o];
@@ -733,35 +721,35 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mixed_small_kernel(const Conv3
   }
 }
 
-template <int BM, int CI_T, int TW, int TAPS>
-static void launch_conv3_plain(const Conv3Params& p, int th, dim3 grid, hipStream_t stream) {
-  if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, false, TAPS>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, false, TAPS>), grid, dim3(256), 0, stream, p);
+// for_precision's shape (precision_dispatch.h) for a tile parameter: functor(std::integral_constant<int, V>{}) for the listed V
+// that equals `value`, and for the LAST listed one when none does (the narrower tile; the full window for any other tap mask).
+template <int FIRST, int... REST, class Functor>
+static void for_listed_or_last(int value, Functor&& functor) {
+  if constexpr (sizeof...(REST) == 0) functor(std::integral_constant<int, FIRST>{});
+  else if (value == FIRST) functor(std::integral_constant<int, FIRST>{});
+  else for_listed_or_last<REST...>(value, functor);
 }
+// the full window, or one of the four 2x2 sub-windows of a stride-2 transposed convolution
+template <class Functor>
+static void for_tap_mask(int taps, Functor&& functor) { for_listed_or_last<0x01B, 0x036, 0x0D8, 0x1B0, 0x1FF>(taps, functor); }
 
 template <int BM, int CI_T, int TW>
 static void launch_conv3_w(const Conv3Params& p, int th, dim3 grid, hipStream_t stream) {
-  if (p.w_packed && p.epi_x) {          // the weight image: the two fused forms of the dense layers (conv3x3_run admits no other)
-    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true, 0x1FF, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true, 0x1FF, true>), grid, dim3(256), 0, stream, p);
-  } else if (p.w_packed) {
-    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, true, TW, false, 0x1FF, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, true, TW, false, 0x1FF, true>), grid, dim3(256), 0, stream, p);
-  } else if (p.epi_x) {
-    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
-  } else if (p.bn_mean) {
-    if (th == 8) hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 8, CI_T, true, TW>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_lds_kernel<BM, 4, CI_T, true, TW>), grid, dim3(256), 0, stream, p);
-  } else {
-    switch (p.taps) {            // the full window, or one of the four 2x2 sub-windows of a stride-2 transposed convolution
-      case 0x01B: launch_conv3_plain<BM, CI_T, TW, 0x01B>(p, th, grid, stream); break;
-      case 0x036: launch_conv3_plain<BM, CI_T, TW, 0x036>(p, th, grid, stream); break;
-      case 0x0D8: launch_conv3_plain<BM, CI_T, TW, 0x0D8>(p, th, grid, stream); break;
-      case 0x1B0: launch_conv3_plain<BM, CI_T, TW, 0x1B0>(p, th, grid, stream); break;
-      default: launch_conv3_plain<BM, CI_T, TW, 0x1FF>(p, th, grid, stream); break;
-    }
-  }
+  for_listed_or_last<8, 4>(th, [&](auto rows) {
+    constexpr int TH = decltype(rows)::value;
+    if (p.w_packed && p.epi_x)            // the weight image: the two fused forms of the dense layers (conv3x3_run admits no other)
+      hipLaunchKernelGGL((conv3x3_lds_kernel<BM, TH, CI_T, false, TW, true, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+    else if (p.w_packed)
+      hipLaunchKernelGGL((conv3x3_lds_kernel<BM, TH, CI_T, true, TW, false, 0x1FF, true>), grid, dim3(256), 0, stream, p);
+    else if (p.epi_x)
+      hipLaunchKernelGGL((conv3x3_lds_kernel<BM, TH, CI_T, false, TW, true>), grid, dim3(256), 0, stream, p);
+    else if (p.bn_mean)
+      hipLaunchKernelGGL((conv3x3_lds_kernel<BM, TH, CI_T, true, TW>), grid, dim3(256), 0, stream, p);
+    else
+      for_tap_mask(p.taps, [&](auto taps) {
+        hipLaunchKernelGGL((conv3x3_lds_kernel<BM, TH, CI_T, false, TW, false, decltype(taps)::value>), grid, dim3(256), 0, stream, p);
+      });
+  });
 }
 
 template <int BM, int CI_T>
@@ -770,43 +758,26 @@ static void launch_conv3(const Conv3Params& p, int th, int tw, dim3 grid, hipStr
   else launch_conv3_w<BM, CI_T, 32>(p, th, grid, stream);
 }
 
-template <int BM, int PREC, int TAPS>
-static void launch_conv3_mixed_taps(const Conv3Params& p, int th, int tw, dim3 grid, hipStream_t stream) {
-  if (tw == 16) hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 4, 16, PREC, TAPS>), grid, dim3(256), 0, stream, p);
-  else if (th == 8) hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 8, 32, PREC, TAPS>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 4, 32, PREC, TAPS>), grid, dim3(256), 0, stream, p);
-}
-
-template <int BM, int PREC>
-static void launch_conv3_mixed_bm(const Conv3Params& p, int th, int tw, dim3 grid, hipStream_t stream) {
-  switch (p.taps) {
-    case 0x01B: launch_conv3_mixed_taps<BM, PREC, 0x01B>(p, th, tw, grid, stream); break;
-    case 0x036: launch_conv3_mixed_taps<BM, PREC, 0x036>(p, th, tw, grid, stream); break;
-    case 0x0D8: launch_conv3_mixed_taps<BM, PREC, 0x0D8>(p, th, tw, grid, stream); break;
-    case 0x1B0: launch_conv3_mixed_taps<BM, PREC, 0x1B0>(p, th, tw, grid, stream); break;
-    default: launch_conv3_mixed_taps<BM, PREC, 0x1FF>(p, th, tw, grid, stream); break;
-  }
+static void launch_conv3_mixed(const Conv3Params& p, int bm, int th, int tw, int precision, dim3 grid, hipStream_t stream) {
+  for_precision<1, 2>(precision, [&](auto code) {
+    for_listed_or_last<64, 32>(bm, [&](auto rows) {
+      for_tap_mask(p.taps, [&](auto taps) {
+        constexpr int PREC = decltype(code)::value, BM = decltype(rows)::value, TAPS = decltype(taps)::value;
+        if (tw == 16) hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 4, 16, PREC, TAPS>), grid, dim3(256), 0, stream, p);
+        else if (th == 8) hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 8, 32, PREC, TAPS>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((conv3x3_mixed_kernel<BM, 4, 32, PREC, TAPS>), grid, dim3(256), 0, stream, p);
+      });
+    });
+  });
 }
 
 template <int P>
 static void launch_conv3_mixed_small(const Conv3Params& p, int bm, int precision, dim3 grid, hipStream_t stream) {
-  if (precision == 1) {
-    if (bm == 64) hipLaunchKernelGGL((conv3x3_mixed_small_kernel<64, P, 1>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_mixed_small_kernel<32, P, 1>), grid, dim3(256), 0, stream, p);
-  } else {
-    if (bm == 64) hipLaunchKernelGGL((conv3x3_mixed_small_kernel<64, P, 2>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv3x3_mixed_small_kernel<32, P, 2>), grid, dim3(256), 0, stream, p);
-  }
-}
-
-static void launch_conv3_mixed(const Conv3Params& p, int bm, int th, int tw, int precision, dim3 grid, hipStream_t stream) {
-  if (precision == 1) {
-    if (bm == 64) launch_conv3_mixed_bm<64, 1>(p, th, tw, grid, stream);
-    else launch_conv3_mixed_bm<32, 1>(p, th, tw, grid, stream);
-  } else {
-    if (bm == 64) launch_conv3_mixed_bm<64, 2>(p, th, tw, grid, stream);
-    else launch_conv3_mixed_bm<32, 2>(p, th, tw, grid, stream);
-  }
+  for_precision<1, 2>(precision, [&](auto code) {
+    for_listed_or_last<64, 32>(bm, [&](auto rows) {
+      hipLaunchKernelGGL((conv3x3_mixed_small_kernel<decltype(rows)::value, P, decltype(code)::value>), grid, dim3(256), 0, stream, p);
+    });
+  });
 }
 
 // Tile choice: the widest output-channel tile (fewest re-reads of the input patch) and the 8-row pixel tile, as long
@@ -958,8 +929,9 @@ int conv3x3_run(const float* in, int64_t in_bs, const Conv3Weights& weights, con
     Half8* packed = reinterpret_cast<Half8*>(partial_workspace((size_t)slots * sizeof(Half8), stream));
     SRGAN_REQUIRE(packed, SRGAN_EINVAL, "conv3x3 mixed precision: register a workspace for this stream first "
                   "(srgan_set_workspace, >= srgan_workspace_bytes(); the packed weights take 2 bytes per element)");
-    if (precision == 1) hipLaunchKernelGGL(conv3x3_pack_weights_kernel<1>, dim3((slots + 255) / 256), dim3(256), 0, stream, p, packed, slots);
-    else hipLaunchKernelGGL(conv3x3_pack_weights_kernel<2>, dim3((slots + 255) / 256), dim3(256), 0, stream, p, packed, slots);
+    for_precision<1, 2>(precision, [&](auto code) {
+      hipLaunchKernelGGL(conv3x3_pack_weights_kernel<decltype(code)::value>, dim3((slots + 255) / 256), dim3(256), 0, stream, p, packed, slots);
+    });
     p.w_packed = packed;
     if (plan.small && W == 4) launch_conv3_mixed_small<4>(p, bm, precision, grid, stream);
     else if (plan.small) launch_conv3_mixed_small<8>(p, bm, precision, grid, stream);

@@ -13,6 +13,7 @@
 // (raw loads from clamped addresses; the validity mask is applied when the registers are written to LDS -- a use of
 // the loaded value before the MFMA loop would make the compiler wait for the loads there).
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
@@ -20,10 +21,6 @@
 #include <type_traits>
 
 namespace srgan {
-
-using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Wgrad3Params {
   const float* x; const float* gy; float* gw;
@@ -258,7 +255,7 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const Wgrad3Params& p, const 
     if (next < p.tiles) fetch(next);
 
     if constexpr (PREC != 0) {
-      using frag = typename std::conditional<PREC == 1, bf16x8, f16x8>::type;
+      using frag = mfma_frag<PREC>;
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
       const half_t* a16 = gs16 + l31 * GC + 8 * lhi;
       const half_t* b16 = xs16 + l31 * XC + kh * XW + 8 * lhi;
@@ -278,15 +275,9 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const Wgrad3Params& p, const 
           w2[i] = d[i + 1];
         }
         const frag b0 = __builtin_bit_cast(frag, w0), b1 = __builtin_bit_cast(frag, w1), b2 = __builtin_bit_cast(frag, w2);
-        if constexpr (PREC == 1) {
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc[1], 0, 0, 0);
-          acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b2, acc[2], 0, 0, 0);
-        } else {
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b0, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b1, acc[1], 0, 0, 0);
-          acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b2, acc[2], 0, 0, 0);
-        }
+        acc[0] = mfma32<PREC>(a, b0, acc[0]);
+        acc[1] = mfma32<PREC>(a, b1, acc[1]);
+        acc[2] = mfma32<PREC>(a, b2, acc[2]);
       }
     } else
 #pragma unroll 1
@@ -297,14 +288,14 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const Wgrad3Params& p, const 
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           const float b = b_base[h * PW + w + kw];
-          acc[kw] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[kw], 0, 0, 0);
+          acc[kw] = mfma32(a, b, acc[kw]);
         }
       }
     }
   }
 
-  // ---- one atomic pass per workgroup.  C/D fragment: column = lane & 31 (ci), row = (r & 3) + 8 * (r >> 2) +
-  // 4 * (lane >> 5) (co).  In that layout a wave's lanes are 36 bytes apart in gw (one L2 atomic transaction per
+  // ---- one atomic pass per workgroup.  C/D fragment: column = lane & 31 (ci), row = mfma32_row(r, lane >> 5)
+  // (co).  In that layout a wave's lanes are 36 bytes apart in gw (one L2 atomic transaction per
   // lane: measured 630 us per launch), so the 32 x 288 block is transposed through LDS and the atomics go out with
   // lanes along the contiguous (ci, tap) run of each output-channel row.
   const int run = min(WG3_CI, p.CI - ci0) * 9;       // valid floats of each row

@@ -19,14 +19,14 @@
 //               operand layout of a second MFMA over k = j -- multiplied into Z_j for the wave's 128 examples, then the
 //               row-wise epilogue dX = 2 g / ||xm_i|| * ((G Z)_i - r_i z_i)
 // The tile T[j][i] = sum_b Z[j][b] Z[i][b] takes Z_j as the A operand and Z_i as the B operand: lane l then holds column
-// i = l & 31 and rows j = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
+// i = l & 31 and rows j = mfma32_row(reg, l >> 5).
 #include <math.h>
 #include "common.h"
+#include "mfma.h"
 
 namespace srgan {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FL_TILE = 32;              // features per wave
 constexpr int FL_GROUP = 128;            // features per workgroup (four waves)
@@ -126,22 +126,22 @@ __device__ __forceinline__ void gram_tiles(const float* __restrict__ zb, const f
     const float4 b0 = *reinterpret_cast<const float4*>(bb + k0), b1 = *reinterpret_cast<const float4*>(bb + k0 + 4);
     const float4 c0 = *reinterpret_cast<const float4*>(ao + k0), c1 = *reinterpret_cast<const float4*>(ao + k0 + 4);
     const float4 d0 = *reinterpret_cast<const float4*>(bo + k0), d1 = *reinterpret_cast<const float4*>(bo + k0 + 4);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c0.x, d0.x, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c0.y, d0.y, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c0.z, d0.z, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c0.w, d0.w, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c1.x, d1.x, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c1.y, d1.y, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c1.z, d1.z, to, 0, 0, 0);
-    tb = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, tb, 0, 0, 0);
-    to = __builtin_amdgcn_mfma_f32_32x32x2f32(c1.w, d1.w, to, 0, 0, 0);
+    tb = mfma32(a0.x, b0.x, tb);
+    to = mfma32(c0.x, d0.x, to);
+    tb = mfma32(a0.y, b0.y, tb);
+    to = mfma32(c0.y, d0.y, to);
+    tb = mfma32(a0.z, b0.z, tb);
+    to = mfma32(c0.z, d0.z, to);
+    tb = mfma32(a0.w, b0.w, tb);
+    to = mfma32(c0.w, d0.w, to);
+    tb = mfma32(a1.x, b1.x, tb);
+    to = mfma32(c1.x, d1.x, to);
+    tb = mfma32(a1.y, b1.y, tb);
+    to = mfma32(c1.y, d1.y, to);
+    tb = mfma32(a1.z, b1.z, tb);
+    to = mfma32(c1.z, d1.z, to);
+    tb = mfma32(a1.w, b1.w, tb);
+    to = mfma32(c1.w, d1.w, to);
   }
 }
 
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void feature_gram_fwd_kernel(const float* __re
       gram_tiles(zb, zo, Bp, j0, i0, c, h, tb, to);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t j = j0 + mfma32_row(r, h);
         if (j < F && i < F && j != i) {
           float d, gb, go;
           entry_terms(tb[r], to[r], d, gb, go);
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void feature_gram_bwd_kernel(const float* __re
     float gv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int64_t j = j0 + mfma32_row(r, h);
       float d, gb, go;
       entry_terms(tb[r], to[r], d, gb, go);
       gv[r] = (j < F && i < F && j != i) ? (SIDE ? go : gb) : 0.f;
@@ -257,8 +257,8 @@ __global__ __launch_bounds__(256) void feature_gram_bwd_kernel(const float* __re
       if (bq < Bp) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int64_t j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          p[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(zs[j * Bp + bq + c], gv[r], p[q], 0, 0, 0);
+          const int64_t j = j0 + mfma32_row(r, h);
+          p[q] = mfma32(zs[j * Bp + bq + c], gv[r], p[q]);
         }
       }
     }
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void feature_gram_bwd_kernel(const float* __re
   for (int q = 0; q < FL_BWD_CHUNKS; ++q)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t b = b_first + 32 * q + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int64_t b = b_first + 32 * q + mfma32_row(r, h);
       if (b < B) {
         const float z = (x[b * F + i] - mean) * inv;
         grad[b * F + i] = factor * (p[q][r] - r_i * z);

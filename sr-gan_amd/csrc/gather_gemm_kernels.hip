@@ -12,6 +12,7 @@
 // Roofline (MI355X_MICROARCH.md): fp32 MFMA 157.3 TF/s; the gather adds ~30 VALU ops per staged element,
 // which overlaps with the 64-cycle MFMAs of the other waves on the SIMD.
 #include "common.h"
+#include "mfma.h"
 #include "split_finish.h"
 #include "gather_gemm.h"
 #include "conv_plan.h"
@@ -21,10 +22,6 @@
 #include <vector>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GG_BK = 32;   // K-slice alignment of split-K chunks (the largest per-config BK)
 
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
       if (more) fetch(k0 + BK);
       if constexpr (PREC != 0) {
         static_assert(PREC == 0 || BK % 16 == 0, "16-deep MFMA steps");
-        using frag = typename std::conditional<PREC == 1, bf16x8, f16x8>::type;
+        using frag = mfma_frag<PREC>;
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 16) {
           frag a[MI], b[NI];                   // one ds_read_b128 each: 8 consecutive k of this lane's row / column
@@ -239,10 +236,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              if constexpr (PREC == 1) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-              else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-            }
+            for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = mfma32<PREC>(a[mi], b[ni], acc[mi][ni]);
         }
       } else
 #pragma unroll
@@ -256,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = mfma32(a[mi], b[ni], acc[mi][ni]);
       }
       __syncthreads();
       if (more) {
@@ -266,14 +260,13 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
     }
   }
 
-  // Epilogue: C/D fragment of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
+  // Epilogue: C/D fragment of the 32x32 MFMA: column = lane & 31, row = mfma32_row(r, lane >> 5).
   int mode = p.mode;
   if (mode >= GG_ORDERED_STORE) {     // K split, ordered finish: the tile's last workgroup goes on with the sum of all slices
     constexpr int COUNT = MI * NI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.partial + (int64_t)blockIdx.x * gridDim.y * (COUNT * 256), (int)blockIdx.y,
                                           (int)gridDim.y, p.tickets + blockIdx.x,
-                                          [&](int i) { return acc[i / (NI * 16)][(i / 16) % NI][i % 16]; },
-                                          [&](int i, float v) { acc[i / (NI * 16)][(i / 16) % NI][i % 16] = v; }))
+                                          acc_flat(acc), acc_flat(acc)))
       return;
     mode -= GG_ORDERED_STORE;
   }
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const Side sm = decode(p.cm, m0 + wm0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi);
+      const Side sm = decode(p.cm, mfma32_row(r, lhi, m0 + wm0 + mi * 32));
       row_bias_all[mi][r] = (add_bias && !p.bias_cols && sm.valid) ? p.bias[sm.c] : 0.f;
     }
 #pragma unroll
@@ -303,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
       if (mode == GG_ACCUMULATE) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-          const int i = m0 + wm0 + mi * 32 + rr + 8 * rq + 4 * lhi;
+          const int i = mfma32_row(4 * rq + rr, lhi, m0 + wm0 + mi * 32);
           const Side sm = decode(p.cm, i);
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
@@ -313,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void gg_mfma_kernel(const GatherGemm p) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int r = 4 * rq + rr;
-        const int i = m0 + wm0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int i = mfma32_row(r, lhi, m0 + wm0 + mi * 32);
         const Side sm = decode(p.cm, i);
         if (!sm.valid) continue;
         const float row_bias = row_bias_all[mi][r];

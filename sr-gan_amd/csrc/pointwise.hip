@@ -19,14 +19,13 @@
 //     half-wave); in a data gradient the batch-norm + ReLU backward of the layer in front is applied on the way (EPI).
 // Roofline: fp32 MFMA 157.3 TF/s, or HBM when CI is small; algorithmic bytes 4 * (CI + CO) per pixel.
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PointwiseParams {
   const float* in;      // [N, CI, HW], batch stride in_bs
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
   // while the row tiles that share one activation column block have consecutive LOGICAL ids -- so logical id =
   // (hardware id % 8) * (grid / 8) + hardware id / 8 keeps them on one XCD and the activations are fetched into one L2.
   int bid = (int)blockIdx.x;
-  if (p.xcd_remap) bid = (bid & 7) * ((int)gridDim.x >> 3) + (bid >> 3);
+  if (p.xcd_remap) bid = xcd_band_order(bid, (int)gridDim.x);
   const int tm = bid % p.tiles_m;
   // Pixel groups never straddle images: an image has gpi = ceil(HW / (32 * NI)) groups, the last one ragged when HW is
   // not a multiple of the group (14 x 14 and 7 x 7 planes of the 224-pixel configuration): its surplus lanes read a
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q & 1][mi], bq[ni], acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = mfma32(a[q & 1][mi], bq[ni], acc[mi][ni]);
       {   // unconditional (clamped) so that the slice stays one basic block; the last slice's loads are unused
         const int k = min(k0 + BK + 2 * q, kend - 2);
 #pragma unroll
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        tile[(mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDT + wave * 32 + l31] = acc[mi][0][r];
+        tile[(mi * 32 + mfma32_row(r, lhi)) * LDT + wave * 32 + l31] = acc[mi][0][r];
     if (tid < BM) {
       const int o = min(m0 + tid, p.CO - 1);
       const float mu = p.bn_mean[o];
@@ -319,8 +318,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
   if (mode >= 3) {       // K split, ordered finish (split_finish.h): the tile's last workgroup goes on with the sum of all slices
     constexpr int COUNT = MI * NI * 16;
     if (!split_finish_ordered<COUNT, 256>(p.split_ws + (int64_t)bid * gridDim.y * (COUNT * 256), (int)blockIdx.y, (int)gridDim.y,
-                                          p.split_tickets + bid, [&](int i) { return acc[i / (NI * 16)][(i / 16) % NI][i % 16]; },
-                                          [&](int i, float v) { acc[i / (NI * 16)][(i / 16) % NI][i % 16] = v; }))
+                                          p.split_tickets + bid, acc_flat(acc), acc_flat(acc)))
       return;
     mode -= 3;
   }
@@ -333,7 +331,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        tile[(mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDT + wave * 32 + l31] = acc[mi][0][r];
+        tile[(mi * 32 + mfma32_row(r, lhi)) * LDT + wave * 32 + l31] = acc[mi][0][r];
     __syncthreads();
     constexpr int RPT = BM / 8;
     const int half = tid >> 5, q4 = (tid & 31) * 4;
@@ -375,7 +373,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
         if (o >= p.CO) continue;
         const float bias = add_bias ? p.bias[o] : 0.f;
 #pragma unroll
@@ -396,7 +394,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
       float previous[16][NI];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
           bool ok = o < p.CO;
@@ -406,7 +404,7 @@ __global__ __launch_bounds__(256, MI * NI >= 4 ? 2 : 4) void pointwise_kernel(co
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = m0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int o = m0 + mi * 32 + mfma32_row(r, lhi);
         if (o >= p.CO) continue;
         const float bias = add_bias ? p.bias[o] : 0.f;
 #pragma unroll

@@ -12,12 +12,11 @@
 // the next chunk is in flight while the current one is in the matrix pipe.  The four partial tiles are summed through
 // LDS at the end.  No memset, no atomics, the activations are read twice (once per 64-row tile of 128 rows).
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include <stdlib.h>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PwKsplitParams {
   const float* in;      // [N, K, HW], batch stride in_bs
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ksplit_kernel(const PwKsplit
       for (int mi = 0; mi < MI; ++mi) {
         const float4 v = a[mi][s >> 2];
         const float av = (s & 3) == 0 ? v.x : ((s & 3) == 1 ? v.y : ((s & 3) == 2 ? v.z : v.w));
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[mi], 0, 0, 0);
+        acc[mi] = mfma32(av, bv, acc[mi]);
       }
     }
   };
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ksplit_kernel(const PwKsplit
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) mine[(mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDR + l31] = acc[mi][r];
+    for (int r = 0; r < 16; ++r) mine[(mi * 32 + mfma32_row(r, lhi)) * LDR + l31] = acc[mi][r];
   __syncthreads();
   float* out_n = p.out + (int64_t)n * p.out_bs + pix0;
 #pragma unroll

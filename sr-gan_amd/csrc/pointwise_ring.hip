@@ -26,16 +26,13 @@
 // Roofline: fp32 MFMA 157.3 TF/s; algorithmic bytes 4 * (CI + CO) per pixel (+ the epilogue streams of a fused data
 // gradient).
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "lds_dma.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct RingParams {
   const float* in;      // [N, CI, HW], batch stride in_bs
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bid = (int)blockIdx.x;
-  if (p.xcd_remap) bid = (bid & 7) * ((int)gridDim.x >> 3) + (bid >> 3);     // the row tiles of a pixel block on one XCD
+  if (p.xcd_remap) bid = xcd_band_order(bid, (int)gridDim.x);     // the row tiles of a pixel block on one XCD
   const int tm = bid % p.tiles_m, cb = bid / p.tiles_m;
   const int n = cb / p.bpi, pix0 = (cb - n * p.bpi) * (32 * NI);
   const int m0 = tm * 128;
@@ -221,12 +218,12 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
         for (int ni = 0; ni < NI; ++ni) b[ni] = f.b[q][ni];
       }
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[q], b[ni], acc[ni], 0, 0, 0);
+      for (int ni = 0; ni < NI; ++ni) acc[ni] = mfma32(f.a[q], b[ni], acc[ni]);
     }
   };
 
   // ---- epilogue operands ----
-  const int64_t row0 = m0 + 32 * wave + 4 * lhi;                       // + (r & 3) + 8 * (r >> 2)
+  const int64_t row0 = m0 + 32 * wave + 4 * lhi;                       // + mfma32_row(r, 0)
   float* out_lane = p.out + (int64_t)n * p.out_bs + row0 * p.HW + pix0 + NI * l31;
   // FUSE 2: the epilogue's own streams -- x for the mask, the accumulated gradient -- are requested while the K loop runs
   // (after the stage-1 / stage-2 DMAs: 128 registers that this kernel has to spare at two workgroups per CU).  The pass
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
       return lhi;
     }
   };
-  // row r of the lane (local row (r & 3) + 8 * (r >> 2) of the wave): its table entry and its masked accumulators
+  // row r of the lane (local row mfma32_row(r, 0) of the wave): its table entry and its masked accumulators
   auto masked_row = [&](const float* rows, int half, int r, int local, f32x4& t) {
     t = *reinterpret_cast<const f32x4*>(rows + (32 * wave + 4 * half + local) * 4);
     const f32x4 x = xs[r];
@@ -325,11 +322,11 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
     if constexpr (FUSE == 2) {
       if (prefetch && t == 0) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) xs[r] = *x_row((r & 3) + 8 * (r >> 2));
+        for (int r = 0; r < 16; ++r) xs[r] = *x_row(mfma32_row(r, 0));
       }
       if (prefetch && t == 1 && accumulate) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) olds[r] = *out_row((r & 3) + 8 * (r >> 2));
+        for (int r = 0; r < 16; ++r) olds[r] = *out_row(mfma32_row(r, 0));
       }
     }
     if (!active) continue;
@@ -353,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
         const int half = epilogue_half();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int local = (r & 3) + 8 * (r >> 2);
+          const int local = mfma32_row(r, 0);
           f32x4 e;
           const f32x4 v = masked_row(table_first, half, r, local, e);
           olds[r] = scaled_add(v, e.x, olds[r]);
@@ -381,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
         if (!PAIR && !prefetch) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            xs[4 * batch + e] = *x_row(e + 8 * batch);                   // r = 4 * batch + e: row (r & 3) + 8 * (r >> 2)
+            xs[4 * batch + e] = *x_row(mfma32_row(4 * batch + e, 0));
             if constexpr (decltype(accumulating)::value) olds[4 * batch + e] = *out_row(e + 8 * batch);
           }
         }
@@ -414,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
     float previous[16][NI];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float* src = out_lane + (int64_t)((r & 3) + 8 * (r >> 2)) * p.HW;
+      const float* src = out_lane + (int64_t)mfma32_row(r, 0) * p.HW;
       if constexpr (NI == 4) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(src);
         previous[r][0] = v.x; previous[r][1] = v.y; previous[r][2] = v.z; previous[r][3] = v.w;
@@ -427,7 +424,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      float* dst = out_lane + (int64_t)((r & 3) + 8 * (r >> 2)) * p.HW;
+      float* dst = out_lane + (int64_t)mfma32_row(r, 0) * p.HW;
       if constexpr (NI == 4) {
         f32x4 v;
         v.x = previous[r][0] + acc[0][r]; v.y = previous[r][1] + acc[1][r]; v.z = previous[r][2] + acc[2][r]; v.w = previous[r][3] + acc[3][r];
@@ -444,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_ring_kernel(const RingParams
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    float* dst = out_lane + (int64_t)((r & 3) + 8 * (r >> 2)) * p.HW;
+    float* dst = out_lane + (int64_t)mfma32_row(r, 0) * p.HW;
     if constexpr (NI == 4) {
       f32x4 v;
       v.x = acc[0][r]; v.y = acc[1][r]; v.z = acc[2][r]; v.w = acc[3][r];

@@ -27,6 +27,7 @@
 // chunk and row block); rows are 128 bytes = half a 256-byte bank row, 16-byte slots XOR-swizzled by the bank-row index
 // (applied to the DMA's source addresses, as in pointwise_ring.hip) -- conflict-free.
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "lds_dma.h"
 #include "split_finish.h"
@@ -34,9 +35,6 @@
 #include <string.h>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PwWgradParams {
   const float* x; const float* gy; float* gw;
@@ -140,7 +138,7 @@ __device__ __forceinline__ void pointwise_wgrad_body(const PwWgradParams& p, con
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi], bv[ni], acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = mfma32(av[mi], bv[ni], acc[mi][ni]);
       }
     }
   };
@@ -158,10 +156,10 @@ __device__ __forceinline__ void pointwise_wgrad_body(const PwWgradParams& p, con
   }
 
   // ---- sum the four waves' tiles through LDS, then one coalesced pass out.  C/D fragment: column = lane & 31, row =
-  // (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).  Two LDS tiles: waves 2, 3 deposit, waves 0, 1 add them to their
+  // mfma32_row(r, lane >> 5).  Two LDS tiles: waves 2, 3 deposit, waves 0, 1 add them to their
   // registers and deposit the pair sums, all 256 threads add the two tiles.
   float* mine = red + (wave & 1) * (ROWS * LDR);
-  auto at = [&](int mi, int ni, int r) { return (mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDR + ni * 32 + l31; };
+  auto at = [&](int mi, int ni, int r) { return (mi * 32 + mfma32_row(r, lhi)) * LDR + ni * 32 + l31; };
   if (wave >= 2) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
@@ -329,7 +327,7 @@ __device__ __forceinline__ void pointwise_wgrad_lds_body(const PwWgradParams& p,
       for (int ni = 0; ni < NI; ++ni) {
         float bv = f.b[ni][e];
         if (PRO) bv = fmaxf(fmaf(bv, pro_a[ni], pro_b[ni]), 0.f);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[e], bv, acc[ni], 0, 0, 0);
+        acc[ni] = mfma32(f.a[e], bv, acc[ni]);
       }
     }
   };
@@ -372,14 +370,14 @@ __device__ __forceinline__ void pointwise_wgrad_lds_body(const PwWgradParams& p,
   }
   if (!active) return;
 
-  // C/D fragment: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5): half a wave writes 128 contiguous bytes
+  // C/D fragment: column = lane & 31, row = mfma32_row(r, lane >> 5): half a wave writes 128 contiguous bytes
   const int row0 = 32 * wave + 4 * lhi;
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int col = 32 * ni + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = row0 + (r & 3) + 8 * (r >> 2);
+      const int row = row0 + mfma32_row(r, 0);
       const float v = acc[ni][r];
       if (p.partial) {
         p.partial[((int64_t)block_x * p.split + block_y) * (PWL_TILE * PWL_TILE) + row * PWL_TILE + col] = v;

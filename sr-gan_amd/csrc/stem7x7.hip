@@ -14,13 +14,12 @@
 //             atomic pass per workgroup.
 // Roofline: fp32 MFMA (157.3 TF/s): 2 * 147 * 64 FLOP per output pixel, against 4 * (3 * 4 + 64) B of HBM traffic.
 #include "common.h"
+#include "mfma.h"
 #include "launchers.h"
 #include "split_finish.h"
 #include <stdlib.h>
 
 namespace srgan {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct StemParams {
   const float* x;      // [N, 3, H, W], batch stride x_bs
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_fwd_kernel(const StemParams p)
           const float b = b_base[c * (ST_PH * ST_PW) + kh * ST_PW + 2 * kp];
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi)
-            acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_base[k * LDA + mi * 32], b, acc[mi], 0, 0, 0);
+            acc[mi] = mfma32(a_base[k * LDA + mi * 32], b, acc[mi]);
         }
       }
     }
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_fwd_kernel(const StemParams p)
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int co = mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * lhi;
+          const int co = mi * 32 + mfma32_row(q, lhi);
           if (co < p.K) __builtin_nontemporal_store(acc[mi][q], yn + (int64_t)co * p.OH * p.OW);
         }
     }
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wgrad_kernel(const StemParams 
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int nj = 0; nj < ST_NJ; ++nj)
-          acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[nj], acc[mi][nj], 0, 0, 0);
+          acc[mi][nj] = mfma32(a[mi], b[nj], acc[mi][nj]);
     }
   }
   // The four waves hold partial sums over different pixel rows of the same [co][weight position] tile: they are summed
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wgrad_kernel(const StemParams 
         for (int nj = 0; nj < ST_NJ; ++nj)
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            float* slot = red + (mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * lhi) * LDR + nj * 32 + l31;
+            float* slot = red + (mi * 32 + mfma32_row(q, lhi)) * LDR + nj * 32 + l31;
             *slot = turn == 0 ? acc[mi][nj][q] : *slot + acc[mi][nj][q];
           }
     }

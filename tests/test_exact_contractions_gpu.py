@@ -1,4 +1,5 @@
-"""Every fp32 contraction kernel path on exact operands, bit for bit against float64.
+"""Every fp32 contraction kernel path (and the mixed-precision 3x3 kernels' store modes) on exact operands, bit for bit
+against float64.
 
 Operands are small integers (x, gy in [-3, 3], weights in [-2, 2], biases in [-4, 4]) or dyadic values of a few bits (the fused
 batch-norm activations are quarter steps).  Every partial sum stays below 2^(24 - f) in magnitude, f = the operands' fractional
@@ -87,10 +88,11 @@ def assert_limit(magnitude, fraction_bits, what):
 
 
 # ------------------------------------------------------------------------------------------------- convolutions
-def desc_of(shape, x_batch_stride=0, y_batch_stride=0):
+def desc_of(shape, x_batch_stride=0, y_batch_stride=0, compute_dtype=0):
     n, c, h, w, k, r, s, stride, pad = shape
     oh, ow = (h + 2 * pad[0] - r) // stride[0] + 1, (w + 2 * pad[1] - s) // stride[1] + 1
-    return _abi().ConvDesc(n, c, h, w, k, r, s, stride[0], stride[1], pad[0], pad[1], oh, ow, x_batch_stride, y_batch_stride, 0)
+    return _abi().ConvDesc(n, c, h, w, k, r, s, stride[0], stride[1], pad[0], pad[1], oh, ow, x_batch_stride, y_batch_stride,
+                           compute_dtype)
 
 
 @functools.lru_cache(maxsize=1)
@@ -162,6 +164,45 @@ def test_convolution_passes_are_exact(lib, entry, force):
         report.assert_reached(entry.reach, entry.split, what)
     else:                                   # the cross-checks run the generic kernels only: direct (1) or MFMA (2)
         assert report.kinds == {0 if force == 1 else 1}, f'{what}: launched {sorted(report.kinds)}\n{report.text}'
+
+
+# The two mixed-precision 3x3 kernels of conv3x3.hip (a tile of one image; whole 4 x 4 / 8 x 8 images side by side) with
+# bf16 / fp16 operands, which hold the integers above exactly: (n, c, h, w, k, the data gradient's K slices).  Only the data
+# gradient has an accumulate argument, and its reduction runs over k: the shapes with k <= 48 (fewer than four 16-channel
+# chunks) stay unsplit -- store and accumulate --, the others split K -- ordered finish storing and accumulating here,
+# fp32 atomics onto the live output in the re-run below.  Small planes: 16 chunks on 8 workgroups; a ragged image group
+# (19 images, 8 per workgroup) with channel tails, split and (c and k swapped) unsplit.  Tiles: the 16-wide tile; channel
+# tails on a 7-wide plane, split and unsplit.
+MIXED_3X3_CASES = [(32, 256, 4, 4, 128, True), (19, 40, 4, 4, 72, True), (19, 72, 4, 4, 40, False),
+                   (2, 64, 16, 16, 64, True), (1, 130, 9, 7, 70, True), (1, 130, 9, 7, 40, False)]
+
+
+@pytest.mark.parametrize('dtype', [1, 2], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('case', MIXED_3X3_CASES, ids=lambda c: 'x'.join(map(str, c[:5])))
+def test_mixed_3x3_store_modes_are_exact(lib, case, dtype):
+    """Forward (stored, with bias) and data gradient (stored and accumulated, with bias) of the mixed-precision 3x3 kernels."""
+    n, c, h, w, k, splits = case
+    shape = (n, c, h, w, k, 3, 3, (1, 1), (1, 1))
+    p = conv_problem(shape)
+    assert_limit(p['largest'], 0, f'{shape}')
+    desc = desc_of(shape, compute_dtype=dtype)
+    x, weight, gy, bias_k, bias_c = cuda(p['x']), cuda(p['weight']), cuda(p['gy']), cuda(p['bias_k']), cuda(p['bias_c'])
+    what = f'mixed 3x3 {case} dtype={dtype}'
+    with profiled(lib) as forward:
+        y = nans(p['y'].shape)
+        check(lib.srgan_conv2d_fwd(desc, x.data_ptr(), weight.data_ptr(), bias_k.data_ptr(), y.data_ptr(), 0, stream()),
+              'srgan_conv2d_fwd')
+        assert_exact(y, p['y'] + p['bias_k'].view(1, -1, 1, 1), f'{what} forward')
+    with profiled(lib) as backward:
+        for accumulate in (0, 1):
+            start = p['old_gx'] if accumulate else torch.full(p['x'].shape, NAN, dtype=torch.float64)
+            gx = cuda(start)
+            check(lib.srgan_conv2d_bwd_data(desc, gy.data_ptr(), weight.data_ptr(), bias_c.data_ptr(), gx.data_ptr(), accumulate, 0,
+                                            stream()), 'srgan_conv2d_bwd_data')
+            assert_exact(gx, p['gx'] + p['bias_c'].view(1, -1, 1, 1) + (start if accumulate else 0.0),
+                         f'{what} data gradient accumulate={accumulate}')
+    assert forward.kinds == {2} and backward.kinds == {2}, f'{what}: not the 3x3 kernel\n{forward.text}{backward.text}'
+    assert {line[6] > 1 for line in backward.lines} == {splits}, f'{what}: K slices\n{backward.text}'
 
 
 @pytest.mark.parametrize('force', [0, 2])
