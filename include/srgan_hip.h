@@ -93,6 +93,9 @@ const char* srgan_last_error(void);
 #define SRGAN_FEATURE_CROWD_PATCH_DRAWS 0x80000u /* ABI 1.1, additive: srgan_crowd_draw_patches /
                                                     srgan_crowd_extract_patches_indexed (the crowd loader's patch positions drawn
                                                     on the device; the cut over per-scene tables) */
+#define SRGAN_FEATURE_EPOCH_ORDER 0x100000u /* ABI 1.1, additive: srgan_epoch_order / srgan_argsort_u64 /
+                                               srgan_epoch_batch_indices (the resident image loaders' epoch order drawn on
+                                               the device; a batch's index table cut from it by the step held in a state) */
 typedef struct srgan_capabilities_t {
   int32_t abi_version;          /* = srgan_version() */
   int32_t struct_bytes;         /* sizeof(srgan_capabilities_t) as the library was built */
@@ -621,6 +624,42 @@ int srgan_regression_evaluation_sums(const float* predictions, int64_t row_strid
 int srgan_image_batch_gather(const void* store, int store_dtype, int32_t count, int32_t C, int32_t h, int32_t w,
                              const float* labels, const int32_t* order, int64_t first, int32_t B, int32_t H, int32_t W,
                              float* out_images, float* out_labels, void* stream);
+/* The epoch order of such a database drawn on the device (SRGAN_FEATURE_EPOCH_ORDER), so that a batch is a function of
+ * (seed, step) and its launches take no argument that changes from step to step.  All pointers are device pointers.
+ * The stream.  A loader with draw id `draw` under state = uint32[4] {seed_lo, seed_hi, iteration, 0} (srgan_random_fill's)
+ * shuffles its n frames once per epoch.  With batches = n / B_global (integer division: the reference's drop_last) the
+ * state's iteration word t -- the training step -- gives the epoch e = t / batches and the batch b = t % batches.  Frame i of
+ * epoch e owns the 64-bit key
+ *     key_i = (uint64(w1) << 32) | w0,   w0..w3 = the words of Philox block i of draw `draw` with the counter's iteration
+ *     word set to e, NOT to the step: counter (i, 0, draw, e), key (seed_lo, seed_hi); w2 and w3 are unused;
+ * order[p] is the frame at sorted position p of the keys in ascending order, a tie going to the lower frame index (a stable
+ * argsort; NumPy: np.argsort(keys, kind='stable')).  Row r of the global batch of step t is frame order[b * B_global + r];
+ * the n - batches * B_global frames at the end of an epoch's order are not used in that epoch.
+ * srgan_epoch_order writes order int32[n] for the epoch of `state`.  One launch: a workgroup owns 256 frames and walks all n
+ *   keys in LDS tiles that it computes itself; every thread counts the keys in front of its own and stores order[rank] = i.
+ *   Every slot is written exactly once; no atomics, no workspace, no keys buffer; two calls give the same bits.  O(n^2)
+ *   comparisons.  conditional == 1: every workgroup reads t and returns unless t % batches == 0, so a launch recorded in a HIP
+ *   graph rebuilds the order exactly at the epoch starts and leaves it untouched otherwise; conditional == 0 always rebuilds
+ *   (first use, a loader put at a step in the middle of an epoch).
+ * srgan_argsort_u64 is the same ranking pass (the same kernel body) over n keys in memory: order = the stable argsort of
+ *   keys.  64-bit Philox ties do not occur in practice; this is where the tie rule can be exercised.
+ * srgan_epoch_batch_indices writes table[i] = order[(t % batches) * B_global + first_row + i] for i < rows, one thread per
+ *   row: rows [first_row, first_row + rows) of the global batch of step t (a data-parallel rank: first_row = rank *
+ *   local_batch).  srgan_image_batch_gather(..., order = table, first = 0, B = rows, ...) then cuts the batch and
+ *   srgan_random_advance ends it: at most four launches, none with a step-dependent argument.
+ * Before any device work: a NULL pointer, n < 1, batches < 1, draw < 0, conditional outside {0, 1}, B_global < 1,
+ *   batches * B_global > n, rows < 0, first_row < 0, first_row + rows > B_global: SRGAN_EINVAL; then n above
+ *   SRGAN_EPOCH_ORDER_MAX: SRGAN_ERANGE.  rows == 0 is a successful no-op.
+ * SRGAN_EPOCH_ORDER_MAX is a capacity of the O(n^2) rebuild, not a tuned value (the reference's largest split is 50 000
+ * frames; profiles/epoch_order.md has the rebuild's time at 2^20). */
+#define SRGAN_EPOCH_ORDER_MAX (1 << 20)
+#define SRGAN_IMAGE_BATCH_DRAW_LABELED 0x30002      /* the labeled loader's draw id: next to the crowd loaders' */
+#define SRGAN_IMAGE_BATCH_DRAW_UNLABELED 0x30003    /* the unlabeled loader's */
+int srgan_epoch_order(int32_t n, int32_t batches, int32_t conditional, int32_t draw, const uint32_t* state, int32_t* order,
+                      void* stream);
+int srgan_argsort_u64(const uint64_t* keys, int32_t n, int32_t* order, void* stream);
+int srgan_epoch_batch_indices(const int32_t* order, int32_t n, int32_t B_global, int32_t batches, int32_t first_row,
+                              int32_t rows, const uint32_t* state, int32_t* table, void* stream);
 
 /* ---- full-image (sliding-window) inference of the crowd application on the device (SRGAN_FEATURE_CROWD_FULL_IMAGE) ----
  * The reference's predict_full_example (crowd/srgan.py:332-395) without its per-window NumPy work.

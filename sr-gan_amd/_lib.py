@@ -127,6 +127,9 @@ SIGNATURES = {
     'srgan_crowd_evaluation_scratch_bytes': ([i32, i32, i64], ctypes.c_int64),
     'srgan_regression_evaluation_sums': ([vp, i64, i32, vp, vp, i32, vp, vp], ctypes.c_int),
     'srgan_image_batch_gather': ([vp, ctypes.c_int, i32, i32, i32, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp], ctypes.c_int),
+    'srgan_epoch_order': ([i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
+    'srgan_argsort_u64': ([vp, i32, vp, vp], ctypes.c_int),
+    'srgan_epoch_batch_indices': ([vp, i32, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
     'srgan_crowd_extract_windows': ([vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp], ctypes.c_int),
     'srgan_crowd_resize_bilinear': ([vp, i32, i32, i32, i32, vp, vp], ctypes.c_int),
     'srgan_crowd_blend_windows': ([vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),

@@ -260,6 +260,20 @@ class DeviceCrowdPatchLoader:
         from ..nn import draw_state
         self.state = draw_state(self.seed, step).to(self.device)
 
+    def prepare_capture(self):
+        """Device draws: the state exists before a HIP graph capture that records ``device_batch()`` (made inside it, it
+        would be a host copy)."""
+        if self.draw_mode != 'device':
+            raise ValueError("prepare_capture belongs to draws='device'")
+        if self.state is None:
+            self.start_at(0)
+        return self
+
+    def batch_shapes(self):
+        """The shapes of one batch ``(image, label, map)`` of this rank."""
+        local, size = self.local_batch_size, self.patch_size
+        return (local, 3, size, size), (local, size, size), (local, size, size)
+
     def _stream(self):
         return torch._C._cuda_getCurrentRawStream(self.device.index if self.device.index is not None
                                                   else torch._C._cuda_getDevice())

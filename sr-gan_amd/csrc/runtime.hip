@@ -109,7 +109,7 @@ int srgan_capabilities(srgan_capabilities_t* out, int32_t out_bytes) {
                   SRGAN_FEATURE_DISTRIBUTION_SUMMARIES | SRGAN_FEATURE_CONV3X3_WEIGHT_IMAGE |
                   SRGAN_FEATURE_DROPOUT | SRGAN_FEATURE_FEATURE_LOSSES | SRGAN_FEATURE_CROWD_EVALUATION |
                   SRGAN_FEATURE_SUMMARY_HISTOGRAM | SRGAN_FEATURE_REGRESSION_EVALUATION |
-                  SRGAN_FEATURE_CROWD_PATCH_DRAWS;
+                  SRGAN_FEATURE_CROWD_PATCH_DRAWS | SRGAN_FEATURE_EPOCH_ORDER;
   out->workspace_bytes = (int64_t)WORKSPACE_BYTES;
   out->max_tensor_elements = ((int64_t)1 << 31) - 1;
   return SRGAN_OK;

@@ -14,6 +14,10 @@ What changes between iterations enters through fixed device buffers that are ref
   (with ``settings.device_random_draws`` they are filled on the device by launches captured with the step, from a device
   state the step advances: nothing is drawn on the host or copied, and only an injected draw enters through a buffer);
 * Adam's update count, kept on the device (``Adam.count_on_device`` / ``srgan_adam_step_counted``).
+With ``experiment.capture_loaders`` (both training loaders in device mode: their batches are launches whose arguments do not
+depend on the step, ``device_batch()``) the iteration is handed the LOADERS instead of batches: the capture records their
+launches in front of the step, a replay copies no input, and the image loaders' conditional rebuild of the epoch order is part
+of the graph.  The loaders' states and orders are persistent buffers made before the capture (``prepare_capture``).
 
 The side streams of the eager schedule (``settings.overlap_dnn_step`` / ``overlap_gradient_penalty`` /
 ``overlap_generator_forwards``) are captured too: a ``wait_stream`` on the capturing stream forks a chain into the capture,
@@ -80,6 +84,7 @@ class CapturedIteration:
         self.records = {}
         self.eager_iterations = 0
         self.replays = 0
+        self.input_copies = 0            # batch tensors copied into static buffers in front of replays (loaders captured: none)
 
     # -------------------------------------------------------------------------------------------------------------
     def optimizers(self):
@@ -103,21 +108,35 @@ class CapturedIteration:
         e.gan_training_step(labeled_examples, labels, unlabeled_examples, step)
         self.eager_iterations += 1
 
-    def run(self, labeled_examples, labels, unlabeled_examples, step):
+    def loader_batches(self, loaders):
+        """``(labeled examples, labels, unlabeled examples)`` of one ``device_batch()`` of each of the two loaders."""
+        from .srgan import as_var
+        labeled_loader, unlabeled_loader = loaders
+        labeled_examples, labels = self.experiment.unpack_labeled(labeled_loader.device_batch())
+        return labeled_examples, labels, as_var(unlabeled_loader.device_batch()[0])
+
+    def run(self, labeled_examples, labels, unlabeled_examples, step, loaders=None):
+        """One iteration on the given batches, or -- ``loaders``: the ``(train, unlabeled)`` loaders in device mode,
+        ``experiment.captured_loaders()`` -- on batches the iteration cuts itself, inside the graph when it is replayed."""
         from .srgan import as_var
         e = self.experiment
         settings = e.settings
-        inputs = as_var((labeled_examples, labels, unlabeled_examples))
+        inputs = None if loaders is not None else as_var((labeled_examples, labels, unlabeled_examples))
         for writer in (e.dnn_summary_writer, e.gan_summary_writer):
             writer.step = step
         summary = e.dnn_summary_writer.is_summary_step() or e.gan_summary_writer.is_summary_step()
         if summary or self.eager_iterations < int(option(settings, 'step_graph_warmup')) or \
                 option(settings, 'reference_schedule'):
-            return self.eager(*inputs, step)
-        flat = _flatten(inputs, [])
+            return self.eager(*(inputs if loaders is None else self.loader_batches(loaders)), step)
+        if loaders is None:
+            flat = _flatten(inputs, [])
+            shapes = tuple(tuple(v.shape) for v in flat)
+        else:                          # no batch exists yet: the shapes the loaders will deliver, in the same order
+            flat = []
+            shapes = tuple(tuple(shape) for shape in loaders[0].batch_shapes()) + (tuple(loaders[1].batch_shapes()[0]),)
         generator_phase = step % settings.generator_training_step_period == 0
         # (the 16-bit path bakes its storage type into every launch and the static loss scale into the scaled backward)
-        batch = inputs[2].shape[0]
+        batch = shapes[-1][0]
         # host draws of THIS iteration, in the order the eager step makes them (srgan.py:286, :364, :301)
         # (a draw injected by a test is used once, exactly as the eager step would use it)
         # settings.device_random_draws: no host draw is made and none is copied -- the fills and the advance of the draws'
@@ -135,9 +154,9 @@ class CapturedIteration:
             host['z_g'] = drawn('z_g', lambda: e.draw_generator_noise(batch))
         host = {name: value.reshape(-1) if name == 'alpha' else value for name, value in host.items() if value is not None}
         # (which draws enter through a buffer is baked in too: with device draws, only the injected ones)
-        key = (tuple(tuple(v.shape) for v in flat), generator_phase, F.COMPUTE_DTYPE,
+        key = (shapes, generator_phase, F.COMPUTE_DTYPE,
                tuple(o.param_groups[0]['lr'] for o in self.optimizers()), option(settings, 'storage_dtype'),
-               float(option(settings, 'loss_scale')), tuple(sorted(host)))
+               float(option(settings, 'loss_scale')), tuple(sorted(host)), loaders is not None)
         record = self.records.get(key)
         if record is not None and record['shadows'] != self.shadow_counts():
             # a weight shadow appeared since this capture (an eager summary step, a new phase): the captured refreshes do not
@@ -145,9 +164,10 @@ class CapturedIteration:
             del self.records[key]
             record = None
         if record is None:
-            record = self.records[key] = self.capture(inputs, flat, host, step)
+            record = self.records[key] = self.capture(inputs, flat, host, step, loaders)
         for target, source in zip(record['inputs'], flat):
             F._unary_raw(F.U_COPY, source.data, out=target.data)
+            self.input_copies += 1
         for name, value in host.items():
             record['draws'][name].copy_(value, non_blocking=True)
         self.order_side_streams()
@@ -161,6 +181,9 @@ class CapturedIteration:
         record['graph'].replay()
         for optimizer, advanced in zip(self.optimizers(), record['advanced']):
             optimizer.step_count += advanced
+        for loader in loaders or ():     # the recorded batches moved the loaders' device states on
+            if hasattr(loader, 'replayed'):
+                loader.replayed()
         # The step outputs (losses, features, gradient norms: a few hundred floats) are COPIED out of the graphs' shared
         # memory pool: a later replay -- of this graph or of another one that reuses the pool as scratch -- may overwrite
         # the static tensors, and a caller may keep an iteration's losses beyond the next one.
@@ -180,9 +203,9 @@ class CapturedIteration:
         for arena in self.arenas():
             blocked16.refresh_if_stale(arena)
 
-    def capture(self, inputs, flat, host, step):
+    def capture(self, inputs, flat, host, step, loaders=None):
         e = self.experiment
-        device = flat[0].data.device
+        device = flat[0].data.device if flat else torch.device('cuda', torch.cuda.current_device())
         static = [Var(torch.empty_like(v.data)) for v in flat]
         draws = {name: torch.empty(value.shape, dtype=torch.float32, device=device) for name, value in host.items()}
         optimizers = self.optimizers()
@@ -192,7 +215,9 @@ class CapturedIteration:
         if e.device_random_draws():
             e.device_draw_state()                             # exists before the capture: made inside it, it would be a host copy
         e.prepare_dropout_streams()                           # (the same for the networks' dropout states, settings.drop_rate)
-        static_inputs = _rebuild(inputs, iter(static))
+        for loader in loaders or ():                          # (and for the loaders' states and epoch orders)
+            loader.prepare_capture()
+        static_inputs = _rebuild(inputs, iter(static)) if loaders is None else None
         injected, e.injected_draws = e.injected_draws, dict(draws)
         graph = torch.cuda.CUDAGraph()
         # ONE memory pool for every captured graph of this experiment: replays are strictly sequential and the step outputs
@@ -215,6 +240,8 @@ class CapturedIteration:
         gc.disable()
         try:
             with torch.cuda.graph(graph, pool=pool):
+                if loaders is not None:                       # the batches are cut by launches recorded with the step
+                    static_inputs = self.loader_batches(loaders)
                 e.dnn_training_step(static_inputs[0], static_inputs[1], step)
                 e.gan_training_step(static_inputs[0], static_inputs[1], static_inputs[2], step)
                 # data parallel: a replay is a closed unit -- the generator's gradient exchange and update, which the
@@ -233,5 +260,6 @@ class CapturedIteration:
             outputs[name] = dict(value) if isinstance(value, dict) else value
         # (the pack plans' device job tables are read by the captured refreshes: the record keeps them alive)
         plans = [getattr(arena, '_pack_plan', None) for arena in self.arenas()]
+        # (batches: what the recorded loaders fill on every replay, kept so that nothing else in the pool takes their place)
         return dict(graph=graph, inputs=static, draws=draws, advanced=advanced, outputs=outputs, shadows=self.shadow_counts(),
-                    plans=plans)
+                    plans=plans, batches=static_inputs if loaders is not None else None)

@@ -132,6 +132,11 @@ class Experiment(ABC):
     # How the crowd application's database loaders draw their patch positions (``crowd.data.DeviceCrowdPatchLoader``); the
     # same kind of switch: an attribute, checked (``ValueError``) in the crowd ``dataset_setup``.
     crowd_patch_draws = 'host'         # 'device': positions from the counter-based stream, a function of (seed, step)
+    # The age / driving counterpart (``data.ResidentImageLoader``, checked in ``data.database_loaders``), and whether the two
+    # training loaders are recorded WITH a captured iteration (``settings.step_graph`` on a single device: both must then draw
+    # on the device; ``captured_loaders``).
+    image_batch_draws = 'host'         # 'device': the epoch orders from the counter-based stream, a function of (seed, step)
+    capture_loaders = False            # True: a replayed iteration cuts its own batches, nothing is copied into the graph
 
     def __init__(self, settings: Settings):
         self.settings = settings
@@ -285,15 +290,41 @@ class Experiment(ABC):
     def training_loop(self):
         """The per-step hot loop (reference srgan.py:99-129)."""
         self.start_loaders_at(self.starting_step)
+        loaders = self.captured_loaders()
         train_dataset_generator = self.infinite_iter(self.train_dataset_loader)
         unlabeled_dataset_generator = self.infinite_iter(self.unlabeled_dataset_loader)
         step_time_start = datetime.datetime.now()
         for step in range(self.starting_step, self.settings.steps_to_run):
             self.adjust_learning_rate(step)
-            labeled_examples, labels = self.unpack_labeled(next(train_dataset_generator))
-            unlabeled_examples = as_var(next(unlabeled_dataset_generator)[0])
-            self.training_iteration(labeled_examples, labels, unlabeled_examples, step)
+            if loaders is not None:        # the iteration draws its own batches: eagerly, or as part of the graph
+                self.captured_iteration().run(None, None, None, step, loaders=loaders)
+            else:
+                labeled_examples, labels = self.unpack_labeled(next(train_dataset_generator))
+                unlabeled_examples = as_var(next(unlabeled_dataset_generator)[0])
+                self.training_iteration(labeled_examples, labels, unlabeled_examples, step)
             step_time_start = self.end_of_step(step, self.gan_summary_writer, step_time_start)
+
+    def captured_loaders(self):
+        """``(train loader, unlabeled loader)`` when the iteration is to take its batches from the loaders itself
+        (``capture_loaders`` with ``settings.step_graph`` on a single device), else None: today's path.  Both loaders must
+        then make a batch from launches whose arguments do not depend on the step -- ``draw_mode == 'device'`` with a
+        ``device_batch()``: the resident image loaders under ``image_batch_draws = 'device'``, the crowd patch loaders under
+        ``crowd_patch_draws = 'device'`` -- or a ``ValueError`` is raised before the first step."""
+        if not self.capture_loaders or not option(self.settings, 'step_graph') or not examples_on_gpu() or \
+                self.parallel or (self.dp is not None and self.dp.world_size > 1):
+            return None
+        loaders = self.train_dataset_loader, self.unlabeled_dataset_loader
+        for loader in loaders:
+            if getattr(loader, 'draw_mode', None) != 'device' or not hasattr(loader, 'device_batch'):
+                raise ValueError('capture_loaders needs both training loaders in device mode (image_batch_draws / '
+                                 "crowd_patch_draws = 'device'), not {}".format(type(loader).__name__))
+        return loaders
+
+    def captured_iteration(self):
+        if self._captured_iteration is None:
+            from .graph import CapturedIteration
+            self._captured_iteration = CapturedIteration(self)
+        return self._captured_iteration
 
     def training_iteration(self, labeled_examples, labels, unlabeled_examples, step):
         """The body of the reference's loop (srgan.py:104-118): the DNN step, then the GAN step.  With
@@ -301,10 +332,7 @@ class Experiment(ABC):
         once as a HIP graph and replayed
         (``graph.CapturedIteration``); summary steps and the first ``settings.step_graph_warmup`` iterations run eagerly."""
         if option(self.settings, 'step_graph') and examples_on_gpu() and self._exchanges_are_capturable():
-            if self._captured_iteration is None:
-                from .graph import CapturedIteration
-                self._captured_iteration = CapturedIteration(self)
-            return self._captured_iteration.run(labeled_examples, labels, unlabeled_examples, step)
+            return self.captured_iteration().run(labeled_examples, labels, unlabeled_examples, step)
         self.dnn_training_step(labeled_examples, labels, step)
         self.gan_training_step(labeled_examples, labels, unlabeled_examples, step)
 
@@ -1324,7 +1352,7 @@ class Experiment(ABC):
 
     def start_loaders_at(self, step):
         """Before the first batch: a loader whose batches are a function of ``(seed, step)`` (``start_at``: the crowd loaders
-        with device draws) is put at ``step``, so that a continued run cuts what the uninterrupted run cuts there."""
+        and the resident image loaders with device draws) is put at ``step``, so that a continued run cuts what the uninterrupted run cuts there."""
         for loader in (self.train_dataset_loader, self.unlabeled_dataset_loader):
             if getattr(loader, 'draw_mode', 'device') == 'device' and hasattr(loader, 'start_at'):
                 loader.start_at(step)
